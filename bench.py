@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s of the path_hip hot path on MI355X (BASELINE.json metric: Cornell box + Sponza class).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one full pass of the hot path over the workload: render every camera sample of the frame
 (generate -> trace -> shade -> shadow ... -> film) with the scene already resident in HBM.
 
+A plain run measures the headline and nothing else: set-up, W warm-up steps, K timed steps, then the result line.  With one
+process on one GPU it does not load PyTorch (phip_render returns with the frame in host memory).  `--dump-outputs DIR`
+writes the frame the last timed step delivered as DIR/film.npy (float32 (H, W, 5): R, G, B, alpha, weight; a film above
+64 MB is written as a fixed, seeded sample of its pixels, DIR/film_sample.npy + DIR/film_sample_pixel.npy).  `--full` adds
+everything else below: the other workloads, the CPU baselines, the device-resident rate and the roofline.
+
 N = 1 (the driver's BENCH run): `value` is BASELINE.json configs[1], the config the metric is quoted on -- Cornell box,
 1024x1024, 256 spp, diffuse + area light, path maxDepth=-1 rrDepth=5, gaussian rfilter (K timed steps after W warm-up
-steps) -- and the same line carries the other single-GPU configs under "workloads": C3 (Sponza-class atrium, 1920x1080,
+steps).  With --full the same line carries the other single-GPU configs under "workloads": C3 (Sponza-class atrium, 1920x1080,
 64 spp, maxDepth 8), C4 (glass room, 1920x1080, 512 spp, maxDepth 16) and a 1/16-spp slice of C5, each timed the same way
 (min(K, 3) steps after one warm-up step).
 
@@ -18,17 +24,17 @@ N > 1 (the driver's SCALE runs): `value` is the SAME config with N x the samples
 is N x the efficiency): the 32x32 blocks are dealt round-robin in the reference's spiral order over the ranks (one process
 per GPU; north_star's "pixel blocks shard across the GPUs"), every rank renders its blocks into a private full-frame film,
 and a single RCCL reduce(SUM) of the (R,G,B,alpha,weight) film onto rank 0 closes every step.  `value` = samples of the whole
-job / max-over-ranks time.  The same line carries BASELINE.json configs[4] -- the atrium at 3840x2160, 1024 spp, ONE FIXED JOB
-split N ways (strong scaling) -- under "workloads", beside the single-GPU rate of that job measured in the same run.
+job / max-over-ranks time.  With --full the same line carries BASELINE.json configs[4] -- the atrium at 3840x2160, 1024 spp,
+ONE FIXED JOB split N ways (strong scaling) -- under "workloads", beside the single-GPU rate of that job measured in the same run.
 `--workload X` with N > 1 shards the fixed job X (strong scaling).
 (Launched WITHOUT torchrun, `--gpus N` uses the library's own multi-device path instead: one host thread per GPU inside
 phip_render_device and ncclReduce from C++ -- what the Mitsuba plugin uses.)
 
-Prints ONE JSON line on rank 0 (see the driver contract).  `roofline` describes the dominant kernel of the `value`
-workload with two honest fractions (neither can exceed 1): hbm = PMC-measured HBM bytes per launch / live launch time /
-8 TB/s, valu = active lane-operations / lane-slots (SQ counters); `cpu_baseline` is the reference itself (oracle/_ref,
-Mitsuba 0.6 compiled from /root/reference) -- or the CPU oracle port where that is not built -- timed on this node's host
-cores on a bounded sample, BEFORE the GPU phase.
+Prints ONE JSON line on rank 0 (see the driver contract).  With --full, `roofline` describes the dominant kernel of the
+`value` workload with two honest fractions (neither can exceed 1): hbm = PMC-measured HBM bytes per launch / live launch
+time / 8 TB/s, valu = active lane-operations / lane-slots (SQ counters); `cpu_baseline` is the reference itself (oracle/_ref,
+Mitsuba 0.6 compiled from the reference's sources) -- or the CPU oracle port where that is not built -- timed on this node's
+host cores on a bounded sample, BEFORE the GPU phase.  A plain run prints both as null.
 """
 import argparse
 import glob
@@ -183,9 +189,26 @@ def cpu_single_core(workload, seconds_target):
                       "sample": "%s on a %dx%d film at %d spp, one worker (%d samples, %.1f s)" % (workload, w8, h8, s, w8 * h8 * s, dt1)}))
 
 
-def time_workload(workload, steps, warmup, rank, world, local, devices, D, torch):
+class OneProcess:
+    """D of a run in one process (no torch.distributed): what mitsuba_amd.distributed does when WORLD_SIZE is 1, without loading PyTorch"""
+    @staticmethod
+    def barrier():
+        pass
+
+    @staticmethod
+    def max_over_ranks(value, device=None):
+        return float(value)
+
+    @staticmethod
+    def sum_over_ranks(value, device=None):
+        return float(value)
+
+
+def time_workload(workload, steps, warmup, rank, world, local, devices, D, torch, resident=True, keep_frame=False):
     """Renders `workload` warmup + steps times on this rank's share (blocks rank, rank + world, ... in spiral order) and
-    returns the per-rank aggregate.  Timed region: barrier + synchronize on both sides, max over ranks."""
+    returns the per-rank aggregate.  Timed region: barrier + synchronize on both sides, max over ranks.  torch=None: one
+    process, no device buffer of PyTorch's (the frame goes to pinned host memory), no device-resident pass.  resident: also
+    time the frame left in HBM.  keep_frame: the result carries a copy of the frame of the last timed step (rank 0)."""
     from mitsuba_amd import _abi as A
     from mitsuba_amd.integrator import Scene
     desc, W, H, spp, md, ntris = build_desc(workload)
@@ -196,8 +219,10 @@ def time_workload(workload, steps, warmup, rank, world, local, devices, D, torch
         scene.replicate(devices)
     accel = scene.accel_info().as_dict()
     integ, integ_name = make_integrator(md)
-    dev = torch.device("cuda", local)
-    film = torch.zeros((H, W, 5), dtype=torch.float32, device=dev)
+    resident = resident and torch is not None
+    sync = torch.cuda.synchronize if torch is not None else (lambda: None)
+    dev = torch.device("cuda", local) if torch is not None else None
+    film = torch.zeros((H, W, 5), dtype=torch.float32, device=dev) if (world > 1 or resident) else None
     extra = {"devices": devices} if devices else {}
     from mitsuba_amd.integrator import PinnedFilm
     host = PinnedFilm(W, H) if rank == 0 else None      # where the frame ends up: page-locked host memory (the metric includes the film's D2H)
@@ -225,7 +250,7 @@ def time_workload(workload, steps, warmup, rank, world, local, devices, D, torch
 
     for _ in range(warmup):
         step()
-    D.barrier(); torch.cuda.synchronize()
+    D.barrier(); sync()
     t0 = time.perf_counter()
     agg = {}
     step_s = []                                          # wall time of every timed step on this rank (a step returns with the frame in host memory: it is synchronous)
@@ -235,26 +260,30 @@ def time_workload(workload, steps, warmup, rank, world, local, devices, D, torch
         step_s.append(time.perf_counter() - ts)
         for k, v in st.as_dict().items():
             agg[k] = agg.get(k, 0) + v
-    D.barrier(); torch.cuda.synchronize()
+    D.barrier(); sync()
     dt = D.max_over_ranks(time.perf_counter() - t0, dev)
     total_samples = D.sum_over_ranks(agg["samples"], dev)
     total_rays = D.sum_over_ranks(agg["closest_rays"] + agg["shadow_rays"], dev)
-    # beside it: the frame left in HBM, timed the same way on fewer steps
-    rsteps = max(1, min(steps, 5))
-    step_resident()
-    D.barrier(); torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(rsteps):
+    frame = host.storage.copy() if (keep_frame and host is not None) else None      # what the caller of the timed path received in the last step
+    dt_res = None
+    if resident:
+        # beside it: the frame left in HBM, timed the same way on fewer steps
+        rsteps = max(1, min(steps, 5))
         step_resident()
-    D.barrier(); torch.cuda.synchronize()
-    dt_res = D.max_over_ranks(time.perf_counter() - t1, dev) / rsteps
+        D.barrier(); sync()
+        t1 = time.perf_counter()
+        for _ in range(rsteps):
+            step_resident()
+        D.barrier(); sync()
+        dt_res = D.max_over_ranks(time.perf_counter() - t1, dev) / rsteps
     scene.close()
     del film
     if host is not None:
         host.close()
     return {"workload": workload, "scene": WORKLOADS[workload][0], "triangles": ntris, "W": W, "H": H, "spp": spp, "integrator": integ_name,
             "accel": accel, "agg": agg, "dt": dt, "steps": steps, "warmup": warmup, "samples": total_samples, "rays": total_rays,
-            "scene_create_ms": t_create * 1e3, "d2h_ms": agg.get("d2h_ms", 0.0) / max(steps, 1), "dt_resident_per_step": dt_res, "step_s": step_s}
+            "scene_create_ms": t_create * 1e3, "d2h_ms": agg.get("d2h_ms", 0.0) / max(steps, 1), "dt_resident_per_step": dt_res, "step_s": step_s,
+            "frame": frame}
 
 
 def dominant_kernel(r):
@@ -396,7 +425,7 @@ def roofline(r):
     return out
 
 
-def summary(r, world):
+def summary(r, world, full=True):
     a = r["agg"]
     msps = r["samples"] / 1e6 / r["dt"]
     ss = sorted(r.get("step_s") or [])
@@ -415,7 +444,27 @@ def summary(r, world):
             "value_device_resident": round(r["samples"] / r["steps"] / 1e6 / r["dt_resident_per_step"], 3) if r.get("dt_resident_per_step") else None,
             "value_note": "value = samples / wall time of phip_render INCLUDING the film's device-to-host copy into page-locked host memory (film_d2h_ms per frame, "
                           "SURVEY 8(d)); value_device_resident = the same frame left in HBM (phip_render_device)",
-            "roofline": roofline(r)}
+            "roofline": roofline(r) if full else None}
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, frame):
+    """DIR/film.npy: the frame of the last timed step as the caller of phip_render receives it, (H, W, 5) float32.  A frame above DUMP_BYTES
+    is written as a fixed sample of its pixels (seed 0, the same for every build): film_sample.npy (n, 5) and their flat indices y * W + x
+    (film_sample_pixel.npy, float64)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(path, "film.npy"), frame)
+        return
+    flat = frame.reshape(-1, frame.shape[-1])
+    n = (DUMP_BYTES - 4096) // (flat.shape[1] * 4 + 8)            # (4 KB: the two files' .npy headers)
+    pix = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=n, replace=False))
+    np.save(os.path.join(path, "film_sample.npy"), flat[pix])
+    np.save(os.path.join(path, "film_sample_pixel.npy"), pix.astype(np.float64))
 
 
 def main():
@@ -427,27 +476,42 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-single-core", default=None, choices=list(WORKLOADS), help="(helper process of cpu_baseline) time ONE CPU worker on this workload and print one JSON object")
     ap.add_argument("--cpu-seconds", type=float, default=4.0)
-    ap.add_argument("--full-c5", action="store_true", help="N = 1: also time the whole 1024-spp 4K job (configs[4]) on one GPU, one step (~13 s): the same-build denominator of an N-GPU line")
-    ap.add_argument("--no-extra", action="store_true", help="N = 1: skip the C3 / C4 / C5-slice workloads")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the other workloads, the CPU baselines, the device-resident rate and the roofline "
+                                                         "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the frame of the last timed step of the headline to DIR/*.npy (float32)")
+    ap.add_argument("--full-c5", action="store_true", help="N = 1: --full, and also time the whole 1024-spp 4K job (configs[4]) on one GPU, one step (~13 s): the same-build denominator of an N-GPU line")
+    ap.add_argument("--no-extra", action="store_true", help="with --full, N = 1: skip the C3 / C4 / C5-slice workloads")
     args = ap.parse_args()
     if args.cpu_single_core:
         cpu_single_core(args.cpu_single_core, args.cpu_seconds)
         return
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = args.full or args.full_c5
 
-    import torch
-    from mitsuba_amd import _ffi, distributed as D
+    from mitsuba_amd import _ffi
 
-    rank, world, local = D.init_from_env()
+    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and not full:
+        # one process on one GPU: phip_render delivers the frame to host memory, PyTorch has nothing to do
+        torch, D = None, OneProcess
+        rank, world, local = 0, 1, int(os.environ.get("LOCAL_RANK", "0"))
+        if _ffi.lib().phip_device_count() <= local:
+            raise SystemExit("bench.py needs a GPU: path_hip has no CPU fallback (%s)" % _ffi.last_error())
+    else:
+        import torch
+        from mitsuba_amd import distributed as D
+        rank, world, local = D.init_from_env()
     in_library = world == 1 and args.gpus > 1          # no torchrun: the library's own multi-device path
     if world != args.gpus and not in_library:
         # a line whose n_gpus is not the --gpus that was asked for would be read as that N's measurement: refuse
         raise SystemExit("bench.py: WORLD_SIZE=%d but --gpus %d: launch with `python -m torch.distributed.run --nnodes=1 --nproc-per-node %d ... bench.py --gpus %d`"
                          % (world, args.gpus, args.gpus, args.gpus))
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a GPU: path_hip has no CPU fallback")
-    if in_library and torch.cuda.device_count() < args.gpus:
-        raise SystemExit("bench.py --gpus %d: only %d GPU(s) visible" % (args.gpus, torch.cuda.device_count()))
-    torch.cuda.set_device(local)
+    if torch is not None:
+        if not torch.cuda.is_available():
+            raise SystemExit("bench.py needs a GPU: path_hip has no CPU fallback")
+        if in_library and torch.cuda.device_count() < args.gpus:
+            raise SystemExit("bench.py --gpus %d: only %d GPU(s) visible" % (args.gpus, torch.cuda.device_count()))
+        torch.cuda.set_device(local)
     n_gpus = args.gpus if in_library else world
     devices = list(range(args.gpus)) if in_library else None
 
@@ -459,7 +523,7 @@ def main():
         headline = "cornell_%dx%d_%dspp" % (w_, h_, spp_ * n_gpus)
         WORKLOADS[headline] = (name, w_, h_, spp_ * n_gpus, md_)
     cpu, cpu_extra = None, {}
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(headline)                   # before the GPU phase: the GPU is busy for the rest of the run
         if not args.workload and not args.no_extra:
             for wl in CPU_BASELINE_EXTRA:
@@ -467,14 +531,16 @@ def main():
 
     steps, warmup = args.steps, args.warmup
     single = None
-    main_r = time_workload(headline, steps, warmup, rank, world, local, devices, D, torch)
+    main_r = time_workload(headline, steps, warmup, rank, world, local, devices, D, torch, resident=full, keep_frame=bool(args.dump_outputs) and rank == 0)
+    if main_r["frame"] is not None:
+        dump_outputs(args.dump_outputs, main_r.pop("frame"))
     if weak:
         main_r["profile_workload"] = HEADLINE
     extras = {}
-    if n_gpus == 1 and not args.workload and not args.no_extra:
+    if full and n_gpus == 1 and not args.workload and not args.no_extra:
         for w in EXTRA_SINGLE_GPU + ([MULTI_GPU_JOB] if args.full_c5 else []):
             extras[w] = time_workload(w, 1 if w == MULTI_GPU_JOB else min(args.steps, 3), 1 if w != MULTI_GPU_JOB else 0, rank, world, local, devices, D, torch)
-    if weak and not args.no_extra:
+    if full and weak and not args.no_extra:
         # BASELINE.json configs[4]: the 4K atrium at 1024 spp as ONE FIXED JOB split N ways (strong scaling).  8.5 G samples per step (about 12 s on one GPU): a bounded
         # number of steps keeps every N inside the driver's time limit.  Its denominator: the SAME job on ONE GPU, unsharded, at 1/16 of the samples per pixel (the rate
         # does not depend on the sample count at this size: --full-c5 on the N = 1 line times all of it), measured in this very run by rank 0 alone
@@ -486,7 +552,7 @@ def main():
         extras[MULTI_GPU_JOB] = time_workload(MULTI_GPU_JOB, min(steps, MULTI_GPU_MAX_STEPS), min(warmup, 1), rank, world, local, devices, D, torch)
 
     if rank == 0:
-        s = summary(main_r, world)
+        s = summary(main_r, world, full)
         out = {
             "metric": "Msamples/s", "value": s["value"], "unit": "Msamples/s", "n_gpus": n_gpus,
             "steps": steps, "warmup": warmup, "ms_per_step": s["ms_per_step"],
@@ -504,7 +570,8 @@ def main():
         }
         if n_gpus > 1:
             out["requested"] = {"steps": args.steps, "warmup": args.warmup}
-            out["roofline"]["scope"] = "the dominant kernel of ONE rank's share of the job (rank 0): the N-GPU line prices no collective -- the film reduce is reduce_ms of the library path / inside ms_per_step here"
+            if out["roofline"] is not None:
+                out["roofline"]["scope"] = "the dominant kernel of ONE rank's share of the job (rank 0): the N-GPU line prices no collective -- the film reduce is reduce_ms of the library path / inside ms_per_step here"
             out["cpu_baseline_note"] = "no CPU baseline on the N > 1 line (the N = 1 line carries one per workload)"
             if weak:
                 out["scaling_note"] = ("weak scaling: %d x the samples per pixel of the N = 1 line's config (%s) on %d GPUs -- value(N) / value(1) / N is the efficiency; "

@@ -202,7 +202,7 @@ def test_reference_render_job_multi_threaded(ref, oracle):
     assert abs(rgb2.mean() - o2.mean()) / o2.mean() < 0.03
 
 
-def test_reference_with_correctly_rounded_libm_is_bit_identical_to_the_parity_build():
+def test_reference_with_correctly_rounded_libm_is_bit_identical_to_the_parity_build(ref):
     """The one difference between Mitsuba 0.6 and the arithmetic the GPU kernels run (oracle parity build) is libm: with
     oracle/_build/libcrm.so LD_PRELOADed -- the reference's sincosf / expf / logf / acosf / atan2f / atanf / tanf / powf calls
     answered by the correctly rounded functions of include/phip_fmath.h -- the REFERENCE's own `path` integrator produces the

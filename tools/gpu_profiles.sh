@@ -16,12 +16,12 @@ for w in "cornell 256 cornell_1024x1024_256spp" "atrium 64 atrium_1920x1080_64sp
   for k in traffic valu tcp; do [ -s $out/${k}_$3.json ] && cp $out/${k}_$3.json profiles/${prefix}_${k}_$3.json; done
 done
 fi
-timeout 1500 python bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-5} > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
+timeout 1500 python bench.py --full --steps ${STEPS:-20} --warmup ${WARMUP:-5} > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
 python - <<PY
 import json
 d = json.load(open('$out/bench.json'))
 print(d['value'], d['ms_per_step'], {k: v['value'] for k, v in d.get('workloads', {}).items()}, d['roofline']['kernel_ms_per_step'], d['roofline']['bound'], d['roofline'].get('fractions'), (d.get('cpu_baseline') or {}).get('value'))
 PY
-(cd /tmp; export TMPDIR=/tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $root/$out/prof -o bench --output-format csv -- python $root/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $root/$out/prof_bench.json 2> $root/$out/prof.err)
-f=$(find $out/prof -name "*kernel_trace.csv" | head -1); python tools/rocprof_summary.py $f "bench.py --steps 2 --warmup 1 --no-cpu-baseline (C2 + C3 + C4 + C5 slice + mixed Cornell box + C2 with direct + the two sphere boxes), MI355X" > $out/kernel_stats.md 2>&1; head -16 $out/kernel_stats.md
+(cd /tmp; export TMPDIR=/tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $root/$out/prof -o bench --output-format csv -- python $root/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $root/$out/prof_bench.json 2> $root/$out/prof.err)
+f=$(find $out/prof -name "*kernel_trace.csv" | head -1); python tools/rocprof_summary.py $f "bench.py --full --steps 2 --warmup 1 --no-cpu-baseline (C2 + C3 + C4 + C5 slice + mixed Cornell box + C2 with direct + the two sphere boxes), MI355X" > $out/kernel_stats.md 2>&1; head -16 $out/kernel_stats.md
 rm -rf $out/pmc/*_agent_info.csv $out/pmc/*kernel_trace.csv $out/prof gpurun_out/pmc_traffic
