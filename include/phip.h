@@ -339,7 +339,7 @@ typedef struct phip_stats {
     double   trace_kernel_bytes;     /* the closest-hit kernel's share: node + triangle + ray + hit bytes */
     double   fused_kernel_ms;        /* ... of k_mega (scenes that fit LDS: the whole path in one kernel) */
     double   reduce_ms;              /* multi-device: ncclReduce of the films + its synchronisation, host wall clock */
-    uint32_t fused;                  /* 1: the call ran the fused kernel (then trace/shadow/shade ms are 0) */
+    uint32_t fused;                  /* 1: the call ran the fused kernel for the whole frame, on every device (then trace/shadow/shade ms are 0); 0 when any pass was rendered again on the wavefront kernels */
     uint32_t n_devices;              /* devices that rendered (counters are summed over them, *_ms are the maximum) */
     double   d2h_ms;                 /* (ABI 7) phip_render: the film's device-to-host copy, host wall clock; included in render_ms */
 } phip_stats;

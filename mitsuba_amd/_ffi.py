@@ -147,11 +147,13 @@ def _build_locked(sid, out_lib, verbose):
     return out_lib
 
 
-# The libraries of two GPU tests (tests/test_gpu_parity.py): the product's sources with a fault or a limit compiled in.  __graft_entry__.build() makes them in the build
+# The libraries of three GPU tests (tests/test_gpu_parity.py): the product's sources with a fault or a limit compiled in.  __graft_entry__.build() makes them in the build
 # container so that they travel with the snapshot (a whole-library build on the GPU box costs the suite two minutes each); the tests call the same function, which
 # returns at once when the file carries the current build id.
-TEST_VARIANTS = {"fault": "-DMEGA_MB_FAULT=1",       # the first wave of every fused launch reports that it gave up: the frame must come from the re-rendered pass
-                 "cap32": "-DWP_CAP=32u"}            # 32-entry task stacks: nearly every push of a big scene spills to memory
+TEST_VARIANTS = {"fault": "-DMEGA_MB_FAULT=1",       # waves of fused launches report that they gave up (by default the first wave of every launch; PHIP_TEST_FAULT_* in phip.hip
+                                                     # choose others): the frame must come from the re-rendered pass
+                 "cap32": "-DWP_CAP=32u",            # 32-entry task stacks: nearly every push of a big scene spills to memory
+                 "overflow": "-DWP_CAP=64u -DWP_SPILL_CAP=64u"}      # 128-entry task stacks, half of them spilled: the tree-in-memory scenes outgrow them -- the wave stops, the pass is re-rendered
 
 
 def build_test_variant(tag):

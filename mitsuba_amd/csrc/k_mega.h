@@ -48,10 +48,7 @@
 #ifndef MEGA_MB_DIAG
 #define MEGA_MB_DIAG 0
 #endif
-#ifndef MEGA_MB_FAULT
-#define MEGA_MB_FAULT 0              /* fault injection (tests/test_gpu_dropin.py builds it): the first wave of the grid reports that it gave up -- the host must then re-render the pass on the
-                                        wavefront kernels and deliver the same frame (phip.hip) */
-#endif
+/* MEGA_MB_FAULT (fault injection): k_pool.h */
 #ifndef MEGA_MAILBOX_QMC
 #define MEGA_MAILBOX_QMC 1           /* the mailboxes in the QMC builds of k_mega<MM_ALL> as well (0: they keep the class deal, as in round 5) */
 #endif
@@ -165,7 +162,7 @@ template <int MM, bool STRICT, int FLAT /* 0: BVH4 walk, 1: flat leaf table (tra
     unsigned char *const waveDeal = wideDeal + waveInBlock * WAVE_BYTES;
     WaveBalance wb = waveBalanceAt(g_smem, waveInBlock);
     if (WIDE) { wb.slot = (lds_u64 *) waveDeal; wb.list = (lds_u16 *) (waveDeal + 2u * 64u * 8u); }
-    bool poolOverflow = false;                                  /* POOL: a task stack ran out of LDS + spill (the host refuses the frame, as for a mailbox time-out) */
+    bool poolOverflow = false;                                  /* POOL: a task stack ran out of LDS + spill (the wave reports that it gave up, as for a mailbox time-out) */
 #if MEGA_REGEN_QUEUE
     uint32_t qHead = 0, qCount = 0;                             /* the wave's queue of prepared camera samples (wave-uniform) */
     V3 camO;                                                    /* the origin cameraRay returns for every sample (dv_scene.h: the camera-to-world translation, by its own expression) */
@@ -743,6 +740,11 @@ template <int MM, bool STRICT, int FLAT /* 0: BVH4 walk, 1: flat leaf table (tra
 #endif
     /* per-wave statistics (one owner per entry, no atomics) */
     PathPool P; P.stat = M.stat; P.nWaves = M.nWaves;
+    bool gaveUp = __any((MAILBOX && mbTimedOut) || (POOL && poolOverflow));          /* (wave-uniform) */
+#if MEGA_MB_FAULT
+    const bool faulty = M.faultWaves == 3u || (M.faultWaves == 2u && waveId < BLOCK / 64u) || (M.faultWaves == 1u && waveId == 0u);
+    if (faulty && M.faultShort != 2u) gaveUp = true;
+#endif
     const int rows[MC_COUNT] = { ST_SAMPLES, ST_VERTICES, ST_CLOSEST_RAYS, ST_NODE, ST_TRI, ST_SHADOW_RAYS, ST_SH_NODE, ST_SH_TRI };
 #pragma unroll
     for (int i = 0; i < MC_COUNT; ++i) {
@@ -752,8 +754,13 @@ template <int MM, bool STRICT, int FLAT /* 0: BVH4 walk, 1: flat leaf table (tra
                 val = i == MC_SAMPLES ? wc[WC_SAMPLES] : i == MC_VERTICES ? wc[WC_VERTICES] : i == MC_RAYS ? wc[WC_RAYS] : i == MC_NODE ? (wc[WC_STEPS] & 0xFFFFFFFFull)
                     : i == MC_TRI ? (wc[WC_STEPS] >> 32) : i == MC_SH_RAYS ? wc[WC_SH_RAYS] : i == MC_SH_NODE ? (wc[WC_SH_STEPS] & 0xFFFFFFFFull) : (wc[WC_SH_STEPS] >> 32);
         } else val = ldsCount[WCNT ? 0 : i][WCNT ? 0 : threadIdx.x];
-        const bool poison = (MAILBOX && mbTimedOut) || (POOL && __any(poolOverflow)) || (MEGA_MB_FAULT && waveId == 0u);
-        waveStat(P, rows[i], waveId, val + ((i == MC_SAMPLES && poison && lane == 0u) ? (1ull << 62) : 0ull));
+#if MEGA_MB_FAULT
+        if (i == MC_SAMPLES && faulty && M.faultShort && lane == 0u) val -= 1ull;      /* (a wave that counted no sample wraps its entry: the row's sum is still one short) */
+#endif
+        waveStat(P, rows[i], waveId, val);
     }
+    /* a wave that gave up says so in a row of its own (ST_GAVE_UP: one owner per entry, zeroed by the host before the launch); the host discards the pass whenever the
+       row's sum is not zero */
+    if (gaveUp && lane == 0u) P.stat[(size_t) ST_GAVE_UP * P.nWaves + waveId] = 1ull;
 }
 

@@ -63,7 +63,9 @@ __host__ __device__ __forceinline__ uint32_t hitClass(uint32_t w) { return w == 
 /* Work counters are kept per wave (one owner, plain read-modify-write, no atomics: a single
  * contended word saturates at ~88 atomics/us on MI355X) in SoA arrays stat[k][waveId] and summed
  * by k_reduce_stats when the host wants them. */
-enum { ST_CLOSEST_RAYS = 0, ST_NODE, ST_TRI, ST_SHADOW_RAYS, ST_SH_NODE, ST_SH_TRI, ST_VERTICES, ST_SAMPLES, ST_ALIVE, ST_COUNT };
+/* ST_GAVE_UP: k_mega only -- 1 in the entry of a wave that gave up on the pass (a mailbox wait timed out, a task stack outgrew LDS + spill): the host re-renders the pass.
+   A row of its own, not a poison added to ST_SAMPLES: a sum of 0/1 entries cannot wrap to zero, nor cancel against samples that are missing */
+enum { ST_CLOSEST_RAYS = 0, ST_NODE, ST_TRI, ST_SHADOW_RAYS, ST_SH_NODE, ST_SH_TRI, ST_VERTICES, ST_SAMPLES, ST_ALIVE, ST_GAVE_UP, ST_COUNT };
 
 #define EMITTER_LDS_FLOATS 1024      /* emitter table staged in LDS by the shading kernels when it has at most this many floats (4 KB) */
 #define MATERIAL_LDS_MAX 48          /* ... and the materials when there are at most this many (4.5 KB) */
@@ -88,6 +90,10 @@ enum { ST_CLOSEST_RAYS = 0, ST_NODE, ST_TRI, ST_SHADOW_RAYS, ST_SH_NODE, ST_SH_T
 #define DYN_SHARDS 8                    /* one dynamic-sample counter per XCD-sized group of blocks */
 #define DYN_STRIDE 16                   /* unsigned long longs between counters (128 B) */
 
+#ifndef MEGA_MB_FAULT
+#define MEGA_MB_FAULT 0              /* fault-injection build (_ffi.TEST_VARIANTS "fault", tests/test_gpu_parity.py): waves of k_mega report that they gave up, as the host
+                                        (phip.hip) selects -- it must then re-render the pass on the wavefront kernels and deliver the same frame.  The product compiles none of it */
+#endif
 /* k_mega (k_mega.h): the fused single-kernel path for scenes that fit LDS */
 struct MegaParams {
     unsigned long long *nextId;      /* the pass's sample-id counter (zeroed by the host) */
@@ -97,6 +103,10 @@ struct MegaParams {
     /* k_mega<.., FLAT >= 4, ..> (the tree in memory: k_wide_wave.h) */
     uint32_t nodeCache;              /* top-of-tree nodes (BFS order) every block stages in LDS */
     uint32_t *spill;                 /* overflow of the group stacks: SPILL_DEPTH words per lane of the grid */
+#if MEGA_MB_FAULT
+    uint32_t faultWaves;             /* fault injection (phip.hip reads PHIP_TEST_FAULT_*): 0 none, 1 wave 0, 2 the four waves of block 0, 3 every wave reports that it gave up */
+    uint32_t faultShort;             /* 1: the poisoned waves also under-report one sample (a mailbox time-out leaves the pass incomplete); 2: they only under-report */
+#endif
 };
 
 struct Counters {

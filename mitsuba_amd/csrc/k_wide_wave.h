@@ -174,6 +174,10 @@ __device__ __forceinline__ void traceWideW(const DevScene &S, WideStackT<BLOCK> 
 #ifndef WP_CAP
 #define WP_CAP 256u                      /* task-stack entries per wave in LDS (8 B each): 8 KB per block -- with 512 the block's LDS (slots, ray table, pair list, node cache, camera-sample queue) costs the fourth block of a CU */
 #endif
+#ifndef WP_SPILL_CAP
+#define WP_SPILL_CAP (64u * SPILL_DEPTH / 2u)       /* task-stack entries per wave in the spill buffer (8 B each): the wave's 64 lanes' share of it, all of it */
+#endif
+static_assert(WP_SPILL_CAP <= 64u * SPILL_DEPTH / 2u, "a wave's task stack spills into its own lanes' share of the spill buffer only");
 #ifndef WP_NEAR_FIRST
 #define WP_NEAR_FIRST 1                  /* the nearest child of every lane on top of the stack (0: every lane's children together, far to near) */
 #endif
@@ -208,13 +212,15 @@ __device__ __forceinline__ void setupWidePool(const DevScene &S, uint32_t nodeCa
     unsigned char *w = smem + widePoolDealOffset(nodeCache) + waveInBlock * WP_WAVE_BYTES;
     wp.pool = (lds_u2 *) (smem + (size_t) waveInBlock * WP_CAP * sizeof(uint2));
     wp.slot = (lds_w64 *) w; wp.uvs = (lds_u2 *) (w + 128u * 8u); wp.srays = (lds_f4 *) (w + 128u * 8u + 64u * 8u); wp.pairs = (lds_w32 *) (w + 128u * 8u + 64u * 8u + 64u * 32u);
-    wp.spill = (unsigned long long *) (spillBlock + (size_t) waveInBlock * 64u * SPILL_DEPTH); wp.spillCap = 64u * SPILL_DEPTH / 2u;
+    wp.spill = (unsigned long long *) (spillBlock + (size_t) waveInBlock * 64u * SPILL_DEPTH); wp.spillCap = WP_SPILL_CAP;
     wp.nodes = (lds_cu4 *) ln; wp.nodeCache = nodeCache;
 }
 
 #define WP_OCCLUDED 0xBF80000000000000ull    /* an any-hit ray that found a hit: interval end -1 */
-/* Every lane of the wave must call, converged; goS / goC = this lane has an any-hit / a closest-hit ray (clipped: (o, d, mint', maxt')).  `overflow` is set when the
-   task stack ran out of LDS + spill (the caller refuses the frame).  wc: node visits | triangle tests << 32 of the wave's any-hit / closest-hit rays (LDS, lane 0 adds). */
+/* Every lane of the wave must call, converged; goS / goC = this lane has an any-hit / a closest-hit ray (clipped: (o, d, mint', maxt')).  `overflow` is set on every
+   lane when the task stack ran out of LDS + spill: the traversal stops there (every task and pair is dropped, no stack entry at or above `room` is ever read), and a
+   call that finds it set already traces nothing -- the rays of the wave miss, its paths end quickly, and k_mega reports that the wave gave up, so that the host discards
+   the pass and renders it again on the wavefront kernels (phip.hip).  wc: node visits | triangle tests << 32 of the wave's any-hit / closest-hit rays (LDS, lane 0 adds). */
 template <bool HAVE_S, bool HAVE_C>
 __device__ __forceinline__ void traceWidePool(const DevScene &S, const WidePool &wp, const uint32_t lane,
                                               bool goS, const V3 &oS, const V3 &dS, const float mintS, const float maxtS,
@@ -227,11 +233,13 @@ __device__ __forceinline__ void traceWidePool(const DevScene &S, const WidePool 
     };
     auto poolRead = [&](uint32_t i) -> uint2 {
         if (i < WP_CAP) { const u2v t = wp.pool[i]; return make_uint2(t.x, t.y); }
+        if (i - WP_CAP >= wp.spillCap) return make_uint2(0u, 0u);      /* (unreachable: count <= room below; an empty triangle group, not a word past the wave's slice) */
         const unsigned long long v = __hip_atomic_load(wp.spill + (i - WP_CAP), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      /* (written by another lane of this wave: past the L1) */
         return make_uint2((uint32_t) v, (uint32_t) (v >> 32));
     };
     if (!HAVE_S) goS = false;
     if (!HAVE_C) goC = false;
+    if (__any(overflow)) { overflow = true; goS = goC = false; }       /* an earlier traversal of this wave overflowed: trace nothing (its pass is discarded) */
     /* the rays' slots: the interval's end, no hit; the any-hit rays' table */
     if (HAVE_C) wp.slot[lane] = ((unsigned long long) pm_to_bits(goC ? maxt : -1.0f) << 32) | 0xFFFFFFFFull;
     if (HAVE_S) {
@@ -248,6 +256,8 @@ __device__ __forceinline__ void traceWidePool(const DevScene &S, const WidePool 
     uint32_t nNodeS = 0, nNodeC = 0, nTriS = 0, nTriC = 0;      /* (wave-uniform) */
     const uint32_t room = WP_CAP + wp.spillCap;
     uint32_t nQ = 0;                                            /* (ray, record) pairs that wait in the queue (wave-uniform) */
+    /* every push writes the stack positions [count before, count after) without gaps, so a push went past the stack iff count > room: then the wave stops */
+    if (count > room || __any(overflow)) { overflow = true; count = 0u; }
     WD_SYNC()
 #define WP_BPERM(srcLane4, x) pm_from_bits((uint32_t) __builtin_amdgcn_ds_bpermute(srcLane4, (int) pm_to_bits(x)))
     /* the ray of a task (every lane must execute: ds_bpermute): origin, direction, interval */
@@ -344,6 +354,7 @@ __device__ __forceinline__ void traceWidePool(const DevScene &S, const WidePool 
             }
             count += nRest + (uint32_t) __popcll(topMask);
         }
+        if (count > room || __any(overflow)) { overflow = true; count = 0u; nQ = 0u; }      /* overflow: drop every task and pair, leave the loop (wave-uniform) */
         WD_SYNC()
         /* ---- the triangle steps: one pair per lane; only FULL steps while node visits are left (a step costs its ~100 instructions whatever the number of its pairs:
                 the remainder waits for the pairs of the next iteration), everything when the stack is empty ---- */

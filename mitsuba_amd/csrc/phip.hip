@@ -1064,9 +1064,19 @@ static void validateParams(const phip_scene *sc, const phip_render_params *p) {
     if (p->n_devices > 1 && p->stream) throw std::invalid_argument("a caller's stream belongs to one device: leave `stream` NULL when n_devices > 1 (every device renders on a stream of the library)");
 }
 
+/* The rest of a job whose fused pass gave up (renderOnDevice calls itself with p = the remaining samples, on the wavefront kernels): what the job had before it.  The
+   continuation writes the caller's sample buffer at the caller's stride, reports progress against the caller's total and keeps what the job's earlier passes left. */
+struct JobSoFar {
+    uint32_t spp;                     /* the caller's spp: the sample buffer's stride, the progress callback's total */
+    int sampleOffset;                 /* the caller's sample_offset: sample k of the job is at k - sampleOffset in a pixel's row of the sample buffer */
+    unsigned long long samplesDone;   /* samples of the passes that are in the film already */
+    bool accumulate;                  /* the caller's PHIP_FLAG_ACCUMULATE: a cancelled job leaves dOut as it is, instead of clearing it */
+};
+
 /* One device's share of a render call: the blocks whose index in the reference's spiral order is congruent to shardIndex
    modulo shardCount, into dOut (device memory of sd.device).  The caller holds the scene's render lock and has validated p. */
-static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params *p, int shardIndex, int shardCount, float *dOut, phip_stats *stats) {
+static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params *p, int shardIndex, int shardCount, float *dOut, phip_stats *stats,
+                          const JobSoFar *job = nullptr) {
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     const bool direct = p->integrator == PHIP_INTEGRATOR_DIRECT;
@@ -1117,8 +1127,10 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
         sppPerPass = (uint32_t) std::min<unsigned long long>(cap, (unsigned long long) p->spp);
     }
     const bool keepSamples = (p->flags & PHIP_FLAG_SAMPLE_BUFFER) != 0;
-    if (keepSamples) { sd.sampleOut.alloc((size_t) W * H * (size_t) p->spp); HIP_TRY(hipMemsetAsync(sd.sampleOut.p, 0, sd.sampleOut.n * sizeof(float4), stream)); }
-    sd.haveSamples = keepSamples; sd.lastSpp = (uint32_t) p->spp;
+    const uint32_t jobSpp = job ? job->spp : (uint32_t) p->spp;                 /* (a continuation: the caller's job, of which p is the rest) */
+    const int jobOffset = job ? job->sampleOffset : p->sample_offset;
+    if (keepSamples && !job) { sd.sampleOut.alloc((size_t) W * H * (size_t) p->spp); HIP_TRY(hipMemsetAsync(sd.sampleOut.p, 0, sd.sampleOut.n * sizeof(float4), stream)); }
+    sd.haveSamples = keepSamples; sd.lastSpp = jobSpp;
 
     const unsigned long long idsFirstPass = idsPerSpp * sppPerPass;
     if (sd.L.n < idsFirstPass) sd.L.alloc((size_t) idsFirstPass);
@@ -1214,14 +1226,15 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
     EventList evTrace, evShadow, evShade, evFilm, evFused;
     const unsigned long long samplesTotal = sd.localPixels;                  /* crop pixels of this device's blocks */
 
-    HIP_TRY(hipMemsetAsync(sd.invalid.p, 0, sizeof(unsigned long long), stream));
+    if (!job) HIP_TRY(hipMemsetAsync(sd.invalid.p, 0, sizeof(unsigned long long), stream));
     int nCU = 256; { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, sd.device) == hipSuccess) nCU = prop.multiProcessorCount; }
     const size_t ldsBytes = traversalLdsBytes(D);
     const dim3 block(BLOCK);
     Counters hc;
     bool cancelled = false;
     bool accumulate = (p->flags & PHIP_FLAG_ACCUMULATE) != 0;
-    unsigned long long samplesDone = 0;
+    const bool callerAccumulate = job ? job->accumulate : accumulate;
+    unsigned long long samplesDone = job ? job->samplesDone : 0ull;
 
     /* wavefront state (allocated only when that path runs) */
     uint32_t capacity = 0, nWaves = 0, nBlocks = 0;
@@ -1327,6 +1340,9 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
 
     /* fused path: resident grid and per-wave statistics rows */
     dim3 megaGrid(1); MegaParams M; memset(&M, 0, sizeof(M));
+#if MEGA_MB_FAULT
+    uint32_t faultWaves = 0; int faultPass = -1;
+#endif
     if (fused) {
         megaGrid = dim3((unsigned) (nCU * megaPerCU));
         M.nWaves = megaGrid.x * (BLOCK / 64);
@@ -1340,6 +1356,17 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
         }
         int *dflag = nullptr; HIP_TRY(hipHostGetDevicePointer((void **) &dflag, sc->cancelFlag, 0));
         M.cancel = dflag;
+#if MEGA_MB_FAULT
+        /* fault-injection build (tests/test_gpu_parity.py), read at every call: PHIP_TEST_FAULT_WAVES = wave0 (the default) | block (the four waves of block 0) | all | none
+           report that they gave up, in pass PHIP_TEST_FAULT_PASS of the call (default: every pass); PHIP_TEST_FAULT_SHORT = 1: they also under-report one sample each,
+           2: they only under-report (the host's exact count must catch it) */
+        {
+            const char *w = getenv("PHIP_TEST_FAULT_WAVES"), *sh = getenv("PHIP_TEST_FAULT_SHORT");
+            faultWaves = !w || !strcmp(w, "wave0") ? 1u : !strcmp(w, "block") ? 2u : !strcmp(w, "all") ? 3u : 0u;
+            faultPass = getenv("PHIP_TEST_FAULT_PASS") ? atoi(getenv("PHIP_TEST_FAULT_PASS")) : -1;
+            M.faultShort = sh ? (uint32_t) atoi(sh) : 0u;
+        }
+#endif
         P.stat = sd.stat.p; P.nWaves = M.nWaves;               /* k_reduce_stats reads these two */
     }
 
@@ -1421,6 +1448,9 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
             /* ---- one launch: every path of the pass from camera sample to its last vertex (k_mega.h) ---- */
             HIP_TRY(hipMemsetAsync(sd.megaNext.p, 0, sizeof(unsigned long long), stream));
             HIP_TRY(hipMemsetAsync(sd.stat.p, 0, (size_t) ST_COUNT * M.nWaves * sizeof(unsigned long long), stream));
+#if MEGA_MB_FAULT
+            M.faultWaves = (faultPass < 0 || (uint32_t) faultPass == sppDone / sppPerPass) ? faultWaves : 0u;
+#endif
             if (rc.totalIds) {
                 if (timing) evFused.record(stream);
                 if (direct) phipLaunchMegaDirect(sc->materialMask, false, megaFlat, qmc, megaGrid, megaLds, stream, D, M, rc, sd.L.p);
@@ -1430,26 +1460,41 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
                 iter = 1;
             }
             HIP_TRY(hipGetLastError());
-            /* k_mega bounds every wait of its mailbox protocol and the depth of its task stacks; a wave that gave up poisons its sample count (k_mega.h).  Such a pass is
-               incomplete: it is not added to the film -- this pass and the rest of the job run on the kernels that have no such protocol (round 6: degrade, do not fail) */
-            HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_SAMPLES], 0, sizeof(unsigned long long), stream));
-            hipLaunchKernelGGL(k_reduce_stats, dim3(1, REDUCE_SPLIT), dim3(256), 0, stream, P, sd.counters.p, (int) ST_SAMPLES);
-            HIP_TRY(hipMemcpyAsync(&hc.total[ST_SAMPLES], &sd.counters.p->total[ST_SAMPLES], sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+            /* k_mega bounds every wait of its mailbox protocol and the depth of its task stacks; a wave that gave up says so in the ST_GAVE_UP row (k_mega.h).  Such a pass
+               is incomplete: it is not added to the film -- this pass and the rest of the job run on the kernels that have no such protocol (round 6: degrade, do not fail).
+               A pass that was not cancelled must also have counted exactly one sample per crop pixel of this device's blocks and sample of the pass (the ids of edge
+               blocks outside the crop window are drawn and skipped: rc.totalIds counts them, the samples do not) */
+            HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_SAMPLES], 0, (ST_GAVE_UP - ST_SAMPLES + 1) * sizeof(unsigned long long), stream));
+            static_assert(ST_GAVE_UP == ST_SAMPLES + 2, "the rows the host reads after a fused pass: samples .. gave up");
+            hipLaunchKernelGGL(k_reduce_stats, dim3(ST_GAVE_UP - ST_SAMPLES + 1, REDUCE_SPLIT), dim3(256), 0, stream, P, sd.counters.p, (int) ST_SAMPLES);
+            HIP_TRY(hipMemcpyAsync(&hc.total[ST_SAMPLES], &sd.counters.p->total[ST_SAMPLES], (ST_GAVE_UP - ST_SAMPLES + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipStreamSynchronize(stream));
             if (cancelRequested(sc)) cancelled = true;
-            if (!cancelled && hc.total[ST_SAMPLES] > rc.totalIds) {
+            const bool gaveUp = hc.total[ST_GAVE_UP] != 0;
+#if MEGA_PROFILE || MEGA_MB_DIAG
+            const bool countKnown = false;              /* (measurement builds of k_mega: the sample row holds what they measure) */
+#else
+            const bool countKnown = true;
+#endif
+            if (!cancelled && (gaveUp || (countKnown && hc.total[ST_SAMPLES] != samplesTotal * rc.sppPass))) {
                 fprintf(stderr, "[phip] warning: the fused kernel gave up on this pass (%s); samples %u.. of the job are rendered by the wavefront kernels\n",
-                        megaWide ? "a task stack outgrew LDS + spill buffer" : "a mailbox wait timed out", (unsigned) (p->sample_offset + sppDone));
+                        !gaveUp ? "it counted a wrong number of samples" : megaWide ? "a task stack outgrew LDS + spill buffer" : "a mailbox wait timed out",
+                        (unsigned) (p->sample_offset + sppDone));
+                /* the rest of the job -- this pass and the ones after it -- on the wavefront kernels, as a continuation of THIS call: the same passes, the caller's sample
+                   buffer at the caller's stride, progress against the caller's total, the film of the passes before accumulated onto */
                 phip_render_params q = *p;
                 q.flags |= PHIP_FLAG_NO_MEGA | PHIP_FLAG_NO_FUSED;
                 q.sample_total = p->sample_total > 0 ? p->sample_total : p->spp;
                 q.sample_offset = p->sample_offset + (int) sppDone; q.spp = p->spp - (int) sppDone;
                 if (sppDone > 0) q.flags |= PHIP_FLAG_ACCUMULATE;
+                const JobSoFar soFar{ jobSpp, jobOffset, samplesDone, callerAccumulate };
                 phip_stats st2; memset(&st2, 0, sizeof(st2));
-                const int rc2 = renderOnDevice(sc, sd, &q, shardIndex, shardCount, dOut, &st2);
+                const int rc2 = renderOnDevice(sc, sd, &q, shardIndex, shardCount, dOut, &st2, &soFar);
                 st2.samples += st.samples; st2.closest_rays += st.closest_rays; st2.shadow_rays += st.shadow_rays; st2.path_vertices += st.path_vertices;
                 st2.closest_node_visits += st.closest_node_visits; st2.closest_triangle_tests += st.closest_triangle_tests;
                 st2.shadow_node_visits += st.shadow_node_visits; st2.shadow_triangle_tests += st.shadow_triangle_tests; st2.iterations += st.iterations;
+                st2.fused_kernel_ms += evFused.sumPairs();
+                st2.fused = 0;                                  /* (part of the frame came from the wavefront kernels) */
                 st2.render_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
                 if (stats) *stats = st2;
                 return rc2;
@@ -1532,7 +1577,7 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
                     HIP_TRY(hipStreamSynchronize(stream));
                     if (hc.total[ST_ALIVE] == 0) done = true;
                     if (hc.total[ST_ALIVE] < capacity) drainingSeen = true;
-                    if (p->progress) { std::lock_guard<std::mutex> g(sc->progressLock); p->progress(p->progress_user, sd.device, samplesDone + hc.total[ST_SAMPLES], samplesTotal * (unsigned long long) p->spp); }
+                    if (p->progress) { std::lock_guard<std::mutex> g(sc->progressLock); p->progress(p->progress_user, sd.device, samplesDone + hc.total[ST_SAMPLES], samplesTotal * (unsigned long long) jobSpp); }
                     if (cancelRequested(sc)) { cancelled = true; done = true; }
                 }
             }
@@ -1589,7 +1634,7 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
         if (keepSamples && rc.totalIds) {
             const size_t n = (size_t) W * H * rc.sppPass;
             hipLaunchKernelGGL(k_export_samples, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream, D, rc, (const float4 *) sd.L.p,
-                               (const int32_t *) sd.tileSlot.p, tilesX, sd.sampleOut.p, (uint32_t) p->spp, (uint32_t) p->sample_offset);
+                               (const int32_t *) sd.tileSlot.p, tilesX, sd.sampleOut.p, jobSpp, (uint32_t) jobOffset);
         }
         HIP_TRY(hipMemsetAsync(sd.counters.p, 0, sizeof(Counters), stream));
         hipLaunchKernelGGL(k_reduce_stats, dim3(ST_COUNT, REDUCE_SPLIT), dim3(256), 0, stream, P, sd.counters.p, 0);
@@ -1600,9 +1645,9 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
         st.path_vertices += hc.total[ST_VERTICES]; st.closest_node_visits += hc.total[ST_NODE]; st.closest_triangle_tests += hc.total[ST_TRI];
         st.shadow_node_visits += hc.total[ST_SH_NODE]; st.shadow_triangle_tests += hc.total[ST_SH_TRI];
         samplesDone += hc.total[ST_SAMPLES];
-        if (p->progress) { std::lock_guard<std::mutex> g(sc->progressLock); p->progress(p->progress_user, sd.device, samplesDone, samplesTotal * (unsigned long long) p->spp); }
+        if (p->progress) { std::lock_guard<std::mutex> g(sc->progressLock); p->progress(p->progress_user, sd.device, samplesDone, samplesTotal * (unsigned long long) jobSpp); }
     }
-    if ((nLocalTiles == 0 || cancelled) && !accumulate) { HIP_TRY(hipMemsetAsync(dOut, 0, (size_t) W * H * 5 * sizeof(float), stream)); HIP_TRY(hipStreamSynchronize(stream)); }
+    if ((nLocalTiles == 0 || cancelled) && !callerAccumulate) { HIP_TRY(hipMemsetAsync(dOut, 0, (size_t) W * H * 5 * sizeof(float), stream)); HIP_TRY(hipStreamSynchronize(stream)); }
     unsigned long long inv = 0;
     HIP_TRY(hipMemcpy(&inv, sd.invalid.p, sizeof(inv), hipMemcpyDeviceToHost));
     st.invalid_samples = inv;
@@ -1784,7 +1829,7 @@ static int renderMultiDevice(phip_scene *sc, const phip_render_params *p, float 
             t.trace_kernel_ms = std::max(t.trace_kernel_ms, a.trace_kernel_ms); t.shadow_kernel_ms = std::max(t.shadow_kernel_ms, a.shadow_kernel_ms);
             t.shade_kernel_ms = std::max(t.shade_kernel_ms, a.shade_kernel_ms); t.film_kernel_ms = std::max(t.film_kernel_ms, a.film_kernel_ms);
             t.fused_kernel_ms = std::max(t.fused_kernel_ms, a.fused_kernel_ms);
-            t.algorithmic_bytes += a.algorithmic_bytes; t.trace_kernel_bytes += a.trace_kernel_bytes; t.fused |= a.fused; t.vertex_traced |= a.vertex_traced;
+            t.algorithmic_bytes += a.algorithmic_bytes; t.trace_kernel_bytes += a.trace_kernel_bytes; t.fused = i ? (t.fused & a.fused) : a.fused; t.vertex_traced |= a.vertex_traced;
         }
         t.n_devices = (uint32_t) n;
         t.reduce_ms = std::chrono::duration<double, std::milli>(clk::now() - tr0).count();

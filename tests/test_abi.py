@@ -40,6 +40,17 @@ def test_product_library_does_not_export_the_test_hooks():
     assert "phip_debug_host_camera_ray" in dbg and "phip_debug_fmath" in dbg
 
 
+def test_product_library_reads_no_fault_knob():
+    """The fault-injection knobs (PHIP_TEST_FAULT_WAVES / _PASS / _SHORT: which waves of which fused pass report that they gave up) are read from the environment
+    by the `fault` test library only: the product compiles none of it (phip.hip, #if MEGA_MB_FAULT).  nm cannot see a getenv argument; the library's bytes can."""
+    from mitsuba_amd import _ffi
+    assert b"PHIP_TEST_FAULT" not in open(_ffi.LIB, "rb").read()
+    assert b"PHIP_TEST_FAULT" not in open(_ffi.LIB_DEBUG, "rb").read()
+    fault = _ffi.build_test_variant("fault")
+    data = open(fault, "rb").read()
+    assert b"PHIP_TEST_FAULT_WAVES" in data and b"PHIP_TEST_FAULT_PASS" in data and b"PHIP_TEST_FAULT_SHORT" in data
+
+
 def test_struct_sizes_match_ctypes_mirror(phip):
     structs = [A.phip_material, A.phip_shape, A.phip_emitter, A.phip_camera, A.phip_film, A.phip_scene_desc,
                A.phip_render_params, A.phip_stats, A.phip_ray, A.phip_hit, A.phip_accel_info]

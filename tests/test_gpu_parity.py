@@ -1007,22 +1007,23 @@ for name, sb, spp in (("mixed", S.cornell_mixed(96, 96, ft), 8), ("box", S.corne
     gs.close()
 np.savez(sys.argv[1], **out)
 """ % root
-    multi = {"PHIP_MAX_PASS_SAMPLES": str(96 * 96 * 3)}          # several passes: the continuation of a job whose k-th pass gave up accumulates onto the passes before
+    # several passes: the fault build poisons EVERY launch, so the job's first pass gives up and the whole job runs on the wavefront kernels, pass by pass (a later pass
+    # that gives up: test_late_fused_pass_that_gives_up_continues_the_job)
+    multi = {"PHIP_MAX_PASS_SAMPLES": str(96 * 96 * 3)}
     res = {}
     for tag, e in (("product", {}), ("fault", {"PHIP_LIB": lib}), ("product_multi", multi), ("fault_multi", dict(multi, PHIP_LIB=lib))):
         f = str(tmp_path / (tag + ".npz"))
-        r = subprocess.run([sys.executable, "-c", script, f], env=dict(os.environ, **e), capture_output=True, text=True)
+        r = subprocess.run([sys.executable, "-c", script, f], env=dict(os.environ, **e), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
         res[tag] = (np.load(f), r.stderr)
         assert ("warning: the fused kernel gave up" in r.stderr) == tag.startswith("fault"), (tag, r.stderr[-500:])
-    for a, b, samples in (("product", "fault", True), ("product_multi", "fault_multi", False)):
+    for a, b in (("product", "fault"), ("product_multi", "fault_multi")):
         prod, fault = res[a][0], res[b][0]
         for name in ("mixed", "box", "spheres"):
             assert prod[name + "_fused"][0] == 1 and fault[name + "_fused"][0] == 0, name                    # the product ran k_mega, the fault build ended on the wavefront kernels
             assert prod[name + "_fused"][1] == fault[name + "_fused"][1], name                                 # every sample counted once
             assert (prod[name + "_film"].view(np.uint32) == fault[name + "_film"].view(np.uint32)).all(), (a, name)
-            if samples:
-                assert (prod[name + "_samples"].view(np.uint32) == fault[name + "_samples"].view(np.uint32)).all(), name
+            assert (prod[name + "_samples"].view(np.uint32) == fault[name + "_samples"].view(np.uint32)).all(), (a, name)
 
 
 def test_task_stack_of_the_fused_kernel_spills_to_memory(gpu, gauss, tmp_path):
@@ -1057,10 +1058,266 @@ np.savez(sys.argv[1], **out)
     res = {}
     for tag, e in (("product", {}), ("cap32", {"PHIP_LIB": lib})):
         f = str(tmp_path / (tag + ".npz"))
-        r = subprocess.run([sys.executable, "-c", script, f], env=dict(os.environ, **e), capture_output=True, text=True)
+        r = subprocess.run([sys.executable, "-c", script, f], env=dict(os.environ, **e), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
         assert "warning" not in r.stderr, r.stderr[-800:]           # (no pass gave up: the stack spilled, it did not overflow)
         res[tag] = np.load(f)
     for name in ("atrium", "glass", "spheres", "direct"):
         assert (res["product"][name].view(np.uint32) == res["cap32"][name].view(np.uint32)).all(), name
         assert (res["product"][name + "_film"].view(np.uint32) == res["cap32"][name + "_film"].view(np.uint32)).all(), name
+
+
+# ---- a fused pass that gives up (k_mega.h: the ST_GAVE_UP row; phip.hip: the continuation on the wavefront kernels; k_wide_wave.h: the bounded task stack) ----
+# One child process per library (PHIP_LIB is read when the library is loaded); inside it the fault knobs of the fault-injection build (PHIP_TEST_FAULT_WAVES / _PASS /
+# _SHORT) and PHIP_MAX_PASS_SAMPLES are read at every render call, so that one child renders every case of a test.  Each case is announced on stderr, so that the
+# library's warnings can be told apart by case.
+_GIVE_UP_CHILD = r"""
+import sys, os, json
+import ctypes as C
+sys.path.insert(0, %r)
+import numpy as np
+from mitsuba_amd import _ffi, _abi as A, scene as S
+from mitsuba_amd.integrator import Scene, PathHIP, DirectHIP, VolPathSimpleHIP, HDRFilm
+ft = _ffi.gaussian_filter(0.5)
+KNOBS = ("PHIP_TEST_FAULT_WAVES", "PHIP_TEST_FAULT_PASS", "PHIP_TEST_FAULT_SHORT", "PHIP_MAX_PASS_SAMPLES")
+def scene(kind):
+    if kind == "mixed": return S.cornell_mixed(96, 96, ft), PathHIP(maxDepth=6), 0
+    if kind == "box": return S.cornell_box(64, 64, ft), PathHIP(maxDepth=6), 0
+    if kind == "spheres": return S.cornell_spheres(96, 96, ft), PathHIP(maxDepth=6), 0
+    if kind == "direct": return S.cornell_spheres(96, 96, ft), DirectHIP(shadingSamples=2), 0
+    if kind == "volpath": return S.cornell_spheres(96, 96, ft), VolPathSimpleHIP(maxDepth=8), 0
+    if kind == "atrium": return S.atrium(96, 54, ft, detail=0.3), PathHIP(maxDepth=6), A.PHIP_FLAG_FUSED_ANY
+    if kind == "ragged": return S.cornell_spheres(100, 70, ft), PathHIP(maxDepth=6), 0
+    raise ValueError(kind)
+def setenv(env):
+    for k in KNOBS:
+        os.environ.pop(k, None)
+    os.environ.update(env)
+out = {}
+for c in json.loads(sys.argv[2]):
+    name, spp = c["name"], c["spp"]
+    sys.stderr.write("@@case %%s\n" %% name); sys.stderr.flush()
+    sb, integ, flags = scene(c["scene"])
+    gs = Scene(sb.desc())
+    prog = []
+    record = lambda user, dev, done, total: prog.append((done, total))
+    if c.get("progressive"):
+        # 3 + 5 samples in two calls, the second accumulated onto the first (test_progressive_passes_add_up_to_the_single_render); the knobs apply to the second call
+        L = _ffi.lib(); block = np.zeros((gs.height, gs.width, 5), np.float32); st = A.phip_stats()
+        setenv(c.get("env_first", {}))
+        p = integ.params(gs, 3, flags=flags, sample_offset=0, sample_total=8)
+        assert L.phip_render(gs._h, C.byref(p), _ffi.fptr(block), C.byref(st)) == 0
+        first_fused = st.fused
+        setenv(c.get("env", {}))
+        p = integ.params(gs, 5, flags=flags | A.PHIP_FLAG_ACCUMULATE, sample_offset=3, sample_total=8, progress=record)
+        assert L.phip_render(gs._h, C.byref(p), _ffi.fptr(block), C.byref(st)) == 0
+        assert first_fused == 1, name
+        out[name + "_film"] = block
+        stats = st
+    else:
+        setenv(c.get("env", {}))
+        film = HDRFilm(gs.width, gs.height)
+        kw = dict(shard_index=c["shard"][0], shard_count=c["shard"][1]) if "shard" in c else {}
+        if "devices" in c:
+            kw["devices"] = c["devices"]; flags |= A.PHIP_FLAG_ALIAS_DEVICES
+        else:
+            flags |= A.PHIP_FLAG_SAMPLE_BUFFER; kw["progress"] = record
+        assert integ.render(gs, film, spp, flags=flags, **kw)
+        if flags & A.PHIP_FLAG_SAMPLE_BUFFER:
+            out[name + "_samples"] = integ.samples(gs, spp).copy()
+        out[name + "_film"] = film.storage.copy()
+        stats = integ.stats
+    out[name + "_stats"] = np.array([stats.fused, stats.samples], np.int64)
+    out[name + "_progress"] = np.array(prog, np.int64).reshape(-1, 2)
+    setenv({})
+    gs.close()
+np.savez(sys.argv[1], **out)
+"""
+
+
+def _give_up_runs(tmp_path, runs):
+    """runs: {tag: (library path or None for the product, [case, ...])} -> {tag: (arrays, {case name: that case's stderr})}"""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = {}
+    for tag, (lib, cases) in runs.items():
+        f = str(tmp_path / (tag + ".npz"))
+        env = dict(os.environ)
+        for k in ("PHIP_LIB", "PHIP_TEST_FAULT_WAVES", "PHIP_TEST_FAULT_PASS", "PHIP_TEST_FAULT_SHORT", "PHIP_MAX_PASS_SAMPLES"):
+            env.pop(k, None)
+        if lib:
+            env["PHIP_LIB"] = lib
+        r = subprocess.run([sys.executable, "-c", _GIVE_UP_CHILD % root, f, json.dumps(cases)], env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, (tag, r.stdout[-2000:] + r.stderr[-3000:])
+        logs = {}
+        for part in r.stderr.split("@@case ")[1:]:
+            head, _, body = part.partition("\n")
+            logs[head.strip()] = body
+        assert sorted(logs) == sorted(c["name"] for c in cases), (tag, r.stderr[-2000:])
+        res[tag] = (np.load(f), logs)
+    return res
+
+
+def _assert_progress(prog, what):
+    """the progress values of one call: never decreasing, against one total, the last one the total"""
+    assert len(prog) >= 1, what
+    done, total = prog[:, 0], prog[:, 1]
+    assert (np.diff(done) >= 0).all(), (what, prog.tolist())
+    assert (total == total[0]).all(), (what, prog.tolist())
+    assert done[-1] == total[0], (what, prog.tolist())
+
+
+def _assert_same_job(prod, other, name, ref=None, samples=True):
+    """`name` of the other build rendered the product's frame of case `ref`: film, sample buffer and sample count bit for bit"""
+    ref = ref or name
+    assert (prod[ref + "_film"].view(np.uint32) == other[name + "_film"].view(np.uint32)).all(), (name, "film")
+    if samples:
+        assert prod[ref + "_samples"].shape == other[name + "_samples"].shape, name
+        assert (prod[ref + "_samples"].view(np.uint32) == other[name + "_samples"].view(np.uint32)).all(), (name, "sample buffer")
+    assert prod[ref + "_stats"][1] == other[name + "_stats"][1], (name, "stats.samples", prod[ref + "_stats"][1], other[name + "_stats"][1])
+
+
+def _need_hipcc():
+    if not os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")):
+        pytest.skip("hipcc not available: the test libraries cannot be built")
+
+
+GAVE_UP = "warning: the fused kernel gave up"
+_GIVE_UP_SCENES = (("mixed", 8), ("box", 8), ("spheres", 4))        # the mailbox build, the build of the metric, the tree in memory
+
+
+def test_fused_pass_that_gives_up_is_rendered_again_however_many_waves_gave_up(gpu, gauss, tmp_path):
+    """A wave of k_mega that gave up used to add 2^62 to its ST_SAMPLES entry, and the host compared the pass's sum with rc.totalIds: four poisoned waves (one block)
+    sum to 2^64 = 0 and the pass was accepted, with its dropped tasks or missing samples.  Now a wave that gave up sets its entry of a row of its own (ST_GAVE_UP), and
+    a pass must also count exactly one sample per crop pixel and sample of the pass.  Under the fault-injection build, wave 0, the four waves of block 0 and every wave
+    give up -- with all their samples counted, one short (a stuck mailbox) or only one short (no flag: the exact count must catch it) -- and every frame must be the
+    product's, bit for bit: film, sample buffer, stats.samples, with fused == 0, the warning, and progress that ends at its total."""
+    _need_hipcc()
+    from mitsuba_amd import _ffi
+    lib = _ffi.build_test_variant("fault")
+    prod_cases = [dict(name=n, scene=n, spp=spp) for n, spp in _GIVE_UP_SCENES] + \
+                 [dict(name=n, scene=n, spp=4) for n in ("direct", "volpath")]
+    cases = []
+    for n, spp in _GIVE_UP_SCENES:
+        for waves in ("wave0", "block", "all"):
+            cases.append(dict(name="%s_%s" % (n, waves), scene=n, spp=spp, ref=n, env=dict(PHIP_TEST_FAULT_WAVES=waves)))
+        for waves in ("block", "all"):
+            cases.append(dict(name="%s_%s_short" % (n, waves), scene=n, spp=spp, ref=n, env=dict(PHIP_TEST_FAULT_WAVES=waves, PHIP_TEST_FAULT_SHORT="1")))
+        cases.append(dict(name="%s_block_count_only" % n, scene=n, spp=spp, ref=n, env=dict(PHIP_TEST_FAULT_WAVES="block", PHIP_TEST_FAULT_SHORT="2")))
+    for n in ("direct", "volpath"):
+        cases.append(dict(name=n + "_all", scene=n, spp=4, ref=n, env=dict(PHIP_TEST_FAULT_WAVES="all")))
+    res = _give_up_runs(tmp_path, {"product": (None, prod_cases), "fault": (lib, cases)})
+    prod, plog = res["product"]
+    fault, flog = res["fault"]
+    for c in prod_cases:
+        assert "warning" not in plog[c["name"]], (c["name"], plog[c["name"]][-800:])
+        assert prod[c["name"] + "_stats"][0] == 1, c["name"]                          # the product ran k_mega
+        _assert_progress(prod[c["name"] + "_progress"], c["name"])
+    for c in cases:
+        name = c["name"]
+        assert GAVE_UP in flog[name], (name, flog[name][-800:])
+        assert fault[name + "_stats"][0] == 0, name                                   # the frame came from the wavefront kernels
+        _assert_same_job(prod, fault, name, c["ref"])
+        _assert_progress(fault[name + "_progress"], name)
+        assert fault[name + "_progress"][-1, 1] == prod[c["ref"] + "_progress"][-1, 1], name
+
+
+def test_late_fused_pass_that_gives_up_continues_the_job(gpu, gauss, tmp_path):
+    """A job of several passes (PHIP_MAX_PASS_SAMPLES) whose pass 1 or 2 gives up: the host renders the rest of the job on the wavefront kernels as a continuation --
+    the same passes, the caller's sample buffer at the caller's spp (it used to be reallocated for the remaining samples and cleared, and phip_get_samples refused the
+    caller's size), stats.samples and progress over the whole job.  Also the second call of a progressive 3 + 5 render (PHIP_FLAG_ACCUMULATE: the film holds the
+    caller's samples) whose second pass gives up.  Every frame must be the product's multi-pass frame, bit for bit."""
+    _need_hipcc()
+    from mitsuba_amd import _ffi
+    lib = _ffi.build_test_variant("fault")
+    ids = {"mixed": 96 * 96, "box": 64 * 64, "spheres": 96 * 96}            # sample ids per sample of the whole film (block size 32: the films are whole blocks)
+    prod_cases, cases = [], []
+    for n, spp in _GIVE_UP_SCENES:
+        multi = dict(PHIP_MAX_PASS_SAMPLES=str(ids[n] * (spp // 4)))         # four passes
+        prod_cases.append(dict(name=n, scene=n, spp=spp, env=multi))
+        for k in ("1", "2"):
+            for waves in ("wave0", "all"):
+                cases.append(dict(name="%s_pass%s_%s" % (n, k, waves), scene=n, spp=spp, ref=n, env=dict(multi, PHIP_TEST_FAULT_WAVES=waves, PHIP_TEST_FAULT_PASS=k)))
+    multi = dict(PHIP_MAX_PASS_SAMPLES=str(ids["box"] * 2))                 # 3 = 2 + 1 and 5 = 2 + 2 + 1 samples
+    prod_cases.append(dict(name="progressive", scene="box", spp=5, progressive=True, env_first=multi, env=multi))
+    cases.append(dict(name="progressive", scene="box", spp=5, ref="progressive", progressive=True, env_first=dict(multi, PHIP_TEST_FAULT_WAVES="none"),
+                      env=dict(multi, PHIP_TEST_FAULT_WAVES="all", PHIP_TEST_FAULT_PASS="1")))
+    res = _give_up_runs(tmp_path, {"product": (None, prod_cases), "fault": (lib, cases)})
+    prod, plog = res["product"]
+    fault, flog = res["fault"]
+    for c in prod_cases:
+        assert "warning" not in plog[c["name"]], (c["name"], plog[c["name"]][-800:])
+        assert prod[c["name"] + "_stats"][0] == 1, c["name"]
+        _assert_progress(prod[c["name"] + "_progress"], c["name"])
+    for c in cases:
+        name = c["name"]
+        log = flog[name]
+        assert log.count(GAVE_UP) == 1, (name, log[-800:])                     # one pass gave up; the continuation does not run k_mega again
+        first = 3 + int(c["env"]["PHIP_TEST_FAULT_PASS"]) * 2 if c.get("progressive") else int(c["env"]["PHIP_TEST_FAULT_PASS"]) * (c["spp"] // 4)
+        assert "samples %d.. of the job" % first in log, (name, log[-800:])       # ... and it was the pass asked for, not the first
+        assert fault[name + "_stats"][0] == 0, name
+        _assert_same_job(prod, fault, name, c["ref"], samples=not c.get("progressive"))
+        prog = fault[name + "_progress"]
+        _assert_progress(prog, name)
+        assert prog[-1, 1] == prod[c["ref"] + "_progress"][-1, 1], name
+        assert len(prog) >= 2 and prog[0, 0] > 0, (name, prog.tolist())            # the passes before the one that gave up were reported, and kept
+
+
+def test_task_stack_overflow_stops_the_wave_and_the_pass_is_rendered_again(gpu, gauss, tmp_path):
+    """traceWidePool (k_wide_wave.h) with task stacks of 64 entries in LDS and 64 in the spill buffer (the `overflow` library): the tree-in-memory scenes outgrow them.
+    A push past the stack used to be dropped while the stack's count still grew, and the pops went on to read past the wave's slice of the spill buffer -- words that
+    became node indices.  Now the wave stops at the overflow, reports that it gave up, and the host renders the pass again: each scene prints the task-stack warning,
+    reports fused == 0 and delivers the product's frame bit for bit; no other warning appears."""
+    _need_hipcc()
+    from mitsuba_amd import _ffi
+    lib = _ffi.build_test_variant("overflow")
+    names = ("atrium", "spheres", "direct", "volpath")
+    cases = [dict(name=n, scene=n, spp=4) for n in names]
+    res = _give_up_runs(tmp_path, {"product": (None, cases), "overflow": (lib, cases)})
+    prod, plog = res["product"]
+    small, slog = res["overflow"]
+    for n in names:
+        assert "warning" not in plog[n] and prod[n + "_stats"][0] == 1, (n, plog[n][-800:])
+        warnings = [l for l in slog[n].splitlines() if "warning" in l]
+        assert warnings and all(GAVE_UP in l and "a task stack outgrew LDS + spill buffer" in l for l in warnings), (n, slog[n][-800:])
+        assert small[n + "_stats"][0] == 0, n
+        _assert_same_job(prod, small, n)
+        _assert_progress(small[n + "_progress"], n)
+
+
+def test_ragged_film_and_a_shard_keep_the_fused_pass(gpu, gauss, tmp_path):
+    """The exact sample count a fused pass must reach is the crop pixels of the device's blocks times the pass's samples -- not rc.totalIds, which counts the ids of
+    edge blocks outside the film (drawn and skipped).  A 100 x 70 film and one shard of three must stay on k_mega: fused == 1, no warning, every sample counted."""
+    cases = [dict(name="ragged", scene="ragged", spp=4), dict(name="shard", scene="ragged", spp=4, shard=[1, 3]),
+             dict(name="ragged_multi", scene="ragged", spp=4, env=dict(PHIP_MAX_PASS_SAMPLES=str(4 * 3 * 1024)))]
+    res = _give_up_runs(tmp_path, {"product": (None, cases)})
+    prod, plog = res["product"]
+    for c in cases:
+        n = c["name"]
+        assert "warning" not in plog[n], (n, plog[n][-800:])
+        assert prod[n + "_stats"][0] == 1, n
+        _assert_progress(prod[n + "_progress"], n)
+    assert prod["ragged_stats"][1] == prod["ragged_multi_stats"][1] == 100 * 70 * 4
+    assert 0 < prod["shard_stats"][1] < 100 * 70 * 4
+    assert prod["shard_progress"][-1, 1] == prod["shard_stats"][1]
+    assert (prod["ragged_samples"].view(np.uint32) == prod["ragged_multi_samples"].view(np.uint32)).all()
+
+
+def test_device_aliases_that_give_up_deliver_the_product_frame(gpu, gauss, tmp_path):
+    """Two aliases of one device (devices=[0, 0], as test_multi_device_render_equals_the_single_device_frame): under the fault build with every wave giving up, each
+    device's share is rendered again on the wavefront kernels, and the merged frame is the product's merged frame, bit for bit; stats.fused is 0 (the merge used to
+    OR the devices' flags)."""
+    _need_hipcc()
+    from mitsuba_amd import _ffi
+    lib = _ffi.build_test_variant("fault")
+    cases = [dict(name=n, scene=n, spp=spp, devices=[0, 0]) for n, spp in _GIVE_UP_SCENES]
+    fcases = [dict(c, env=dict(PHIP_TEST_FAULT_WAVES="all")) for c in cases]
+    res = _give_up_runs(tmp_path, {"product": (None, cases), "fault": (lib, fcases)})
+    prod, plog = res["product"]
+    fault, flog = res["fault"]
+    for c in cases:
+        n = c["name"]
+        assert "warning" not in plog[n] and prod[n + "_stats"][0] == 1, (n, plog[n][-800:])
+        assert flog[n].count(GAVE_UP) == 2, (n, flog[n][-800:])                 # once per device
+        assert fault[n + "_stats"][0] == 0, n
+        _assert_same_job(prod, fault, n, samples=False)
