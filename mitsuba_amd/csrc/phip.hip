@@ -1025,7 +1025,6 @@ static void validateParams(const phip_scene *sc, const phip_render_params *p) {
         if (n >= (1ull << 17)) throw std::invalid_argument(std::string(name) + ": at most 131071 samples per pixel (32-bit pixel offsets)");
     }
     if (p->sampler == PHIP_SAMPLER_SOBOL || p->sampler == PHIP_SAMPLER_STRATIFIED) {
-        const char *name = p->sampler == PHIP_SAMPLER_SOBOL ? "PHIP_SAMPLER_SOBOL" : "PHIP_SAMPLER_STRATIFIED";
         const DevScene &D0 = sc->devs[0]->dev;
         if (p->sampler == PHIP_SAMPLER_SOBOL) {
             if (!p->sobol_matrices || p->sobol_dimensions < 8) throw std::invalid_argument("PHIP_SAMPLER_SOBOL: sobol_matrices / sobol_dimensions (the reference plugin's direction numbers) are required");
@@ -1064,241 +1063,242 @@ static void validateParams(const phip_scene *sc, const phip_render_params *p) {
     if (p->n_devices > 1 && p->stream) throw std::invalid_argument("a caller's stream belongs to one device: leave `stream` NULL when n_devices > 1 (every device renders on a stream of the library)");
 }
 
-/* The rest of a job whose fused pass gave up (renderOnDevice calls itself with p = the remaining samples, on the wavefront kernels): what the job had before it.  The
-   continuation writes the caller's sample buffer at the caller's stride, reports progress against the caller's total and keeps what the job's earlier passes left. */
-struct JobSoFar {
-    uint32_t spp;                     /* the caller's spp: the sample buffer's stride, the progress callback's total */
-    int sampleOffset;                 /* the caller's sample_offset: sample k of the job is at k - sampleOffset in a pixel's row of the sample buffer */
-    unsigned long long samplesDone;   /* samples of the passes that are in the film already */
-    bool accumulate;                  /* the caller's PHIP_FLAG_ACCUMULATE: a cancelled job leaves dOut as it is, instead of clearing it */
+/* The work counters of `a` added to `t`: samples, rays, vertices, node visits and triangle tests (a pass into its job, a device into the call) */
+static void addWork(phip_stats &t, const phip_stats &a) {
+    t.samples += a.samples; t.closest_rays += a.closest_rays; t.shadow_rays += a.shadow_rays; t.path_vertices += a.path_vertices;
+    t.closest_node_visits += a.closest_node_visits; t.closest_triangle_tests += a.closest_triangle_tests;
+    t.shadow_node_visits += a.shadow_node_visits; t.shadow_triangle_tests += a.shadow_triangle_tests;
+}
+
+/* k_mega's entry points for one traversal form (phip_common.h) */
+using MegaBlocksPerCU = int (*)(int, bool, int, bool, size_t);
+using MegaLaunch = void (*)(int, bool, int, bool, dim3, size_t, hipStream_t, const DevScene &, const MegaParams &, const RenderConst &, float4 *);
+
+/* The fused kernel for one render call: whether it runs, in which traversal form, and its resident grid */
+struct FusedPlan {
+    bool on = false;                        /* the passes run on k_mega -- until one of them gives up */
+    int flat = 0; bool wide = false;        /* k_mega's traversal form (k_mega.h); >= 4: the 8-wide tree in memory */
+    bool strictNormals = false;
+    MegaBlocksPerCU blocksPerCU = nullptr; MegaLaunch launch = nullptr;
+    int perCU = 0; uint32_t nodeCache = 0; size_t lds = 0;
+    dim3 grid = dim3(1); MegaParams M;
+#if MEGA_MB_FAULT
+    uint32_t faultWaves = 0; int faultPass = -1;
+#endif
 };
 
-/* One device's share of a render call: the blocks whose index in the reference's spiral order is congruent to shardIndex
-   modulo shardCount, into dOut (device memory of sd.device).  The caller holds the scene's render lock and has validated p. */
-static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params *p, int shardIndex, int shardCount, float *dOut, phip_stats *stats,
-                          const JobSoFar *job = nullptr) {
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    const bool direct = p->integrator == PHIP_INTEGRATOR_DIRECT;
-    const int bs = p->block_size > 0 ? p->block_size : 32;
-    HIP_TRY(hipSetDevice(sd.device));
+/* The wavefront kernels for one render call (set up only when that path runs): pool, kernel choice, grids */
+struct WavefrontPlan {
+    bool shadeTrace = false;                /* k_shade_trace: the vertex kernel traces both rays of the iteration itself */
+    bool merged = false;                    /* closest-hit and any-hit rays share one persistent launch */
+    uint32_t capacity = 0, nWaves = 0, nBlocks = 0;
+    int feat = 0;                           /* FEAT of the shading kernels: 1 environment emitter, 2 bitmap textures, 8 the QMC samplers */
+    size_t ldsBytes = 0, wideLds = 0, shadeTraceLds = 0;
+    dim3 grid = dim3(1), pgridRays = dim3(1);
+#if PHIP_EXPERIMENTS
+    dim3 pgrid = dim3(1), pgridTrace = dim3(1); bool forcePersist = false;
+#endif
+};
 
-    DevScene D = sd.dev;
-    D.film.blockSize = bs;
-    const int W = D.film.width, H = D.film.height;
-    int tileShift = 0; while ((1 << tileShift) < bs) ++tileShift;
+/* One device's share of one render call: what the stages of renderOnDevice hand to each other */
+struct RenderJob {
+    phip_scene *sc; SceneDev &sd; const phip_render_params *p; float *dOut;
+    hipStream_t stream = nullptr;
+    DevScene D;                             /* sd.dev with this call's block size */
+    int bs, W, H, tileShift = 0, tilesX, nCU = 256;
+    bool direct, timing, keepSamples, rinv, qmc, keepJitter = false;
+    uint32_t sppPerPass = 0; unsigned long long idsPerSpp = 0;
+    FusedPlan F; WavefrontPlan wf;
+    PathPool P;                             /* the wavefront pool; a fused pass sets its statistics rows only (k_reduce_stats) */
+    RenderConst rc;                         /* of the call, then of the pass that is running */
+    EventList evTrace, evShadow, evShade, evFilm, evFused;
+    Counters hc; phip_stats st;
+    unsigned long long samplesDone = 0;     /* samples of the passes that are in the film already */
+    bool cancelled = false;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 
-    /* tile -> shard assignment in the reference's spiral order (cached between calls with the same layout) */
-    const int tilesX = (W + bs - 1) / bs, tilesY = (H + bs - 1) / bs;
-    if (sd.tileKey[0] != bs || sd.tileKey[1] != shardIndex || sd.tileKey[2] != shardCount) {
-        std::vector<std::pair<int, int>> spiral;
-        spiralBlocks(W, H, bs, spiral);
-        std::vector<int32_t> tileSlot((size_t) tilesX * tilesY, -1);
-        std::vector<uint32_t> tileOrigin;
-        for (size_t i = 0; i < spiral.size(); ++i) {
-            if ((int) (i % (size_t) shardCount) != shardIndex) continue;
-            tileSlot[(size_t) spiral[i].second * tilesX + spiral[i].first] = (int32_t) tileOrigin.size();
-            tileOrigin.push_back((uint32_t) (spiral[i].first * bs) | ((uint32_t) (spiral[i].second * bs) << 16));
-        }
-        sd.nLocalTiles = (uint32_t) tileOrigin.size();
-        sd.localPixels = 0;
-        for (uint32_t o : tileOrigin) sd.localPixels += (unsigned long long) std::min(bs, W - (int) (o & 0xFFFFu)) * std::min(bs, H - (int) (o >> 16));
-        if (tileOrigin.empty()) sd.tileOrigin.alloc(1);
-        else sd.tileOrigin.upload(tileOrigin.data(), tileOrigin.size());
-        sd.tileSlot.upload(tileSlot.data(), tileSlot.size());
-        sd.tileKey[0] = bs; sd.tileKey[1] = shardIndex; sd.tileKey[2] = shardCount;
+    RenderJob(phip_scene *sc, SceneDev &sd, const phip_render_params *p, float *dOut) : sc(sc), sd(sd), p(p), dOut(dOut), D(sd.dev) {
+        bs = p->block_size > 0 ? p->block_size : 32;
+        D.film.blockSize = bs;
+        W = D.film.width; H = D.film.height; tilesX = (W + bs - 1) / bs;
+        while ((1 << tileShift) < bs) ++tileShift;
+        direct = p->integrator == PHIP_INTEGRATOR_DIRECT;
+        timing = (p->flags & PHIP_FLAG_KERNEL_TIMING) != 0;
+        keepSamples = (p->flags & PHIP_FLAG_SAMPLE_BUFFER) != 0;
+        rinv = p->sampler == PHIP_SAMPLER_HALTON || p->sampler == PHIP_SAMPLER_HAMMERSLEY;
+        qmc = p->sampler == PHIP_SAMPLER_SOBOL || p->sampler == PHIP_SAMPLER_STRATIFIED || rinv;     /* served by the wavefront kernels compiled with FEAT bit 3 */
+        memset(&F.M, 0, sizeof(F.M)); memset(&P, 0, sizeof(P)); memset(&rc, 0, sizeof(rc)); memset(&hc, 0, sizeof(hc)); memset(&st, 0, sizeof(st));
     }
-    const uint32_t nLocalTiles = sd.nLocalTiles;
+    uint32_t sampleTotal() const { return (uint32_t) (p->sample_total > 0 ? p->sample_total : p->spp); }     /* samples per pixel of the whole render, of which this call may be a part */
+    void progress(unsigned long long done) {
+        if (!p->progress) return;
+        std::lock_guard<std::mutex> g(sc->progressLock);
+        p->progress(p->progress_user, sd.device, done, sd.localPixels * (unsigned long long) p->spp);
+    }
+};
 
-    hipStream_t stream = (p->n_devices <= 1) ? (hipStream_t) p->stream : nullptr;    /* a caller's stream belongs to one device */
-    if (!stream) { if (!sd.stream) HIP_TRY(hipStreamCreate(&sd.stream)); stream = sd.stream; }
+/* tile -> shard assignment in the reference's spiral order (cached between calls with the same layout) */
+static void shardTiles(RenderJob &J, int shardIndex, int shardCount) {
+    SceneDev &sd = J.sd;
+    const int bs = J.bs, W = J.W, H = J.H, tilesX = J.tilesX, tilesY = (H + bs - 1) / bs;
+    if (sd.tileKey[0] == bs && sd.tileKey[1] == shardIndex && sd.tileKey[2] == shardCount) return;
+    std::vector<std::pair<int, int>> spiral;
+    spiralBlocks(W, H, bs, spiral);
+    std::vector<int32_t> tileSlot((size_t) tilesX * tilesY, -1);
+    std::vector<uint32_t> tileOrigin;
+    for (size_t i = 0; i < spiral.size(); ++i) {
+        if ((int) (i % (size_t) shardCount) != shardIndex) continue;
+        tileSlot[(size_t) spiral[i].second * tilesX + spiral[i].first] = (int32_t) tileOrigin.size();
+        tileOrigin.push_back((uint32_t) (spiral[i].first * bs) | ((uint32_t) (spiral[i].second * bs) << 16));
+    }
+    sd.nLocalTiles = (uint32_t) tileOrigin.size();
+    sd.localPixels = 0;
+    for (uint32_t o : tileOrigin) sd.localPixels += (unsigned long long) std::min(bs, W - (int) (o & 0xFFFFu)) * std::min(bs, H - (int) (o >> 16));
+    if (tileOrigin.empty()) sd.tileOrigin.alloc(1);
+    else sd.tileOrigin.upload(tileOrigin.data(), tileOrigin.size());
+    sd.tileSlot.upload(tileSlot.data(), tileSlot.size());
+    sd.tileKey[0] = bs; sd.tileKey[1] = shardIndex; sd.tileKey[2] = shardCount;
+}
 
-    /* passes: bound the per-sample buffer (16 B per sample id; 24 B with the jitter the sequence samplers keep for the film pass) */
-    const bool keepJitter = (p->sampler == PHIP_SAMPLER_SOBOL || p->sampler == PHIP_SAMPLER_HALTON || p->sampler == PHIP_SAMPLER_HAMMERSLEY) && !expEnv("PHIP_NO_JITTER_BUFFER");
-    const unsigned long long tilePixels = (unsigned long long) bs * bs;
+/* passes: bound the per-sample buffer (16 B per sample id; 24 B with the jitter the sequence samplers keep for the film pass) */
+static void planPasses(RenderJob &J) {
+    SceneDev &sd = J.sd; const phip_render_params *p = J.p;
+    J.keepJitter = (p->sampler == PHIP_SAMPLER_SOBOL || p->sampler == PHIP_SAMPLER_HALTON || p->sampler == PHIP_SAMPLER_HAMMERSLEY) && !expEnv("PHIP_NO_JITTER_BUFFER");
     const unsigned long long maxIdsPerPass = (1ull << 32) - 1;                 /* sample ids are 32-bit in the slot state */
-    unsigned long long budgetIds = (24ull << 30) / (keepJitter ? 24 : 16);    /* 24 GiB of sample buffer */
+    unsigned long long budgetIds = (24ull << 30) / (J.keepJitter ? 24 : 16);  /* 24 GiB of sample buffer */
     if (const char *e = getenv("PHIP_MAX_PASS_SAMPLES")) budgetIds = std::max(1ull, strtoull(e, nullptr, 10));   /* test hook: force several passes */
-    unsigned long long idsPerSpp = (unsigned long long) nLocalTiles * tilePixels;
-    uint32_t sppPerPass = (uint32_t) p->spp;
-    if (idsPerSpp > 0) {
-        unsigned long long cap = std::min(maxIdsPerPass, budgetIds) / idsPerSpp;
+    J.idsPerSpp = (unsigned long long) sd.nLocalTiles * ((unsigned long long) J.bs * J.bs);
+    J.sppPerPass = (uint32_t) p->spp;
+    if (J.idsPerSpp > 0) {
+        unsigned long long cap = std::min(maxIdsPerPass, budgetIds) / J.idsPerSpp;
         if (cap < 1) cap = 1;
-        sppPerPass = (uint32_t) std::min<unsigned long long>(cap, (unsigned long long) p->spp);
+        J.sppPerPass = (uint32_t) std::min<unsigned long long>(cap, (unsigned long long) p->spp);
     }
-    const bool keepSamples = (p->flags & PHIP_FLAG_SAMPLE_BUFFER) != 0;
-    const uint32_t jobSpp = job ? job->spp : (uint32_t) p->spp;                 /* (a continuation: the caller's job, of which p is the rest) */
-    const int jobOffset = job ? job->sampleOffset : p->sample_offset;
-    if (keepSamples && !job) { sd.sampleOut.alloc((size_t) W * H * (size_t) p->spp); HIP_TRY(hipMemsetAsync(sd.sampleOut.p, 0, sd.sampleOut.n * sizeof(float4), stream)); }
-    sd.haveSamples = keepSamples; sd.lastSpp = jobSpp;
-
-    const unsigned long long idsFirstPass = idsPerSpp * sppPerPass;
+    if (J.keepSamples) { sd.sampleOut.alloc((size_t) J.W * J.H * (size_t) p->spp); HIP_TRY(hipMemsetAsync(sd.sampleOut.p, 0, sd.sampleOut.n * sizeof(float4), J.stream)); }
+    sd.haveSamples = J.keepSamples; sd.lastSpp = (uint32_t) p->spp;
+    const unsigned long long idsFirstPass = J.idsPerSpp * J.sppPerPass;
     if (sd.L.n < idsFirstPass) sd.L.alloc((size_t) idsFirstPass);
-    if (keepJitter && sd.jitter.n < idsFirstPass) sd.jitter.alloc((size_t) idsFirstPass);
+    if (J.keepJitter && sd.jitter.n < idsFirstPass) sd.jitter.alloc((size_t) idsFirstPass);
+}
 
-    /* which device path: the fused kernel when the scene fits its LDS plan (decided at scene creation) */
-    const bool rinv = p->sampler == PHIP_SAMPLER_HALTON || p->sampler == PHIP_SAMPLER_HAMMERSLEY;
-    const bool qmc = p->sampler == PHIP_SAMPLER_SOBOL || p->sampler == PHIP_SAMPLER_STRATIFIED || rinv;     /* served by the wavefront kernels compiled with FEAT bit 3 */
+/* PHIP_SAMPLER_SOBOL: the plugin's tables, uploaded once per content: ~210 KB of direction numbers + the two 52-word enumeration rows */
+static void uploadSobolTables(RenderJob &J) {
+    SceneDev &sd = J.sd; const phip_render_params *p = J.p;
+    const size_t nm = (size_t) p->sobol_dimensions * PHIP_SOBOL_MATRIX_SIZE;
+    /* (keyed by CONTENT: the tables are host pointers "read during the call" -- a caller may refill or reallocate them at the same address) */
+    uint64_t key = contentHash(p->sobol_matrices, nm * sizeof(uint32_t), 0x9E3779B97F4A7C15ull);
+    if (p->sobol_log_resolution > 1) { key = contentHash(p->sobol_vdc, PHIP_SOBOL_MATRIX_SIZE * sizeof(uint64_t), key); key = contentHash(p->sobol_vdc_inv, PHIP_SOBOL_MATRIX_SIZE * sizeof(uint64_t), key); }
+    if (sd.sobolKey == key && sd.sobolMat.n == nm && sd.sobolLogRes == p->sobol_log_resolution) return;
+    sd.sobolMat.upload(p->sobol_matrices, nm);
+    std::vector<unsigned long long> v(2 * PHIP_SOBOL_MATRIX_SIZE, 0ull);
+    if (p->sobol_log_resolution > 1)
+        for (int i = 0; i < PHIP_SOBOL_MATRIX_SIZE; ++i) { v[i] = p->sobol_vdc[i]; v[PHIP_SOBOL_MATRIX_SIZE + i] = p->sobol_vdc_inv[i]; }
+    sd.sobolVdc.upload(v.data(), v.size());
+    std::vector<uint32_t> bt; std::vector<unsigned long long> vb;
+    buildSobolByteTables(p->sobol_matrices, (size_t) p->sobol_dimensions, v.data(), bt, vb);
+    sd.sobolBt.upload(bt.data(), bt.size()); sd.sobolVdcBt.upload(vb.data(), vb.size());
+    sd.sobolKey = key; sd.sobolLogRes = p->sobol_log_resolution;
+}
+
+/* PHIP_SAMPLER_HALTON / _HAMMERSLEY: primes + permutations, keyed by content (at most ~200 KB; see the Sobol tables above) */
+static void uploadRinvTables(RenderJob &J) {
+    SceneDev &sd = J.sd; const phip_render_params *p = J.p;
+    std::vector<uint32_t> off(p->qmc_dimensions);
+    size_t total = 0;
+    for (uint32_t d = 0; d < p->qmc_dimensions; ++d) { off[d] = (uint32_t) total; total += p->qmc_primes[d]; }
+    uint64_t rinvKey = contentHash(p->qmc_primes, p->qmc_dimensions * sizeof(uint32_t), p->qmc_permutations ? 0x51ED270B7A5F1D3Bull : 0x2545F4914F6CDD1Dull);
+    if (p->qmc_permutations) rinvKey = contentHash(p->qmc_permutations, total * sizeof(uint16_t), rinvKey);
+    if (sd.rinvKey == rinvKey && sd.rinvPrimes.n == p->qmc_dimensions) return;
+    /* primes, the start of every base's permutation, the permutations themselves; the inverse permutations of bases 2 and 3 (the pixel enumeration) */
+    sd.rinvPrimes.upload(p->qmc_primes, p->qmc_dimensions); sd.rinvOffsets.upload(off.data(), off.size());
+    sd.rinvInvPerm2 = 0x4u; sd.rinvInvPerm3 = 0x24u;
+    if (p->qmc_permutations) {
+        sd.rinvPerm.upload(p->qmc_permutations, total);
+        const uint16_t *p2 = p->qmc_permutations, *p3 = p->qmc_permutations + 2;
+        sd.rinvInvPerm2 = sd.rinvInvPerm3 = 0;
+        for (uint32_t i = 0; i < 2; ++i) sd.rinvInvPerm2 |= i << (2u * p2[i]);          /* invPerm[perm[i]] = i (faure.cpp: invertPermutation) */
+        for (uint32_t i = 0; i < 3; ++i) sd.rinvInvPerm3 |= i << (2u * p3[i]);
+    }
+    std::vector<uint32_t> di, ch, pw; std::vector<float> fc;
+    sd.rinvTabDims = buildRinvTables(p->qmc_primes, p->qmc_permutations, off.data(), p->qmc_dimensions, di, ch, fc, pw);
+    if (sd.rinvTabDims) { sd.rinvDimInfo.upload(di.data(), di.size()); sd.rinvChunk.upload(ch.data(), ch.size()); sd.rinvFac.upload(fc.data(), fc.size()); sd.rinvPw.upload(pw.data(), pw.size()); }
+    sd.rinvKey = rinvKey;
+}
+
+/* which device path: the fused kernel when the scene fits its LDS plan (decided at scene creation) and a block of it fits a compute unit for THIS render */
+static void planFused(RenderJob &J) {
+    phip_scene *sc = J.sc; SceneDev &sd = J.sd; const phip_render_params *p = J.p; FusedPlan &F = J.F;
     /* (the fused kernel on the 8-wide tree: by default where it is faster than the wavefront kernels -- trees that live in L2, DESIGN.md 3.9 -- with PHIP_FLAG_FUSED_ANY wherever it can run) */
     const bool wideFused = sc->fusedWide && (sc->bvh.nWNodes <= PHIP_FUSED_WIDE_MAX_NODES || (p->flags & PHIP_FLAG_FUSED_ANY));
-    bool fused = (sc->fitsLds || wideFused) && sc->traversal == 2 && !(p->flags & (PHIP_FLAG_NO_FUSED | PHIP_FLAG_NO_MEGA));
-    const int megaFlat = sc->fitsLds ? (D.nFlatLeaves ? (int) D.flatMode : 0) : sc->fusedWide;      /* k_mega's traversal form (k_mega.h) */
-    if (direct && megaFlat < 2) fused = false;      /* (round 6: `direct` rides the fused kernel too -- k_mega<.., DIRECT>, on the packed leaf tables and on the tree in memory) */
-    const bool megaWide = megaFlat >= 4;
-    if (qmc && p->sampler == PHIP_SAMPLER_SOBOL) {
-        /* the plugin's tables, uploaded once per (pointer, size): ~210 KB of direction numbers + the two 52-word enumeration rows */
-        const size_t nm = (size_t) p->sobol_dimensions * PHIP_SOBOL_MATRIX_SIZE;
-        /* (keyed by CONTENT: the tables are host pointers "read during the call" -- a caller may refill or reallocate them at the same address) */
-        uint64_t key = contentHash(p->sobol_matrices, nm * sizeof(uint32_t), 0x9E3779B97F4A7C15ull);
-        if (p->sobol_log_resolution > 1) { key = contentHash(p->sobol_vdc, PHIP_SOBOL_MATRIX_SIZE * sizeof(uint64_t), key); key = contentHash(p->sobol_vdc_inv, PHIP_SOBOL_MATRIX_SIZE * sizeof(uint64_t), key); }
-        if (sd.sobolKey != key || sd.sobolMat.n != nm || sd.sobolLogRes != p->sobol_log_resolution) {
-            sd.sobolMat.upload(p->sobol_matrices, nm);
-            std::vector<unsigned long long> v(2 * PHIP_SOBOL_MATRIX_SIZE, 0ull);
-            if (p->sobol_log_resolution > 1)
-                for (int i = 0; i < PHIP_SOBOL_MATRIX_SIZE; ++i) { v[i] = p->sobol_vdc[i]; v[PHIP_SOBOL_MATRIX_SIZE + i] = p->sobol_vdc_inv[i]; }
-            sd.sobolVdc.upload(v.data(), v.size());
-            {
-                std::vector<uint32_t> bt; std::vector<unsigned long long> vb;
-                buildSobolByteTables(p->sobol_matrices, (size_t) p->sobol_dimensions, v.data(), bt, vb);
-                sd.sobolBt.upload(bt.data(), bt.size()); sd.sobolVdcBt.upload(vb.data(), vb.size());
-            }
-            sd.sobolKey = key; sd.sobolLogRes = p->sobol_log_resolution;
-        }
-    }
-    uint64_t rinvKey = 0;
-    if (rinv) {                                        /* content key of primes + permutations (at most ~200 KB; see the Sobol tables above) */
-        size_t total = 0;
-        for (uint32_t d = 0; d < p->qmc_dimensions; ++d) total += p->qmc_primes[d];
-        rinvKey = contentHash(p->qmc_primes, p->qmc_dimensions * sizeof(uint32_t), p->qmc_permutations ? 0x51ED270B7A5F1D3Bull : 0x2545F4914F6CDD1Dull);
-        if (p->qmc_permutations) rinvKey = contentHash(p->qmc_permutations, total * sizeof(uint16_t), rinvKey);
-    }
-    if (rinv && (sd.rinvKey != rinvKey || sd.rinvPrimes.n != p->qmc_dimensions)) {
-        /* primes, the start of every base's permutation, the permutations themselves; the inverse permutations of bases 2 and 3 (the pixel enumeration) */
-        std::vector<uint32_t> off(p->qmc_dimensions);
-        size_t total = 0;
-        for (uint32_t d = 0; d < p->qmc_dimensions; ++d) { off[d] = (uint32_t) total; total += p->qmc_primes[d]; }
-        sd.rinvPrimes.upload(p->qmc_primes, p->qmc_dimensions); sd.rinvOffsets.upload(off.data(), off.size());
-        sd.rinvInvPerm2 = 0x4u; sd.rinvInvPerm3 = 0x24u;
-        if (p->qmc_permutations) {
-            sd.rinvPerm.upload(p->qmc_permutations, total);
-            const uint16_t *p2 = p->qmc_permutations, *p3 = p->qmc_permutations + 2;
-            sd.rinvInvPerm2 = sd.rinvInvPerm3 = 0;
-            for (uint32_t i = 0; i < 2; ++i) sd.rinvInvPerm2 |= i << (2u * p2[i]);          /* invPerm[perm[i]] = i (faure.cpp: invertPermutation) */
-            for (uint32_t i = 0; i < 3; ++i) sd.rinvInvPerm3 |= i << (2u * p3[i]);
-        }
-        {
-            std::vector<uint32_t> di, ch, pw; std::vector<float> fc;
-            sd.rinvTabDims = buildRinvTables(p->qmc_primes, p->qmc_permutations, off.data(), p->qmc_dimensions, di, ch, fc, pw);
-            if (sd.rinvTabDims) { sd.rinvDimInfo.upload(di.data(), di.size()); sd.rinvChunk.upload(ch.data(), ch.size()); sd.rinvFac.upload(fc.data(), fc.size()); sd.rinvPw.upload(pw.data(), pw.size()); }
-        }
-        sd.rinvKey = rinvKey;
-    }
-    if (const char *e = expEnv("PHIP_MEGA")) fused = fused && atoi(e) != 0;            /* experiment hook: PHIP_MEGA=0 forces the wavefront kernels */
+    F.on = (sc->fitsLds || wideFused) && sc->traversal == 2 && !(p->flags & (PHIP_FLAG_NO_FUSED | PHIP_FLAG_NO_MEGA));
+    F.flat = sc->fitsLds ? (J.D.nFlatLeaves ? (int) J.D.flatMode : 0) : sc->fusedWide;
+    if (J.direct && F.flat < 2) F.on = false;      /* (round 6: `direct` rides the fused kernel too -- k_mega<.., DIRECT>, on the packed leaf tables and on the tree in memory) */
+    F.wide = F.flat >= 4;
+    if (const char *e = expEnv("PHIP_MEGA")) F.on = F.on && atoi(e) != 0;            /* experiment hook: PHIP_MEGA=0 forces the wavefront kernels */
+    F.strictNormals = !J.direct && p->strict_normals != 0;
+    F.blocksPerCU = J.direct ? phipMegaBlocksPerCUDirect : F.wide ? phipMegaBlocksPerCUWide : phipMegaBlocksPerCU;
+    F.launch = J.direct ? phipLaunchMegaDirect : F.wide ? phipLaunchMegaWide : phipLaunchMega;
     /* resident blocks of the fused kernel for THIS render (the QMC build has ~15 KB more static LDS than the plan of fitsLds priced at scene
        creation): when none fits a compute unit the render runs on the wavefront kernels, as it did before the samplers moved to k_mega */
-    int megaPerCU = 0;
-    uint32_t megaNodeCache = 0; size_t megaLds = 0;
-    if (fused) {
-        if (megaWide) {
+    if (F.on) {
+        if (F.wide) {
             /* the top of the tree every block stages (BFS order); the mailbox build (all leaf BSDF models, counter stream) has the S-box behind the round buffers */
-            megaNodeCache = std::min<uint32_t>(sc->bvh.nWNodes, MEGA_WIDE_NODE_CACHE);
-            if (const char *e = expEnv("PHIP_MEGA_NODE_CACHE")) megaNodeCache = std::min<uint32_t>(sc->bvh.nWNodes, (uint32_t) atoi(e));
+            F.nodeCache = std::min<uint32_t>(sc->bvh.nWNodes, MEGA_WIDE_NODE_CACHE);
+            if (const char *e = expEnv("PHIP_MEGA_NODE_CACHE")) F.nodeCache = std::min<uint32_t>(sc->bvh.nWNodes, (uint32_t) atoi(e));
             const bool mailbox = false;     /* (the tree-in-memory builds deal their paths by BSDF model; the mailboxes' LDS would cost the fourth block of a CU: k_mega.h) */
-            megaLds = MEGA_POOL ? megaWidePoolLdsBytesOf(D, megaNodeCache, mailbox, megaFlat == 4, MB_DW * MB_NS * sizeof(uint32_t))
-                                : megaWideLdsBytesOf(D, megaNodeCache, mailbox, megaFlat == 4, MB_DW * MB_NS * sizeof(uint32_t));
-            megaPerCU = std::min(MEGA_WAVES, direct ? phipMegaBlocksPerCUDirect(sc->materialMask, false, megaFlat, qmc, megaLds)
-                                                    : phipMegaBlocksPerCUWide(sc->materialMask, p->strict_normals != 0, megaFlat, qmc, megaLds));
+            F.lds = MEGA_POOL ? megaWidePoolLdsBytesOf(J.D, F.nodeCache, mailbox, F.flat == 4, MB_DW * MB_NS * sizeof(uint32_t))
+                              : megaWideLdsBytesOf(J.D, F.nodeCache, mailbox, F.flat == 4, MB_DW * MB_NS * sizeof(uint32_t));
         } else {
-            megaLds = megaLdsBytesOf(D);
-            megaPerCU = std::min(MEGA_WAVES, direct ? phipMegaBlocksPerCUDirect(sc->materialMask, false, megaFlat, qmc, megaLds)
-                                                    : phipMegaBlocksPerCU(sc->materialMask, p->strict_normals != 0, megaFlat, qmc, megaLds));
+            F.lds = megaLdsBytesOf(J.D);
         }
-        if (const char *e = expEnv("PHIP_MEGA_BLOCKS")) megaPerCU = std::max(1, std::min(megaPerCU, atoi(e)));
-        if (megaPerCU <= 0) fused = false;
-        if (getenv("PHIP_DEBUG_TIMING")) fprintf(stderr, "[phip] k_mega (traversal form %d): %d blocks per CU with %zu bytes of dynamic LDS\n", megaFlat, megaPerCU, megaLds);
+        F.perCU = std::min(MEGA_WAVES, F.blocksPerCU(sc->materialMask, F.strictNormals, F.flat, J.qmc, F.lds));
+        if (const char *e = expEnv("PHIP_MEGA_BLOCKS")) F.perCU = std::max(1, std::min(F.perCU, atoi(e)));
+        if (F.perCU <= 0) F.on = false;
+        if (getenv("PHIP_DEBUG_TIMING")) fprintf(stderr, "[phip] k_mega (traversal form %d): %d blocks per CU with %zu bytes of dynamic LDS\n", F.flat, F.perCU, F.lds);
     }
-    sd.fused = fused;
+    sd.fused = F.on;
     /* ... or k_shade_trace: the scene's tree is the packed leaf table, but k_mega does not serve it (glass / copper / textures / environment emitter) */
-    const bool shadeTrace = !fused && (sc->flatTrace || sc->flatTraceToo) && !direct && sc->traversal == 2 && !(p->flags & PHIP_FLAG_NO_FUSED);
+    J.wf.shadeTrace = !F.on && (sc->flatTrace || sc->flatTraceToo) && !J.direct && sc->traversal == 2 && !(p->flags & PHIP_FLAG_NO_FUSED);
+    sd.mergedRays = false;                  /* (until the wavefront setup decides) */
+    if (!F.on) return;
 
-    phip_stats st; memset(&st, 0, sizeof(st));
-    const bool timing = (p->flags & PHIP_FLAG_KERNEL_TIMING) != 0;
-    EventList evTrace, evShadow, evShade, evFilm, evFused;
-    const unsigned long long samplesTotal = sd.localPixels;                  /* crop pixels of this device's blocks */
-
-    if (!job) HIP_TRY(hipMemsetAsync(sd.invalid.p, 0, sizeof(unsigned long long), stream));
-    int nCU = 256; { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, sd.device) == hipSuccess) nCU = prop.multiProcessorCount; }
-    const size_t ldsBytes = traversalLdsBytes(D);
-    const dim3 block(BLOCK);
-    Counters hc;
-    bool cancelled = false;
-    bool accumulate = (p->flags & PHIP_FLAG_ACCUMULATE) != 0;
-    const bool callerAccumulate = job ? job->accumulate : accumulate;
-    unsigned long long samplesDone = job ? job->samplesDone : 0ull;
-
-    /* wavefront state (allocated only when that path runs) */
-    uint32_t capacity = 0, nWaves = 0, nBlocks = 0;
-    PathPool P; memset(&P, 0, sizeof(P));
-    bool merged = false;
-    if (!fused) {
-        /* pool size: large enough that per-launch fixed costs vanish, small enough that the tail (slots
-           running dry at the end of a pass) stays a small fraction of the pass (measured: 4M / 8M slots) */
-        /* (round 3) Every launch of the persistent ray kernel ends with a drain in which each wave waits for its longest ray while the
-           work queue is empty: ~0.15 ms per launch on the 250 k-triangle scenes, 14 % of a launch over 4 M slots, 7 % over 8 M.  A bigger
-           pool means fewer, longer launches: atrium 1920x1080x64 spp 427 / 454 / 470 / 470 Msamples/s with 4 / 8 / 16 / 32 M slots, the
-           glass room at 512 spp 480 / 496 / 505 with 8 / 16 / 32 M -- so the pool grows with the job (about 0.14 KB of HBM per slot). */
-        /* (round 4, after the ray kernel's triangle rounds: 8 / 16 / 32 / 64 M slots on the 4K slice (531 M ids) 610 / 636 / 646 / 657 Msamples/s, C4 at 512 spp (1062 M ids)
-           flat at 64 M and -2 % at 128 M, C3 (133 M ids) flat from 16 M on: jobs of more than 256 M ids get 64 M slots) */
-        /* (round 5: k_shade_trace has no persistent ray kernel whose drain a big pool amortises -- what a big pool costs it is the tail of the pass, the launches
-           in which the long paths of a few slots finish: mixed Cornell box at 256 spp with 1 / 2 / 4 / 8 / 16 M slots 1518 / 1617 / 1643 / 1596 / 1450 Msamples/s,
-           profiles/r05_gpu_call_e_*) */
-        const unsigned long long poolCap = shadeTrace ? (1ull << 22)
-                                         : idsFirstPass > (256ull << 20) ? (1ull << 26) : idsFirstPass >= (64ull << 20) ? (1ull << 24)
-                                         : idsFirstPass >= (16ull << 20) ? (1ull << 23) : (1ull << 22);
-        capacity = (uint32_t) std::min<unsigned long long>(std::max<unsigned long long>(idsFirstPass, BLOCK), poolCap);
-        /* traversal-stack overflow: SPILL_DEPTH words per LANE of a ray kernel -- the wide tree is only walked by persistent grids
-           (at most 8 resident blocks of 256 per CU), the BVH4 also by one-lane-per-slot launches */
-        const bool canSpill = sc->wide ? (int) sc->bvh.wMaxDepth + 2 > WIDE_STACK_LDS : 3 * ((int) sc->bvh.maxDepth - 1) + 1 > (int) D.stackDepth;
-        const bool persistentOnly = sc->wide || (sc->traversal == 2 && sc->bvh.nNodes >= 64 && !expEnv("PHIP_MERGED"));
-        {   /* ... and with the memory that is there: the pool's state is ~144 B per slot (+ 384 B of spill stack where every slot is a lane that can
-               spill); it may take a quarter of what is free now (a shared or partitioned GPU, n_devices replicas), never less than the 4 M slots
-               every job ran with before the pool grew */
-            size_t freeB = 0, totalB = 0;
-            if (sd.rayO.n < capacity && hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-                unsigned long long fit = (unsigned long long) (freeB / 4) / (144ull + ((!persistentOnly && canSpill) ? (unsigned long long) SPILL_DEPTH * 4ull : 0ull));
-                while (capacity > (1u << 22) && capacity > fit) capacity >>= 1;
-            }
-        }
-        capacity = (capacity + BLOCK - 1) / BLOCK * BLOCK;
-        if (const char *e = expEnv("PHIP_POOL")) { capacity = (uint32_t) std::max(BLOCK, atoi(e)) / BLOCK * BLOCK; }
-        const size_t laneCap = ((size_t) capacity + WIDE_BLOCK - 1) / WIDE_BLOCK * WIDE_BLOCK;      /* k_rays_w runs whole blocks of WIDE_BLOCK lanes */
-        nWaves = (uint32_t) (laneCap / 64); nBlocks = capacity / BLOCK;
-        if (sd.rayO.n < capacity) {
-            sd.rayO.alloc(capacity); sd.rayD.alloc(capacity); sd.hit.alloc(capacity); sd.thr.alloc(capacity);
-            sd.mis.alloc(capacity); sd.info.alloc(capacity); sd.state.alloc(capacity); sd.shadow.alloc(3 * (size_t) capacity);
-            sd.shadowCount.alloc(nBlocks); sd.blockDead.alloc(nBlocks); sd.blockShard.alloc(nBlocks);
-        }
-        {   /* persistent grids (at most 8 resident blocks of 256 per CU): the buffer always covers the whole grid, also when the host's depth bound says
-               that no lane can reach it -- 200 MB of 288 GB against a silent out-of-bounds write should that hand-derived bound ever be off.  One lane
-               per slot (BVH4 trees of < 64 nodes: small scenes with non-diffuse materials, every `direct` render of a small scene): 384 B per SLOT of a
-               pool of up to 64 M slots is 3..25 GB for a stack that is at most ~20 entries deep on such a tree -- there the bound decides, as before
-               round 4; when it says "can spill" the full size is allocated AND priced in the free-memory guard above */
-            const size_t spillLanes = persistentOnly ? std::min<size_t>(laneCap, (size_t) nCU * 8 * 256) : (canSpill ? laneCap : (size_t) WIDE_BLOCK);
-            if (sd.spill.n < spillLanes * SPILL_DEPTH) sd.spill.alloc(spillLanes * SPILL_DEPTH);
-            P.spillLanes = (uint32_t) std::min<size_t>(sd.spill.n / SPILL_DEPTH, 0xFFFFFFFFu);
-        }
-        if (sd.stat.n < (size_t) ST_COUNT * nWaves) sd.stat.alloc((size_t) ST_COUNT * nWaves);
-        if (direct && sd.camHit.n < capacity) sd.camHit.alloc(capacity);
-        P.camHit = sd.camHit.p;
-        P.rayO = sd.rayO.p; P.rayD = sd.rayD.p; P.hit = sd.hit.p; P.thr = sd.thr.p; P.mis = sd.mis.p; P.info = sd.info.p; P.state = sd.state.p;
-        P.shadow = sd.shadow.p; P.shadowCount = sd.shadowCount.p; P.blockDead = sd.blockDead.p; P.stat = sd.stat.p; P.spill = sd.spill.p; P.capacity = capacity; P.nWaves = nWaves;
-        /* big trees: closest-hit and any-hit rays share one persistent launch (measured +2..4 % on the 250k-triangle scenes;
-           on small trees the plain per-slot closest-hit launch wins, so the kernels stay separate there) */
-        merged = sc->traversal == 2 && sc->bvh.nNodes >= 64;
-        if (const char *e = expEnv("PHIP_MERGED")) merged = sc->traversal == 2 && atoi(e) != 0;
-        if (sc->wide) merged = true;                             /* the wide tree has the merged kernel only */
+    /* resident grid and per-wave statistics rows */
+    MegaParams &M = F.M;
+    F.grid = dim3((unsigned) (J.nCU * F.perCU));
+    M.nWaves = F.grid.x * (BLOCK / 64);
+    if (sd.stat.n < (size_t) ST_COUNT * M.nWaves) sd.stat.alloc((size_t) ST_COUNT * M.nWaves);
+    M.stat = sd.stat.p; M.nextId = sd.megaNext.p;
+    M.nodeCache = F.nodeCache; M.spill = nullptr;
+    if (F.wide) {     /* the group stacks' overflow behind their six LDS entries: the buffer always covers the grid, as for k_rays_w (a silent out-of-bounds write otherwise) */
+        const size_t spillLanes = (size_t) F.grid.x * BLOCK;
+        if (sd.spill.n < spillLanes * SPILL_DEPTH) sd.spill.alloc(spillLanes * SPILL_DEPTH);
+        M.spill = sd.spill.p;
     }
-    sd.mergedRays = merged;
+    int *dflag = nullptr; HIP_TRY(hipHostGetDevicePointer((void **) &dflag, sc->cancelFlag, 0));
+    M.cancel = dflag;
+#if MEGA_MB_FAULT
+    /* fault-injection build (tests/test_gpu_parity.py), read at every call: PHIP_TEST_FAULT_WAVES = wave0 (the default) | block (the four waves of block 0) | all | none
+       report that they gave up, in pass PHIP_TEST_FAULT_PASS of the call (default: every pass); PHIP_TEST_FAULT_SHORT = 1: they also under-report one sample each,
+       2: they only under-report (the host's exact count must catch it) */
+    {
+        const char *w = getenv("PHIP_TEST_FAULT_WAVES"), *sh = getenv("PHIP_TEST_FAULT_SHORT");
+        F.faultWaves = !w || !strcmp(w, "wave0") ? 1u : !strcmp(w, "block") ? 2u : !strcmp(w, "all") ? 3u : 0u;
+        F.faultPass = getenv("PHIP_TEST_FAULT_PASS") ? atoi(getenv("PHIP_TEST_FAULT_PASS")) : -1;
+        M.faultShort = sh ? (uint32_t) atoi(sh) : 0u;
+    }
+#endif
+    J.P.stat = sd.stat.p; J.P.nWaves = M.nWaves;               /* k_reduce_stats reads these two */
+}
+
+/* The wavefront path's kernels and grids, for the pool of setupWavefront */
+static void setupWavefrontGrids(RenderJob &J) {
+    phip_scene *sc = J.sc; WavefrontPlan &wf = J.wf;
+    const DevScene &D = J.D; const uint32_t capacity = wf.capacity; const int nCU = J.nCU;
+    /* environment emitter, bitmap textures; 8: the QMC samplers (two builds: the plain one, and one with both other features) */
+    const int feat0 = (D.envEmitter >= 0 ? 1 : 0) | (sc->hasTextures ? 2 : 0);
+    wf.feat = J.qmc ? (feat0 ? 11 : 8) : feat0;
+    wf.shadeTraceLds = shadeTraceLdsBytes(D);
+    wf.ldsBytes = traversalLdsBytes(D);
     /* persistent kernels: exactly the resident set (TRACE_WAVES waves per SIMD = TRACE_WAVES blocks of 256 per CU)
        ... but never more blocks per CU than their LDS (stack + node/record cache) allows: a persistent grid larger than
        the resident set would serialise */
@@ -1308,357 +1308,444 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
        node cache grew to 7.5 KB (round 2). */
     auto residentBlocks = [&](const void *kernel, int wanted) {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, BLOCK, ldsBytes) != hipSuccess || n <= 0) n = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, BLOCK, wf.ldsBytes) != hipSuccess || n <= 0) n = 1;
         return std::min(n, wanted);
     };
     [[maybe_unused]] auto persistentGrid = [&](const void *kernel, int blocksPerCU) {
         return dim3((unsigned) std::max(1, std::min<int>(nCU * residentBlocks(kernel, blocksPerCU), (int) ((capacity + BLOCK - 1) / BLOCK))));
     };
-    const dim3 grid((capacity + BLOCK - 1) / BLOCK);
+    wf.grid = dim3((capacity + BLOCK - 1) / BLOCK);
 #if PHIP_EXPERIMENTS
-    const dim3 pgrid = persistentGrid((const void *) k_shadow_p, TRACE_WAVES);
-    const dim3 pgridTrace = persistentGrid(sc->bvh.nNodes >= 64 ? (const void *) k_trace_p<false> : (const void *) k_trace_p<true>, TRACE_P_WAVES);
+    wf.pgrid = persistentGrid((const void *) k_shadow_p, TRACE_WAVES);
+    wf.pgridTrace = persistentGrid(sc->bvh.nNodes >= 64 ? (const void *) k_trace_p<false> : (const void *) k_trace_p<true>, TRACE_P_WAVES);
+    wf.pgridRays = persistentGrid((const void *) k_rays_p, RAYS_WAVES);       /* (PHIP_WIDE=0: the BVH4 ray kernels of rounds 1-2 on the big scenes) */
+    wf.forcePersist = expEnv("PHIP_TRACE_PERSIST") != nullptr;
 #endif
     /* k_rays_w: blocks of WIDE_BLOCK threads with their own LDS plan (one block per CU holds 800 nodes of the tree) */
-    const size_t wideLds = sc->wide ? wideLdsBytes(D.wideNodeCache, WIDE_BLOCK) + wideDealBytes(WIDE_BLOCK) : 0;
-#if PHIP_EXPERIMENTS
-    dim3 pgridRays = persistentGrid((const void *) k_rays_p, RAYS_WAVES);       /* (PHIP_WIDE=0: the BVH4 ray kernels of rounds 1-2 on the big scenes) */
-#else
-    dim3 pgridRays(1);
-#endif
+    wf.wideLds = sc->wide ? wideLdsBytes(D.wideNodeCache, WIDE_BLOCK) + wideDealBytes(WIDE_BLOCK) : 0;
     if (sc->wide) {
-        if (wideLds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *) k_rays_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int) wideLds));
+        if (wf.wideLds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *) k_rays_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int) wf.wideLds));
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *) k_rays_w, WIDE_BLOCK, wideLds) != hipSuccess || n <= 0) n = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *) k_rays_w, WIDE_BLOCK, wf.wideLds) != hipSuccess || n <= 0) n = 1;
         n = std::min(n, WIDE_WAVES * 256 / WIDE_BLOCK);
         if (n <= 0) n = 1;
-        pgridRays = dim3((unsigned) std::max(1, std::min<int>(nCU * n, (int) ((capacity + WIDE_BLOCK - 1) / WIDE_BLOCK))));
+        wf.pgridRays = dim3((unsigned) std::max(1, std::min<int>(nCU * n, (int) ((capacity + WIDE_BLOCK - 1) / WIDE_BLOCK))));
+        /* k_rays_w draws its chunks from sharded counters */
+        if (J.sd.drawCounters.n < 2 * RAY_SHARDS * RAY_SHARD_STRIDE) J.sd.drawCounters.alloc(2 * RAY_SHARDS * RAY_SHARD_STRIDE);
     }
-#if PHIP_EXPERIMENTS
-    const bool forcePersist = expEnv("PHIP_TRACE_PERSIST") != nullptr;
-#endif
+}
 
-    /* fused path: resident grid and per-wave statistics rows */
-    dim3 megaGrid(1); MegaParams M; memset(&M, 0, sizeof(M));
-#if MEGA_MB_FAULT
-    uint32_t faultWaves = 0; int faultPass = -1;
-#endif
-    if (fused) {
-        megaGrid = dim3((unsigned) (nCU * megaPerCU));
-        M.nWaves = megaGrid.x * (BLOCK / 64);
-        if (sd.stat.n < (size_t) ST_COUNT * M.nWaves) sd.stat.alloc((size_t) ST_COUNT * M.nWaves);
-        M.stat = sd.stat.p; M.nextId = sd.megaNext.p;
-        M.nodeCache = megaNodeCache; M.spill = nullptr;
-        if (megaWide) {     /* the group stacks' overflow behind their six LDS entries: the buffer always covers the grid, as for k_rays_w (a silent out-of-bounds write otherwise) */
-            const size_t spillLanes = (size_t) megaGrid.x * BLOCK;
-            if (sd.spill.n < spillLanes * SPILL_DEPTH) sd.spill.alloc(spillLanes * SPILL_DEPTH);
-            M.spill = sd.spill.p;
+/* The wavefront path's pool, sized for a first pass of idsFirstPass sample ids and for the memory that is free now; then its kernels and grids */
+static void setupWavefront(RenderJob &J, unsigned long long idsFirstPass) {
+    phip_scene *sc = J.sc; SceneDev &sd = J.sd; WavefrontPlan &wf = J.wf; PathPool &P = J.P;
+    /* pool size: large enough that per-launch fixed costs vanish, small enough that the tail (slots
+       running dry at the end of a pass) stays a small fraction of the pass (measured: 4M / 8M slots) */
+    /* (round 3) Every launch of the persistent ray kernel ends with a drain in which each wave waits for its longest ray while the
+       work queue is empty: ~0.15 ms per launch on the 250 k-triangle scenes, 14 % of a launch over 4 M slots, 7 % over 8 M.  A bigger
+       pool means fewer, longer launches: atrium 1920x1080x64 spp 427 / 454 / 470 / 470 Msamples/s with 4 / 8 / 16 / 32 M slots, the
+       glass room at 512 spp 480 / 496 / 505 with 8 / 16 / 32 M -- so the pool grows with the job (about 0.14 KB of HBM per slot). */
+    /* (round 4, after the ray kernel's triangle rounds: 8 / 16 / 32 / 64 M slots on the 4K slice (531 M ids) 610 / 636 / 646 / 657 Msamples/s, C4 at 512 spp (1062 M ids)
+       flat at 64 M and -2 % at 128 M, C3 (133 M ids) flat from 16 M on: jobs of more than 256 M ids get 64 M slots) */
+    /* (round 5: k_shade_trace has no persistent ray kernel whose drain a big pool amortises -- what a big pool costs it is the tail of the pass, the launches
+       in which the long paths of a few slots finish: mixed Cornell box at 256 spp with 1 / 2 / 4 / 8 / 16 M slots 1518 / 1617 / 1643 / 1596 / 1450 Msamples/s,
+       profiles/r05_gpu_call_e_*) */
+    const unsigned long long poolCap = wf.shadeTrace ? (1ull << 22)
+                                     : idsFirstPass > (256ull << 20) ? (1ull << 26) : idsFirstPass >= (64ull << 20) ? (1ull << 24)
+                                     : idsFirstPass >= (16ull << 20) ? (1ull << 23) : (1ull << 22);
+    uint32_t capacity = (uint32_t) std::min<unsigned long long>(std::max<unsigned long long>(idsFirstPass, BLOCK), poolCap);
+    /* traversal-stack overflow: SPILL_DEPTH words per LANE of a ray kernel -- the wide tree is only walked by persistent grids
+       (at most 8 resident blocks of 256 per CU), the BVH4 also by one-lane-per-slot launches */
+    const bool canSpill = sc->wide ? (int) sc->bvh.wMaxDepth + 2 > WIDE_STACK_LDS : 3 * ((int) sc->bvh.maxDepth - 1) + 1 > (int) J.D.stackDepth;
+    const bool persistentOnly = sc->wide || (sc->traversal == 2 && sc->bvh.nNodes >= 64 && !expEnv("PHIP_MERGED"));
+    {   /* ... and with the memory that is there: the pool's state is ~144 B per slot (+ 384 B of spill stack where every slot is a lane that can
+           spill); it may take a quarter of what is free now (a shared or partitioned GPU, n_devices replicas), never less than the 4 M slots
+           every job ran with before the pool grew */
+        size_t freeB = 0, totalB = 0;
+        if (sd.rayO.n < capacity && hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
+            unsigned long long fit = (unsigned long long) (freeB / 4) / (144ull + ((!persistentOnly && canSpill) ? (unsigned long long) SPILL_DEPTH * 4ull : 0ull));
+            while (capacity > (1u << 22) && capacity > fit) capacity >>= 1;
         }
-        int *dflag = nullptr; HIP_TRY(hipHostGetDevicePointer((void **) &dflag, sc->cancelFlag, 0));
-        M.cancel = dflag;
-#if MEGA_MB_FAULT
-        /* fault-injection build (tests/test_gpu_parity.py), read at every call: PHIP_TEST_FAULT_WAVES = wave0 (the default) | block (the four waves of block 0) | all | none
-           report that they gave up, in pass PHIP_TEST_FAULT_PASS of the call (default: every pass); PHIP_TEST_FAULT_SHORT = 1: they also under-report one sample each,
-           2: they only under-report (the host's exact count must catch it) */
-        {
-            const char *w = getenv("PHIP_TEST_FAULT_WAVES"), *sh = getenv("PHIP_TEST_FAULT_SHORT");
-            faultWaves = !w || !strcmp(w, "wave0") ? 1u : !strcmp(w, "block") ? 2u : !strcmp(w, "all") ? 3u : 0u;
-            faultPass = getenv("PHIP_TEST_FAULT_PASS") ? atoi(getenv("PHIP_TEST_FAULT_PASS")) : -1;
-            M.faultShort = sh ? (uint32_t) atoi(sh) : 0u;
-        }
-#endif
-        P.stat = sd.stat.p; P.nWaves = M.nWaves;               /* k_reduce_stats reads these two */
     }
+    capacity = (capacity + BLOCK - 1) / BLOCK * BLOCK;
+    if (const char *e = expEnv("PHIP_POOL")) { capacity = (uint32_t) std::max(BLOCK, atoi(e)) / BLOCK * BLOCK; }
+    const size_t laneCap = ((size_t) capacity + WIDE_BLOCK - 1) / WIDE_BLOCK * WIDE_BLOCK;      /* k_rays_w runs whole blocks of WIDE_BLOCK lanes */
+    const uint32_t nWaves = (uint32_t) (laneCap / 64), nBlocks = capacity / BLOCK;
+    if (sd.rayO.n < capacity) {
+        sd.rayO.alloc(capacity); sd.rayD.alloc(capacity); sd.hit.alloc(capacity); sd.thr.alloc(capacity);
+        sd.mis.alloc(capacity); sd.info.alloc(capacity); sd.state.alloc(capacity); sd.shadow.alloc(3 * (size_t) capacity);
+        sd.shadowCount.alloc(nBlocks); sd.blockDead.alloc(nBlocks); sd.blockShard.alloc(nBlocks);
+    }
+    {   /* persistent grids (at most 8 resident blocks of 256 per CU): the buffer always covers the whole grid, also when the host's depth bound says
+           that no lane can reach it -- 200 MB of 288 GB against a silent out-of-bounds write should that hand-derived bound ever be off.  One lane
+           per slot (BVH4 trees of < 64 nodes: small scenes with non-diffuse materials, every `direct` render of a small scene): 384 B per SLOT of a
+           pool of up to 64 M slots is 3..25 GB for a stack that is at most ~20 entries deep on such a tree -- there the bound decides, as before
+           round 4; when it says "can spill" the full size is allocated AND priced in the free-memory guard above */
+        const size_t spillLanes = persistentOnly ? std::min<size_t>(laneCap, (size_t) J.nCU * 8 * 256) : (canSpill ? laneCap : (size_t) WIDE_BLOCK);
+        if (sd.spill.n < spillLanes * SPILL_DEPTH) sd.spill.alloc(spillLanes * SPILL_DEPTH);
+        P.spillLanes = (uint32_t) std::min<size_t>(sd.spill.n / SPILL_DEPTH, 0xFFFFFFFFu);
+    }
+    if (sd.stat.n < (size_t) ST_COUNT * nWaves) sd.stat.alloc((size_t) ST_COUNT * nWaves);
+    if (J.direct && sd.camHit.n < capacity) sd.camHit.alloc(capacity);
+    P.camHit = sd.camHit.p;
+    P.rayO = sd.rayO.p; P.rayD = sd.rayD.p; P.hit = sd.hit.p; P.thr = sd.thr.p; P.mis = sd.mis.p; P.info = sd.info.p; P.state = sd.state.p;
+    P.shadow = sd.shadow.p; P.shadowCount = sd.shadowCount.p; P.blockDead = sd.blockDead.p; P.stat = sd.stat.p; P.spill = sd.spill.p; P.capacity = capacity; P.nWaves = nWaves;
+    J.rc.blockShard = sd.blockShard.p;
+    wf.capacity = capacity; wf.nWaves = nWaves; wf.nBlocks = nBlocks;
+    /* big trees: closest-hit and any-hit rays share one persistent launch (measured +2..4 % on the 250k-triangle scenes;
+       on small trees the plain per-slot closest-hit launch wins, so the kernels stay separate there) */
+    wf.merged = sc->traversal == 2 && sc->bvh.nNodes >= 64;
+    if (const char *e = expEnv("PHIP_MERGED")) wf.merged = sc->traversal == 2 && atoi(e) != 0;
+    if (sc->wide) wf.merged = true;                             /* the wide tree has the merged kernel only */
+    sd.mergedRays = wf.merged;
+    setupWavefrontGrids(J);
+}
 
-    for (uint32_t sppDone = 0; sppDone < (uint32_t) p->spp && !cancelled; sppDone += sppPerPass) {
-        RenderConst rc;
-        rc.sppPass = std::min(sppPerPass, (uint32_t) p->spp - sppDone); rc.sppFirst = (uint32_t) p->sample_offset + sppDone;
-        rc.sppMagic = (uint32_t) std::min<unsigned long long>((1ull << 32) / rc.sppPass, 0xFFFFFFFFull);
-        rc.tilePixels = (uint32_t) tilePixels; rc.tileShift = (uint32_t) tileShift; rc.nLocalTiles = nLocalTiles;
-        rc.totalIds = idsPerSpp * rc.sppPass;
-        rc.maxDepth = p->max_depth; rc.rrDepth = p->rr_depth; rc.strictNormals = p->strict_normals; rc.hideEmitters = p->hide_emitters;
-        rc.seed = p->seed; rc.tileOrigin = sd.tileOrigin.p; rc.countAlive = 0;
-        rc.sampler = (uint32_t) p->sampler; rc.ldMask = (uint32_t) (p->sample_total > 0 ? p->sample_total : p->spp) - 1u;
-        memset(&rc.sobol, 0, sizeof(rc.sobol)); rc.stRes = 1;
-        if (p->sampler == PHIP_SAMPLER_SOBOL) {
-            rc.sobol.matrices = sd.sobolMat.p; rc.sobol.vdc = (const uint64_t *) sd.sobolVdc.p; rc.sobol.vdcInv = (const uint64_t *) sd.sobolVdc.p + PHIP_SOBOL_MATRIX_SIZE;
-            rc.sobol.dims = p->sobol_dimensions; rc.sobol.logRes = p->sobol_log_resolution; rc.sobol.scramble = (uint32_t) p->sobol_scramble;
-            rc.sobol.resolution = (float) (1u << p->sobol_log_resolution);
-            if (!(PHIP_EXPERIMENTS && expEnv("PHIP_SOBOL_BITWISE"))) {      /* (experiment builds, A/B: the row-by-row loops of sobolseq.h -- the product's device code has the byte tables only) */
-                rc.sobol.matBt = sd.sobolBt.p;
-                rc.sobol.vdcBt = (const uint64_t *) sd.sobolVdcBt.p; rc.sobol.vdcInvBt = (const uint64_t *) sd.sobolVdcBt.p + 4u * 256u;
-            }
-        } else if (p->sampler == PHIP_SAMPLER_STRATIFIED) {
-            const unsigned n = (unsigned) (p->sample_total > 0 ? p->sample_total : p->spp);
-            unsigned r = 1; while (r * r < n) ++r;
-            rc.stRes = r;
+/* HaltonSampler / HammersleySampler::setFilmResolution(res, blocked = true): the partition of the sequence over the pixels */
+static void rinvFilmResolution(RinvTab &T, bool halton, const uint32_t res[2]) {
+    if (halton) {
+        /* halton.cpp:244-266 */
+        T.hammersley = 0; T.stride = 1;
+        uint32_t pw[2], ex[2];
+        for (int i = 0; i < 2; ++i) {
+            const uint32_t prime = i ? 3u : 2u; uint32_t value = 1, e = 0;
+            while (value < std::min(res[i], RINV_MAX_RESOLUTION)) { value *= prime; ++e; }
+            pw[i] = value; ex[i] = e; T.stride *= value;
         }
-        memset(&rc.rinv, 0, sizeof(rc.rinv));
-        if (rinv) {
-            RinvTab &T = rc.rinv;
-            T.primes = sd.rinvPrimes.p; T.perm = p->qmc_permutations ? sd.rinvPerm.p : nullptr; T.permOffset = sd.rinvOffsets.p; T.dims = p->qmc_dimensions;
-            T.invPerm2 = sd.rinvInvPerm2; T.invPerm3 = sd.rinvInvPerm3;
-            if (sd.rinvTabDims && !expEnv("PHIP_RINV_DIGITWISE")) {     /* (A/B: the digit-by-digit loops of qmc.cpp) */
-                T.dimInfo = sd.rinvDimInfo.p; T.chunk = sd.rinvChunk.p; T.fac = sd.rinvFac.p; T.pw = sd.rinvPw.p; T.tabDims = sd.rinvTabDims;
-            }
-            const uint32_t res[2] = { (uint32_t) D.film.width, (uint32_t) D.film.height };
-            T.sampleCount = (uint32_t) (p->sample_total > 0 ? p->sample_total : p->spp);
-            if (p->sampler == PHIP_SAMPLER_HALTON) {
-                /* HaltonSampler::setFilmResolution(res, blocked = true), halton.cpp:244-266 */
-                T.hammersley = 0; T.stride = 1;
-                uint32_t pw[2], ex[2];
-                for (int i = 0; i < 2; ++i) {
-                    const uint32_t prime = i ? 3u : 2u; uint32_t value = 1, e = 0;
-                    while (value < std::min(res[i], RINV_MAX_RESOLUTION)) { value *= prime; ++e; }
-                    pw[i] = value; ex[i] = e; T.stride *= value;
-                }
-                T.powX = pw[0]; T.powY = pw[1]; T.expX = ex[0]; T.expY = ex[1];
-                /* multiplicativeInverse(a, n): x with a x = 1 (mod n), in 0 .. n - 1 (halton.cpp:214-241; n = 1 gives 0) */
-                auto inverse = [](uint32_t a, uint32_t n) { for (uint32_t x = 0; x < n; ++x) if ((unsigned long long) a * x % n == 1u % n) return x; return 0u; };
-                T.multInvX = inverse(T.powY, T.powX); T.multInvY = inverse(T.powX, T.powY);
-            } else {
-                /* HammersleySampler::setFilmResolution(res, blocked = true), hammersley.cpp:181-196 */
-                T.hammersley = 1;
-                uint32_t r[2];
-                for (int i = 0; i < 2; ++i) { uint32_t v = 1; while (v < res[i]) v <<= 1; r[i] = std::min(RINV_MAX_RESOLUTION, v); }
-                T.powX = r[0]; T.powY = r[1]; T.expX = 0; T.expY = 0; while ((1u << T.expY) < r[1]) ++T.expY;
-                T.stride = r[1];
-                T.factor = 1.0f / (float) ((size_t) T.sampleCount * (size_t) r[0] * (size_t) r[1]);
-            }
-        }
-        rc.diffScaleFactor = 1.0f / sqrtf((float) (p->sample_total > 0 ? p->sample_total : p->spp));
-        rc.emitterSamples = direct ? p->emitter_samples : 0; rc.bsdfSamples = direct ? p->bsdf_samples : 0;
-        if (direct) {   /* direct.cpp:130-138 */
-            const size_t sum = (size_t) p->emitter_samples + (size_t) p->bsdf_samples;
-            rc.weightBSDF = 1 / (float) (size_t) p->bsdf_samples;
-            rc.weightLum = 1 / (float) (size_t) p->emitter_samples;
-            rc.fracBSDF = (size_t) p->bsdf_samples / (float) sum;
-            rc.fracLum = (size_t) p->emitter_samples / (float) sum;
-        } else {
-            rc.weightBSDF = rc.weightLum = 1.0f; rc.fracBSDF = rc.fracLum = 0.5f;
-        }
-        rc.envFiltered = (sc->envLevelCount > 1 && !(p->flags & PHIP_FLAG_ENVMAP_BILINEAR_BACKGROUND)) ? 1u : 0u;
-        rc.volpath = p->integrator == PHIP_INTEGRATOR_VOLPATH_SIMPLE ? 1u : 0u;
-        rc.staticIds = 0; rc.shardIds = 0; rc.dynCounter = sd.dynCounter.p; rc.blockShard = sd.blockShard.p;
-        rc.jitter = keepJitter ? sd.jitter.p : nullptr;
-        HIP_TRY(hipMemsetAsync(sd.counters.p, 0, sizeof(Counters), stream));
-        uint32_t iter = 0;
+        T.powX = pw[0]; T.powY = pw[1]; T.expX = ex[0]; T.expY = ex[1];
+        /* multiplicativeInverse(a, n): x with a x = 1 (mod n), in 0 .. n - 1 (halton.cpp:214-241; n = 1 gives 0) */
+        auto inverse = [](uint32_t a, uint32_t n) { for (uint32_t x = 0; x < n; ++x) if ((unsigned long long) a * x % n == 1u % n) return x; return 0u; };
+        T.multInvX = inverse(T.powY, T.powX); T.multInvY = inverse(T.powX, T.powY);
+    } else {
+        /* hammersley.cpp:181-196 */
+        T.hammersley = 1;
+        uint32_t r[2];
+        for (int i = 0; i < 2; ++i) { uint32_t v = 1; while (v < res[i]) v <<= 1; r[i] = std::min(RINV_MAX_RESOLUTION, v); }
+        T.powX = r[0]; T.powY = r[1]; T.expX = 0; T.expY = 0; while ((1u << T.expY) < r[1]) ++T.expY;
+        T.stride = r[1];
+        T.factor = 1.0f / (float) ((size_t) T.sampleCount * (size_t) r[0] * (size_t) r[1]);
+    }
+}
 
-        if (fused) {
-            /* ---- one launch: every path of the pass from camera sample to its last vertex (k_mega.h) ---- */
-            HIP_TRY(hipMemsetAsync(sd.megaNext.p, 0, sizeof(unsigned long long), stream));
-            HIP_TRY(hipMemsetAsync(sd.stat.p, 0, (size_t) ST_COUNT * M.nWaves * sizeof(unsigned long long), stream));
+/* The RenderConst fields that hold for every pass of the call (J.rc starts zeroed) */
+static void callConstants(RenderJob &J) {
+    phip_scene *sc = J.sc; SceneDev &sd = J.sd; const phip_render_params *p = J.p; RenderConst &rc = J.rc;
+    rc.tilePixels = (uint32_t) (J.bs * J.bs); rc.tileShift = (uint32_t) J.tileShift; rc.nLocalTiles = sd.nLocalTiles;
+    rc.maxDepth = p->max_depth; rc.rrDepth = p->rr_depth; rc.strictNormals = p->strict_normals; rc.hideEmitters = p->hide_emitters;
+    rc.seed = p->seed; rc.tileOrigin = sd.tileOrigin.p;
+    rc.sampler = (uint32_t) p->sampler; rc.ldMask = J.sampleTotal() - 1u;
+    rc.stRes = 1;
+    if (p->sampler == PHIP_SAMPLER_SOBOL) {
+        rc.sobol.matrices = sd.sobolMat.p; rc.sobol.vdc = (const uint64_t *) sd.sobolVdc.p; rc.sobol.vdcInv = (const uint64_t *) sd.sobolVdc.p + PHIP_SOBOL_MATRIX_SIZE;
+        rc.sobol.dims = p->sobol_dimensions; rc.sobol.logRes = p->sobol_log_resolution; rc.sobol.scramble = (uint32_t) p->sobol_scramble;
+        rc.sobol.resolution = (float) (1u << p->sobol_log_resolution);
+        if (!(PHIP_EXPERIMENTS && expEnv("PHIP_SOBOL_BITWISE"))) {      /* (experiment builds, A/B: the row-by-row loops of sobolseq.h -- the product's device code has the byte tables only) */
+            rc.sobol.matBt = sd.sobolBt.p;
+            rc.sobol.vdcBt = (const uint64_t *) sd.sobolVdcBt.p; rc.sobol.vdcInvBt = (const uint64_t *) sd.sobolVdcBt.p + 4u * 256u;
+        }
+    } else if (p->sampler == PHIP_SAMPLER_STRATIFIED) {
+        const unsigned n = J.sampleTotal();
+        unsigned r = 1; while (r * r < n) ++r;
+        rc.stRes = r;
+    }
+    if (J.rinv) {
+        RinvTab &T = rc.rinv;
+        T.primes = sd.rinvPrimes.p; T.perm = p->qmc_permutations ? sd.rinvPerm.p : nullptr; T.permOffset = sd.rinvOffsets.p; T.dims = p->qmc_dimensions;
+        T.invPerm2 = sd.rinvInvPerm2; T.invPerm3 = sd.rinvInvPerm3;
+        if (sd.rinvTabDims && !expEnv("PHIP_RINV_DIGITWISE")) {     /* (A/B: the digit-by-digit loops of qmc.cpp) */
+            T.dimInfo = sd.rinvDimInfo.p; T.chunk = sd.rinvChunk.p; T.fac = sd.rinvFac.p; T.pw = sd.rinvPw.p; T.tabDims = sd.rinvTabDims;
+        }
+        const uint32_t res[2] = { (uint32_t) J.D.film.width, (uint32_t) J.D.film.height };
+        T.sampleCount = J.sampleTotal();
+        rinvFilmResolution(T, p->sampler == PHIP_SAMPLER_HALTON, res);
+    }
+    rc.diffScaleFactor = 1.0f / sqrtf((float) (p->sample_total > 0 ? p->sample_total : p->spp));
+    rc.emitterSamples = J.direct ? p->emitter_samples : 0; rc.bsdfSamples = J.direct ? p->bsdf_samples : 0;
+    if (J.direct) {   /* direct.cpp:130-138 */
+        const size_t sum = (size_t) p->emitter_samples + (size_t) p->bsdf_samples;
+        rc.weightBSDF = 1 / (float) (size_t) p->bsdf_samples;
+        rc.weightLum = 1 / (float) (size_t) p->emitter_samples;
+        rc.fracBSDF = (size_t) p->bsdf_samples / (float) sum;
+        rc.fracLum = (size_t) p->emitter_samples / (float) sum;
+    } else {
+        rc.weightBSDF = rc.weightLum = 1.0f; rc.fracBSDF = rc.fracLum = 0.5f;
+    }
+    rc.envFiltered = (sc->envLevelCount > 1 && !(p->flags & PHIP_FLAG_ENVMAP_BILINEAR_BACKGROUND)) ? 1u : 0u;
+    rc.volpath = p->integrator == PHIP_INTEGRATOR_VOLPATH_SIMPLE ? 1u : 0u;
+    rc.dynCounter = sd.dynCounter.p;        /* (blockShard: with the pool, setupWavefront) */
+    rc.jitter = J.keepJitter ? sd.jitter.p : nullptr;
+}
+
+/* ... and the ones of the pass that starts at sample sppDone of the call */
+static void passConstants(RenderJob &J, uint32_t sppDone) {
+    RenderConst &rc = J.rc;
+    rc.sppPass = std::min(J.sppPerPass, (uint32_t) J.p->spp - sppDone); rc.sppFirst = (uint32_t) J.p->sample_offset + sppDone;
+    rc.sppMagic = (uint32_t) std::min<unsigned long long>((1ull << 32) / rc.sppPass, 0xFFFFFFFFull);
+    rc.totalIds = J.idsPerSpp * rc.sppPass;
+    rc.staticIds = 0; rc.shardIds = 0; rc.countAlive = 0; rc.draining = 0;
+}
+
+enum class FusedPass { Done, GaveUp, Cancelled };
+
+/* One launch: every path of the pass from camera sample to its last vertex (k_mega.h) */
+static FusedPass fusedPass(RenderJob &J, uint32_t sppDone) {
+    phip_scene *sc = J.sc; SceneDev &sd = J.sd; FusedPlan &F = J.F; hipStream_t stream = J.stream;
+    const RenderConst &rc = J.rc; Counters &hc = J.hc;
+    const unsigned long long samplesTotal = sd.localPixels;                  /* crop pixels of this device's blocks */
+    HIP_TRY(hipMemsetAsync(sd.counters.p, 0, sizeof(Counters), stream));
+    HIP_TRY(hipMemsetAsync(sd.megaNext.p, 0, sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(sd.stat.p, 0, (size_t) ST_COUNT * F.M.nWaves * sizeof(unsigned long long), stream));
 #if MEGA_MB_FAULT
-            M.faultWaves = (faultPass < 0 || (uint32_t) faultPass == sppDone / sppPerPass) ? faultWaves : 0u;
+    F.M.faultWaves = (F.faultPass < 0 || (uint32_t) F.faultPass == sppDone / J.sppPerPass) ? F.faultWaves : 0u;
+#else
+    (void) sppDone;
 #endif
-            if (rc.totalIds) {
-                if (timing) evFused.record(stream);
-                if (direct) phipLaunchMegaDirect(sc->materialMask, false, megaFlat, qmc, megaGrid, megaLds, stream, D, M, rc, sd.L.p);
-                else if (megaWide) phipLaunchMegaWide(sc->materialMask, p->strict_normals != 0, megaFlat, qmc, megaGrid, megaLds, stream, D, M, rc, sd.L.p);
-                else phipLaunchMega(sc->materialMask, p->strict_normals != 0, megaFlat, qmc, megaGrid, megaLds, stream, D, M, rc, sd.L.p);
-                if (timing) evFused.record(stream);
-                iter = 1;
-            }
-            HIP_TRY(hipGetLastError());
-            /* k_mega bounds every wait of its mailbox protocol and the depth of its task stacks; a wave that gave up says so in the ST_GAVE_UP row (k_mega.h).  Such a pass
-               is incomplete: it is not added to the film -- this pass and the rest of the job run on the kernels that have no such protocol (round 6: degrade, do not fail).
-               A pass that was not cancelled must also have counted exactly one sample per crop pixel of this device's blocks and sample of the pass (the ids of edge
-               blocks outside the crop window are drawn and skipped: rc.totalIds counts them, the samples do not) */
-            HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_SAMPLES], 0, (ST_GAVE_UP - ST_SAMPLES + 1) * sizeof(unsigned long long), stream));
-            static_assert(ST_GAVE_UP == ST_SAMPLES + 2, "the rows the host reads after a fused pass: samples .. gave up");
-            hipLaunchKernelGGL(k_reduce_stats, dim3(ST_GAVE_UP - ST_SAMPLES + 1, REDUCE_SPLIT), dim3(256), 0, stream, P, sd.counters.p, (int) ST_SAMPLES);
-            HIP_TRY(hipMemcpyAsync(&hc.total[ST_SAMPLES], &sd.counters.p->total[ST_SAMPLES], (ST_GAVE_UP - ST_SAMPLES + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (cancelRequested(sc)) cancelled = true;
-            const bool gaveUp = hc.total[ST_GAVE_UP] != 0;
+    if (rc.totalIds) {
+        if (J.timing) J.evFused.record(stream);
+        F.launch(sc->materialMask, F.strictNormals, F.flat, J.qmc, F.grid, F.lds, stream, J.D, F.M, rc, sd.L.p);
+        if (J.timing) J.evFused.record(stream);
+    }
+    HIP_TRY(hipGetLastError());
+    /* k_mega bounds every wait of its mailbox protocol and the depth of its task stacks; a wave that gave up says so in the ST_GAVE_UP row (k_mega.h).  Such a pass
+       is incomplete: it is not added to the film -- this pass and the rest of the job run on the kernels that have no such protocol (round 6: degrade, do not fail).
+       A pass that was not cancelled must also have counted exactly one sample per crop pixel of this device's blocks and sample of the pass (the ids of edge
+       blocks outside the crop window are drawn and skipped: rc.totalIds counts them, the samples do not) */
+    HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_SAMPLES], 0, (ST_GAVE_UP - ST_SAMPLES + 1) * sizeof(unsigned long long), stream));
+    static_assert(ST_GAVE_UP == ST_SAMPLES + 2, "the rows the host reads after a fused pass: samples .. gave up");
+    hipLaunchKernelGGL(k_reduce_stats, dim3(ST_GAVE_UP - ST_SAMPLES + 1, REDUCE_SPLIT), dim3(256), 0, stream, J.P, sd.counters.p, (int) ST_SAMPLES);
+    HIP_TRY(hipMemcpyAsync(&hc.total[ST_SAMPLES], &sd.counters.p->total[ST_SAMPLES], (ST_GAVE_UP - ST_SAMPLES + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const bool cancelled = cancelRequested(sc);
+    const bool gaveUp = hc.total[ST_GAVE_UP] != 0;
 #if MEGA_PROFILE || MEGA_MB_DIAG
-            const bool countKnown = false;              /* (measurement builds of k_mega: the sample row holds what they measure) */
+    const bool countKnown = false;              /* (measurement builds of k_mega: the sample row holds what they measure) */
 #else
-            const bool countKnown = true;
+    const bool countKnown = true;
 #endif
-            if (!cancelled && (gaveUp || (countKnown && hc.total[ST_SAMPLES] != samplesTotal * rc.sppPass))) {
-                fprintf(stderr, "[phip] warning: the fused kernel gave up on this pass (%s); samples %u.. of the job are rendered by the wavefront kernels\n",
-                        !gaveUp ? "it counted a wrong number of samples" : megaWide ? "a task stack outgrew LDS + spill buffer" : "a mailbox wait timed out",
-                        (unsigned) (p->sample_offset + sppDone));
-                /* the rest of the job -- this pass and the ones after it -- on the wavefront kernels, as a continuation of THIS call: the same passes, the caller's sample
-                   buffer at the caller's stride, progress against the caller's total, the film of the passes before accumulated onto */
-                phip_render_params q = *p;
-                q.flags |= PHIP_FLAG_NO_MEGA | PHIP_FLAG_NO_FUSED;
-                q.sample_total = p->sample_total > 0 ? p->sample_total : p->spp;
-                q.sample_offset = p->sample_offset + (int) sppDone; q.spp = p->spp - (int) sppDone;
-                if (sppDone > 0) q.flags |= PHIP_FLAG_ACCUMULATE;
-                const JobSoFar soFar{ jobSpp, jobOffset, samplesDone, callerAccumulate };
-                phip_stats st2; memset(&st2, 0, sizeof(st2));
-                const int rc2 = renderOnDevice(sc, sd, &q, shardIndex, shardCount, dOut, &st2, &soFar);
-                st2.samples += st.samples; st2.closest_rays += st.closest_rays; st2.shadow_rays += st.shadow_rays; st2.path_vertices += st.path_vertices;
-                st2.closest_node_visits += st.closest_node_visits; st2.closest_triangle_tests += st.closest_triangle_tests;
-                st2.shadow_node_visits += st.shadow_node_visits; st2.shadow_triangle_tests += st.shadow_triangle_tests; st2.iterations += st.iterations;
-                st2.fused_kernel_ms += evFused.sumPairs();
-                st2.fused = 0;                                  /* (part of the frame came from the wavefront kernels) */
-                st2.render_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-                if (stats) *stats = st2;
-                return rc2;
-            }
-        } else {
-            /* static share: the first 3/4 of every slot's samples; the remainder is handed out dynamically */
-            {
-                const unsigned long long perSlot = rc.totalIds / capacity;
-                unsigned long long staticPerSlot = perSlot - perSlot / 4;
-                if (const char *e = expEnv("PHIP_STATIC_PERCENT")) staticPerSlot = perSlot * (unsigned long long) atoi(e) / 100;
-                rc.staticIds = staticPerSlot * capacity;
-                const unsigned long long dyn = rc.totalIds - rc.staticIds;
-                rc.shardIds = (dyn + DYN_SHARDS - 1) / DYN_SHARDS;
-                HIP_TRY(hipMemsetAsync(sd.blockShard.p, 0, nBlocks * sizeof(uint32_t), stream));
-                HIP_TRY(hipMemsetAsync(sd.dynCounter.p, 0, DYN_SHARDS * DYN_STRIDE * sizeof(unsigned long long), stream));
-            }
-            HIP_TRY(hipMemsetAsync(sd.stat.p, 0, (size_t) ST_COUNT * nWaves * sizeof(unsigned long long), stream));
-            HIP_TRY(hipMemsetAsync(sd.shadowCount.p, 0, (size_t) nBlocks * sizeof(uint32_t), stream));
-            HIP_TRY(hipMemsetAsync(sd.blockDead.p, 0, (size_t) nBlocks * sizeof(uint32_t), stream));
-            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) sd.state.p, (int) F_FRESH, (size_t) capacity, stream));
-            /* (no clear of L: the first vertex of every sample -- or its camera ray leaving the scene -- writes L[id]) */
-
-            HIP_TRY(hipStreamSynchronize(stream));
-            const auto tLoop0 = clk::now();
-            bool done = rc.totalIds == 0;
-            bool drainingSeen = false;                          /* a termination test has counted fewer live slots than the pool holds: blocks may have retired */
-            /* environment emitter, bitmap textures; 8: the QMC samplers (two builds: the plain one, and one with both other features) */
-            const int feat0 = (D.envEmitter >= 0 ? 1 : 0) | (sc->hasTextures ? 2 : 0), feat = qmc ? (feat0 ? 11 : 8) : feat0;
-            const size_t shadeTraceLds = shadeTraceLdsBytes(D);
-            while (!done) {
-                const bool check = ((iter + 1) & 7) == 0 || rc.totalIds <= (unsigned long long) capacity * 4;
-                rc.countAlive = check ? 1 : 0;
-                rc.draining = drainingSeen ? 1u : 0u;
-                if (timing) evShade.record(stream);
-                if (direct) phipLaunchShadeDirect(feat, sc->materialMask, grid, stream, D, P, rc, sd.L.p);
-                else if (shadeTrace) phipLaunchShadeTrace(feat, rc.strictNormals != 0, sc->materialMask, grid, shadeTraceLds, stream, D, P, rc, sd.L.p);
-                else phipLaunchShade(feat, rc.strictNormals != 0, sc->materialMask, grid, stream, D, P, rc, sd.L.p);
-                if (timing) evShade.record(stream);
-                if (shadeTrace) {
-                    /* (the vertex kernel traced both rays of the iteration itself: k_shade_trace.h) */
-                } else if (merged) {
-                    if (timing) evTrace.record(stream);
-                    if (sc->wide) {
-                        /* k_rays_w draws its chunks from sharded counters */
-                        if (sd.drawCounters.n < 2 * RAY_SHARDS * RAY_SHARD_STRIDE) sd.drawCounters.alloc(2 * RAY_SHARDS * RAY_SHARD_STRIDE);
-                        HIP_TRY(hipMemsetAsync(sd.drawCounters.p, 0, 2 * RAY_SHARDS * RAY_SHARD_STRIDE * sizeof(unsigned int), stream));
-                        hipLaunchKernelGGL(k_rays_w, pgridRays, dim3(WIDE_BLOCK), wideLds, stream, D, P, sd.L.p, sd.drawCounters.p);
-                    }
-#if PHIP_EXPERIMENTS
-                    else hipLaunchKernelGGL(k_rays_p, pgridRays, block, ldsBytes, stream, D, P, sd.L.p);
-#endif
-                    if (timing) evTrace.record(stream);
-                } else {
-#if PHIP_EXPERIMENTS      /* the BVH4 ray kernels of round 1 (PHIP_BVH4_RAYS=1 on a small scene, PHIP_WIDE=0 / PHIP_TRAVERSAL=lane): A/B only */
-                    if (timing) evShadow.record(stream);
-                    if (sc->traversal != 2) hipLaunchKernelGGL(k_shadow, grid, block, ldsBytes, stream, D, P, sd.L.p); else
-                    hipLaunchKernelGGL(k_shadow_p, pgrid, block, ldsBytes, stream, D, P, sd.L.p);
-                    if (timing) evShadow.record(stream);
-                    if (timing) evTrace.record(stream);
-                    if (sc->traversal == 2 && sc->bvh.nNodes >= 64) hipLaunchKernelGGL(k_trace_p<false>, pgridTrace, block, ldsBytes, stream, D, P);
-                    else if (sc->traversal == 2 && forcePersist) hipLaunchKernelGGL(k_trace_p<true>, pgridTrace, block, ldsBytes, stream, D, P);
-                    else
-                    hipLaunchKernelGGL(k_trace, grid, block, ldsBytes, stream, D, P);
-                    if (timing) evTrace.record(stream);
-#else
-                    throw std::runtime_error("internal error: no ray kernel for this scene (the wide tree is missing)");
-#endif
-                }
-                ++iter;
-                if (check) {
-                    /* termination test: only the live-slot row (and, for a progress callback, the finished-sample row) is summed inside the loop */
-                    HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_ALIVE], 0, sizeof(unsigned long long), stream));
-                    hipLaunchKernelGGL(k_reduce_stats, dim3(1, REDUCE_SPLIT), dim3(256), 0, stream, P, sd.counters.p, (int) ST_ALIVE);
-                    HIP_TRY(hipMemcpyAsync(&hc.total[ST_ALIVE], &sd.counters.p->total[ST_ALIVE], sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-                    if (p->progress) {
-                        HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_SAMPLES], 0, sizeof(unsigned long long), stream));
-                        hipLaunchKernelGGL(k_reduce_stats, dim3(1, REDUCE_SPLIT), dim3(256), 0, stream, P, sd.counters.p, (int) ST_SAMPLES);
-                        HIP_TRY(hipMemcpyAsync(&hc.total[ST_SAMPLES], &sd.counters.p->total[ST_SAMPLES], sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-                    }
-                    HIP_TRY(hipStreamSynchronize(stream));
-                    if (hc.total[ST_ALIVE] == 0) done = true;
-                    if (hc.total[ST_ALIVE] < capacity) drainingSeen = true;
-                    if (p->progress) { std::lock_guard<std::mutex> g(sc->progressLock); p->progress(p->progress_user, sd.device, samplesDone + hc.total[ST_SAMPLES], samplesTotal * (unsigned long long) jobSpp); }
-                    if (cancelRequested(sc)) { cancelled = true; done = true; }
-                }
-            }
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (getenv("PHIP_DEBUG_TIMING")) fprintf(stderr, "[phip] setup %.2f ms, loop %.2f ms (%u iterations)\n", std::chrono::duration<double, std::milli>(tLoop0 - t0).count(), std::chrono::duration<double, std::milli>(clk::now() - tLoop0).count(), iter);
-        }
-        st.iterations += iter;
-        if (cancelled) break;                                   /* L is incomplete: no film pass */
-
-        /* film */
-        if (timing) evFilm.record(stream);
-        {
-            const dim3 fg((W + 15) / 16, (H + 15) / 16);
-            const int reach = (int) std::floor(D.film.radius + 0.5f);
-            const int acc = (sppDone > 0 || accumulate) ? 1 : 0;
-            const char *fv = expEnv("PHIP_FILM_V1"); (void) fv;       /* experiment hook: the round-2 tiled kernel */
-            const bool splat = reach <= 2 && tileShift >= 4 && bs == (1 << tileShift) && nLocalTiles > 0 && !expEnv("PHIP_FILM_GATHER");     /* PHIP_FILM_GATHER: the tiled gathers of rounds 2 / 3 (A/B) */
-            if (splat) {
-                /* round 4: one pass over L with the footprint sums in registers, then an ordered merge of the 16 x 16 patch images (k_film.h) */
-                const int r = std::max(reach, 1), cells = (16 + 2 * r) * (16 + 2 * r) * 5;
-                const unsigned nPatches = (unsigned) nLocalTiles << (2 * (tileShift - 4));
-                if (sd.patchImg.n < (size_t) nPatches * cells) sd.patchImg.alloc((size_t) nPatches * cells);
-                const float4 *Lc = (const float4 *) sd.L.p;
-                if (r == 1) { if (qmc) hipLaunchKernelGGL((k_film_splat<1, true>), dim3(nPatches), dim3(256), 0, stream, D, rc, Lc, sd.patchImg.p, sd.invalid.p);
-                              else hipLaunchKernelGGL((k_film_splat<1, false>), dim3(nPatches), dim3(256), 0, stream, D, rc, Lc, sd.patchImg.p, sd.invalid.p);
-                              hipLaunchKernelGGL(k_film_merge<1>, fg, block, 0, stream, D, rc, (const float *) sd.patchImg.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut, acc); }
-                else        { if (qmc) hipLaunchKernelGGL((k_film_splat<2, true>), dim3(nPatches), dim3(256), 0, stream, D, rc, Lc, sd.patchImg.p, sd.invalid.p);
-                              else hipLaunchKernelGGL((k_film_splat<2, false>), dim3(nPatches), dim3(256), 0, stream, D, rc, Lc, sd.patchImg.p, sd.invalid.p);
-                              hipLaunchKernelGGL(k_film_merge<2>, fg, block, 0, stream, D, rc, (const float *) sd.patchImg.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut, acc); }
-            } else if (qmc)
-                hipLaunchKernelGGL(k_film<true>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut,
-                                   acc, sd.invalid.p);
-#if PHIP_EXPERIMENTS
-            else if (reach <= 2 && bs >= FILM_TILE + 2 * std::max(reach, 1) && !expEnv("PHIP_FILM_GENERIC") && !(fv && atoi(fv))) {
-                if (reach <= 1)
-                    hipLaunchKernelGGL(k_film_tiled2<1>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut, acc, sd.invalid.p);
-                else
-                    hipLaunchKernelGGL(k_film_tiled2<2>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut, acc, sd.invalid.p);
-            }
-#endif
-            else if (reach <= FILM_MAX_REACH && !expEnv("PHIP_FILM_GENERIC"))
-                if (reach <= 2)
-                    hipLaunchKernelGGL(k_film_tiled<2>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut,
-                                       acc, sd.invalid.p, reach);
-                else
-                    hipLaunchKernelGGL(k_film_tiled<FILM_MAX_REACH>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut,
-                                       acc, sd.invalid.p, reach);
-            else
-                hipLaunchKernelGGL(k_film<false>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut,
-                                   acc, sd.invalid.p);
-        }
-        if (timing) evFilm.record(stream);
-        if (keepSamples && rc.totalIds) {
-            const size_t n = (size_t) W * H * rc.sppPass;
-            hipLaunchKernelGGL(k_export_samples, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream, D, rc, (const float4 *) sd.L.p,
-                               (const int32_t *) sd.tileSlot.p, tilesX, sd.sampleOut.p, jobSpp, (uint32_t) jobOffset);
-        }
-        HIP_TRY(hipMemsetAsync(sd.counters.p, 0, sizeof(Counters), stream));
-        hipLaunchKernelGGL(k_reduce_stats, dim3(ST_COUNT, REDUCE_SPLIT), dim3(256), 0, stream, P, sd.counters.p, 0);
-        HIP_TRY(hipMemcpyAsync(&hc, sd.counters.p, sizeof(Counters), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipGetLastError());
-        st.samples += hc.total[ST_SAMPLES]; st.closest_rays += hc.total[ST_CLOSEST_RAYS]; st.shadow_rays += hc.total[ST_SHADOW_RAYS];
-        st.path_vertices += hc.total[ST_VERTICES]; st.closest_node_visits += hc.total[ST_NODE]; st.closest_triangle_tests += hc.total[ST_TRI];
-        st.shadow_node_visits += hc.total[ST_SH_NODE]; st.shadow_triangle_tests += hc.total[ST_SH_TRI];
-        samplesDone += hc.total[ST_SAMPLES];
-        if (p->progress) { std::lock_guard<std::mutex> g(sc->progressLock); p->progress(p->progress_user, sd.device, samplesDone, samplesTotal * (unsigned long long) jobSpp); }
+    if (!cancelled && (gaveUp || (countKnown && hc.total[ST_SAMPLES] != samplesTotal * rc.sppPass))) {
+        fprintf(stderr, "[phip] warning: the fused kernel gave up on this pass (%s); samples %u.. of the job are rendered by the wavefront kernels\n",
+                !gaveUp ? "it counted a wrong number of samples" : F.wide ? "a task stack outgrew LDS + spill buffer" : "a mailbox wait timed out",
+                (unsigned) rc.sppFirst);
+        return FusedPass::GaveUp;               /* (its launch is not one of the job's iterations) */
     }
-    if ((nLocalTiles == 0 || cancelled) && !callerAccumulate) { HIP_TRY(hipMemsetAsync(dOut, 0, (size_t) W * H * 5 * sizeof(float), stream)); HIP_TRY(hipStreamSynchronize(stream)); }
+    if (rc.totalIds) J.st.iterations += 1;
+    return cancelled ? FusedPass::Cancelled : FusedPass::Done;
+}
+
+/* The ray kernel(s) of one wavefront iteration */
+static void launchRayKernels(RenderJob &J) {
+    phip_scene *sc = J.sc; SceneDev &sd = J.sd; const WavefrontPlan &wf = J.wf; hipStream_t stream = J.stream;
+    [[maybe_unused]] const dim3 block(BLOCK);
+    if (wf.merged) {
+        if (J.timing) J.evTrace.record(stream);
+        if (sc->wide) {
+            HIP_TRY(hipMemsetAsync(sd.drawCounters.p, 0, 2 * RAY_SHARDS * RAY_SHARD_STRIDE * sizeof(unsigned int), stream));
+            hipLaunchKernelGGL(k_rays_w, wf.pgridRays, dim3(WIDE_BLOCK), wf.wideLds, stream, J.D, J.P, sd.L.p, sd.drawCounters.p);
+        }
+#if PHIP_EXPERIMENTS
+        else hipLaunchKernelGGL(k_rays_p, wf.pgridRays, block, wf.ldsBytes, stream, J.D, J.P, sd.L.p);
+#endif
+        if (J.timing) J.evTrace.record(stream);
+    } else {
+#if PHIP_EXPERIMENTS      /* the BVH4 ray kernels of round 1 (PHIP_BVH4_RAYS=1 on a small scene, PHIP_WIDE=0 / PHIP_TRAVERSAL=lane): A/B only */
+        if (J.timing) J.evShadow.record(stream);
+        if (sc->traversal != 2) hipLaunchKernelGGL(k_shadow, wf.grid, block, wf.ldsBytes, stream, J.D, J.P, sd.L.p); else
+        hipLaunchKernelGGL(k_shadow_p, wf.pgrid, block, wf.ldsBytes, stream, J.D, J.P, sd.L.p);
+        if (J.timing) J.evShadow.record(stream);
+        if (J.timing) J.evTrace.record(stream);
+        if (sc->traversal == 2 && sc->bvh.nNodes >= 64) hipLaunchKernelGGL(k_trace_p<false>, wf.pgridTrace, block, wf.ldsBytes, stream, J.D, J.P);
+        else if (sc->traversal == 2 && wf.forcePersist) hipLaunchKernelGGL(k_trace_p<true>, wf.pgridTrace, block, wf.ldsBytes, stream, J.D, J.P);
+        else
+        hipLaunchKernelGGL(k_trace, wf.grid, block, wf.ldsBytes, stream, J.D, J.P);
+        if (J.timing) J.evTrace.record(stream);
+#else
+        throw std::runtime_error("internal error: no ray kernel for this scene (the wide tree is missing)");
+#endif
+    }
+}
+
+/* One pass on the wavefront kernels: the pool's slots draw sample ids until none is left, one vertex of every live path per iteration */
+static void wavefrontPass(RenderJob &J) {
+    using clk = std::chrono::steady_clock;
+    phip_scene *sc = J.sc; SceneDev &sd = J.sd; const WavefrontPlan &wf = J.wf; hipStream_t stream = J.stream;
+    RenderConst &rc = J.rc; Counters &hc = J.hc;
+    const uint32_t capacity = wf.capacity;
+    HIP_TRY(hipMemsetAsync(sd.counters.p, 0, sizeof(Counters), stream));
+    /* static share: the first 3/4 of every slot's samples; the remainder is handed out dynamically */
+    {
+        const unsigned long long perSlot = rc.totalIds / capacity;
+        unsigned long long staticPerSlot = perSlot - perSlot / 4;
+        if (const char *e = expEnv("PHIP_STATIC_PERCENT")) staticPerSlot = perSlot * (unsigned long long) atoi(e) / 100;
+        rc.staticIds = staticPerSlot * capacity;
+        const unsigned long long dyn = rc.totalIds - rc.staticIds;
+        rc.shardIds = (dyn + DYN_SHARDS - 1) / DYN_SHARDS;
+        HIP_TRY(hipMemsetAsync(sd.blockShard.p, 0, wf.nBlocks * sizeof(uint32_t), stream));
+        HIP_TRY(hipMemsetAsync(sd.dynCounter.p, 0, DYN_SHARDS * DYN_STRIDE * sizeof(unsigned long long), stream));
+    }
+    HIP_TRY(hipMemsetAsync(sd.stat.p, 0, (size_t) ST_COUNT * wf.nWaves * sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(sd.shadowCount.p, 0, (size_t) wf.nBlocks * sizeof(uint32_t), stream));
+    HIP_TRY(hipMemsetAsync(sd.blockDead.p, 0, (size_t) wf.nBlocks * sizeof(uint32_t), stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) sd.state.p, (int) F_FRESH, (size_t) capacity, stream));
+    /* (no clear of L: the first vertex of every sample -- or its camera ray leaving the scene -- writes L[id]) */
+
+    HIP_TRY(hipStreamSynchronize(stream));
+    const auto tLoop0 = clk::now();
+    uint32_t iter = 0;
+    bool done = rc.totalIds == 0;
+    bool drainingSeen = false;                          /* a termination test has counted fewer live slots than the pool holds: blocks may have retired */
+    while (!done) {
+        const bool check = ((iter + 1) & 7) == 0 || rc.totalIds <= (unsigned long long) capacity * 4;
+        rc.countAlive = check ? 1 : 0;
+        rc.draining = drainingSeen ? 1u : 0u;
+        if (J.timing) J.evShade.record(stream);
+        if (J.direct) phipLaunchShadeDirect(wf.feat, sc->materialMask, wf.grid, stream, J.D, J.P, rc, sd.L.p);
+        else if (wf.shadeTrace) phipLaunchShadeTrace(wf.feat, rc.strictNormals != 0, sc->materialMask, wf.grid, wf.shadeTraceLds, stream, J.D, J.P, rc, sd.L.p);
+        else phipLaunchShade(wf.feat, rc.strictNormals != 0, sc->materialMask, wf.grid, stream, J.D, J.P, rc, sd.L.p);
+        if (J.timing) J.evShade.record(stream);
+        if (!wf.shadeTrace) launchRayKernels(J);        /* (k_shade_trace traced both rays of the iteration itself: k_shade_trace.h) */
+        ++iter;
+        if (check) {
+            /* termination test: only the live-slot row (and, for a progress callback, the finished-sample row) is summed inside the loop */
+            HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_ALIVE], 0, sizeof(unsigned long long), stream));
+            hipLaunchKernelGGL(k_reduce_stats, dim3(1, REDUCE_SPLIT), dim3(256), 0, stream, J.P, sd.counters.p, (int) ST_ALIVE);
+            HIP_TRY(hipMemcpyAsync(&hc.total[ST_ALIVE], &sd.counters.p->total[ST_ALIVE], sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+            if (J.p->progress) {
+                HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_SAMPLES], 0, sizeof(unsigned long long), stream));
+                hipLaunchKernelGGL(k_reduce_stats, dim3(1, REDUCE_SPLIT), dim3(256), 0, stream, J.P, sd.counters.p, (int) ST_SAMPLES);
+                HIP_TRY(hipMemcpyAsync(&hc.total[ST_SAMPLES], &sd.counters.p->total[ST_SAMPLES], sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+            }
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (hc.total[ST_ALIVE] == 0) done = true;
+            if (hc.total[ST_ALIVE] < capacity) drainingSeen = true;
+            J.progress(J.samplesDone + hc.total[ST_SAMPLES]);
+            if (cancelRequested(sc)) { J.cancelled = true; done = true; }
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (getenv("PHIP_DEBUG_TIMING")) fprintf(stderr, "[phip] setup %.2f ms, loop %.2f ms (%u iterations)\n", std::chrono::duration<double, std::milli>(tLoop0 - J.t0).count(), std::chrono::duration<double, std::milli>(clk::now() - tLoop0).count(), iter);
+    J.st.iterations += iter;
+}
+
+/* round 4: one pass over L with the footprint sums in registers, then an ordered merge of the 16 x 16 patch images (k_film.h) */
+template <int R> static void launchFilmSplat(RenderJob &J, dim3 fg, int acc) {
+    SceneDev &sd = J.sd; hipStream_t stream = J.stream;
+    const int cells = (16 + 2 * R) * (16 + 2 * R) * 5;
+    const unsigned nPatches = (unsigned) sd.nLocalTiles << (2 * (J.tileShift - 4));
+    if (sd.patchImg.n < (size_t) nPatches * cells) sd.patchImg.alloc((size_t) nPatches * cells);
+    const float4 *Lc = (const float4 *) sd.L.p;
+    if (J.qmc) hipLaunchKernelGGL((k_film_splat<R, true>), dim3(nPatches), dim3(256), 0, stream, J.D, J.rc, Lc, sd.patchImg.p, sd.invalid.p);
+    else hipLaunchKernelGGL((k_film_splat<R, false>), dim3(nPatches), dim3(256), 0, stream, J.D, J.rc, Lc, sd.patchImg.p, sd.invalid.p);
+    hipLaunchKernelGGL(k_film_merge<R>, fg, dim3(BLOCK), 0, stream, J.D, J.rc, (const float *) sd.patchImg.p, (const int32_t *) sd.tileSlot.p, J.tilesX, J.dOut, acc);
+}
+
+/* The pass's samples (sd.L) filtered into dOut: onto what is there (acc) or over it */
+static void filmPass(RenderJob &J, int acc) {
+    SceneDev &sd = J.sd; hipStream_t stream = J.stream;
+    const DevScene &D = J.D; const RenderConst &rc = J.rc; float *dOut = J.dOut;
+    const int W = J.W, H = J.H, bs = J.bs, tileShift = J.tileShift, tilesX = J.tilesX;
+    const dim3 block(BLOCK);
+    if (J.timing) J.evFilm.record(stream);
+    const dim3 fg((W + 15) / 16, (H + 15) / 16);
+    const int reach = (int) std::floor(D.film.radius + 0.5f);
+    const char *fv = expEnv("PHIP_FILM_V1"); (void) fv;       /* experiment hook: the round-2 tiled kernel */
+    const bool splat = reach <= 2 && tileShift >= 4 && bs == (1 << tileShift) && sd.nLocalTiles > 0 && !expEnv("PHIP_FILM_GATHER");     /* PHIP_FILM_GATHER: the tiled gathers of rounds 2 / 3 (A/B) */
+    if (splat) {
+        if (reach <= 1) launchFilmSplat<1>(J, fg, acc);
+        else launchFilmSplat<2>(J, fg, acc);
+    } else if (J.qmc)
+        hipLaunchKernelGGL(k_film<true>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut,
+                           acc, sd.invalid.p);
+#if PHIP_EXPERIMENTS
+    else if (reach <= 2 && bs >= FILM_TILE + 2 * std::max(reach, 1) && !expEnv("PHIP_FILM_GENERIC") && !(fv && atoi(fv))) {
+        if (reach <= 1)
+            hipLaunchKernelGGL(k_film_tiled2<1>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut, acc, sd.invalid.p);
+        else
+            hipLaunchKernelGGL(k_film_tiled2<2>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut, acc, sd.invalid.p);
+    }
+#endif
+    else if (reach <= FILM_MAX_REACH && !expEnv("PHIP_FILM_GENERIC"))
+        if (reach <= 2)
+            hipLaunchKernelGGL(k_film_tiled<2>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut,
+                               acc, sd.invalid.p, reach);
+        else
+            hipLaunchKernelGGL(k_film_tiled<FILM_MAX_REACH>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut,
+                               acc, sd.invalid.p, reach);
+    else
+        hipLaunchKernelGGL(k_film<false>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut,
+                           acc, sd.invalid.p);
+    if (J.timing) J.evFilm.record(stream);
+}
+
+/* After the film pass: the sample buffer's share of the pass, the pass's counters into the job's, progress */
+static void passResults(RenderJob &J) {
+    SceneDev &sd = J.sd; hipStream_t stream = J.stream; const RenderConst &rc = J.rc; Counters &hc = J.hc;
+    if (J.keepSamples && rc.totalIds) {
+        const size_t n = (size_t) J.W * J.H * rc.sppPass;
+        hipLaunchKernelGGL(k_export_samples, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream, J.D, rc, (const float4 *) sd.L.p,
+                           (const int32_t *) sd.tileSlot.p, J.tilesX, sd.sampleOut.p, (uint32_t) J.p->spp, (uint32_t) J.p->sample_offset);
+    }
+    HIP_TRY(hipMemsetAsync(sd.counters.p, 0, sizeof(Counters), stream));
+    hipLaunchKernelGGL(k_reduce_stats, dim3(ST_COUNT, REDUCE_SPLIT), dim3(256), 0, stream, J.P, sd.counters.p, 0);
+    HIP_TRY(hipMemcpyAsync(&hc, sd.counters.p, sizeof(Counters), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    phip_stats pass; memset(&pass, 0, sizeof(pass));
+    pass.samples = hc.total[ST_SAMPLES]; pass.closest_rays = hc.total[ST_CLOSEST_RAYS]; pass.shadow_rays = hc.total[ST_SHADOW_RAYS];
+    pass.path_vertices = hc.total[ST_VERTICES]; pass.closest_node_visits = hc.total[ST_NODE]; pass.closest_triangle_tests = hc.total[ST_TRI];
+    pass.shadow_node_visits = hc.total[ST_SH_NODE]; pass.shadow_triangle_tests = hc.total[ST_SH_TRI];
+    addWork(J.st, pass);
+    J.samplesDone += pass.samples;
+    J.progress(J.samplesDone);
+}
+
+/* One device's share of a render call: the blocks whose index in the reference's spiral order is congruent to shardIndex
+   modulo shardCount, into dOut (device memory of sd.device).  The caller holds the scene's render lock and has validated p. */
+static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params *p, int shardIndex, int shardCount, float *dOut, phip_stats *stats) {
+    HIP_TRY(hipSetDevice(sd.device));
+    RenderJob J(sc, sd, p, dOut);
+    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, sd.device) == hipSuccess) J.nCU = prop.multiProcessorCount; }
+    shardTiles(J, shardIndex, shardCount);
+    J.stream = (p->n_devices <= 1) ? (hipStream_t) p->stream : nullptr;    /* a caller's stream belongs to one device */
+    if (!J.stream) { if (!sd.stream) HIP_TRY(hipStreamCreate(&sd.stream)); J.stream = sd.stream; }
+    planPasses(J);
+    if (p->sampler == PHIP_SAMPLER_SOBOL) uploadSobolTables(J);
+    if (J.rinv) uploadRinvTables(J);
+    planFused(J);
+    HIP_TRY(hipMemsetAsync(sd.invalid.p, 0, sizeof(unsigned long long), J.stream));
+    if (!J.F.on) setupWavefront(J, J.idsPerSpp * J.sppPerPass);
+    callConstants(J);
+
+    const bool accumulate = (p->flags & PHIP_FLAG_ACCUMULATE) != 0;
+    for (uint32_t sppDone = 0; sppDone < (uint32_t) p->spp && !J.cancelled; sppDone += J.sppPerPass) {
+        passConstants(J, sppDone);
+        if (J.F.on) {
+            const FusedPass r = fusedPass(J, sppDone);
+            if (r == FusedPass::Cancelled) J.cancelled = true;
+            if (r == FusedPass::GaveUp) {
+                /* this pass again, and the rest of the job, on k_shade + the ray kernel, which have no such protocol: the same passes, a pool sized for this one */
+                J.F.on = false; sd.fused = false;
+                setupWavefront(J, J.rc.totalIds);
+            }
+        }
+        if (!J.F.on) wavefrontPass(J);
+        if (J.cancelled) break;                                 /* L is incomplete: no film pass */
+        filmPass(J, (sppDone > 0 || accumulate) ? 1 : 0);
+        passResults(J);
+    }
+
+    phip_stats &st = J.st;
+    if ((sd.nLocalTiles == 0 || J.cancelled) && !accumulate) { HIP_TRY(hipMemsetAsync(dOut, 0, (size_t) J.W * J.H * 5 * sizeof(float), J.stream)); HIP_TRY(hipStreamSynchronize(J.stream)); }
     unsigned long long inv = 0;
     HIP_TRY(hipMemcpy(&inv, sd.invalid.p, sizeof(inv), hipMemcpyDeviceToHost));
     st.invalid_samples = inv;
-    st.trace_kernel_ms = evTrace.sumPairs(); st.shadow_kernel_ms = evShadow.sumPairs();
-    st.shade_kernel_ms = evShade.sumPairs(); st.film_kernel_ms = evFilm.sumPairs(); st.fused_kernel_ms = evFused.sumPairs();
-    st.fused = fused ? 1u : 0u; st.n_devices = 1;
-    st.vertex_traced = shadeTrace ? 1u : 0u;
-    st.render_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    algorithmicBytes(merged, st, (double) W * H, sc->wide);
+    st.trace_kernel_ms = J.evTrace.sumPairs(); st.shadow_kernel_ms = J.evShadow.sumPairs();
+    st.shade_kernel_ms = J.evShade.sumPairs(); st.film_kernel_ms = J.evFilm.sumPairs(); st.fused_kernel_ms = J.evFused.sumPairs();
+    st.fused = J.F.on ? 1u : 0u; st.n_devices = 1;
+    st.vertex_traced = J.wf.shadeTrace ? 1u : 0u;
+    st.render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - J.t0).count();
+    algorithmicBytes(J.wf.merged, st, (double) J.W * J.H, sc->wide);
     if (stats) *stats = st;
-    return cancelled ? PHIP_ERR_CANCELLED : PHIP_OK;
+    return J.cancelled ? PHIP_ERR_CANCELLED : PHIP_OK;
 }
 
 /* ---- RCCL, bound at the first multi-GPU render (librccl is not a load-time dependency of single-GPU users; a process that
@@ -1822,9 +1909,7 @@ static int renderMultiDevice(phip_scene *sc, const phip_render_params *p, float 
         phip_stats t; memset(&t, 0, sizeof(t));
         for (int i = 0; i < n; ++i) {
             const phip_stats &a = st[i];
-            t.samples += a.samples; t.closest_rays += a.closest_rays; t.shadow_rays += a.shadow_rays; t.path_vertices += a.path_vertices;
-            t.closest_node_visits += a.closest_node_visits; t.closest_triangle_tests += a.closest_triangle_tests;
-            t.shadow_node_visits += a.shadow_node_visits; t.shadow_triangle_tests += a.shadow_triangle_tests;
+            addWork(t, a);
             t.invalid_samples += a.invalid_samples; t.iterations = std::max(t.iterations, a.iterations);
             t.trace_kernel_ms = std::max(t.trace_kernel_ms, a.trace_kernel_ms); t.shadow_kernel_ms = std::max(t.shadow_kernel_ms, a.shadow_kernel_ms);
             t.shade_kernel_ms = std::max(t.shade_kernel_ms, a.shade_kernel_ms); t.film_kernel_ms = std::max(t.film_kernel_ms, a.film_kernel_ms);
