@@ -33,8 +33,8 @@
  *                 k_film (wider filters, small blocks): ImageBlock::put, include/mitsuba/render/imageblock.h:124-204;
  *                 k_reduce_stats, k_export_samples                                                                [this unit]
  *
- * This file: error handling, scene validation and upload (BVH build via bvh.h, camera set-up), replication of the scene to
- * further GPUs, the render loop, the multi-device orchestration (one host thread + stream per GPU, ncclReduce of the
+ * This file: error handling, scene construction as stages over one SceneBuild (validation, host arrays, BVH build via bvh.h, the
+ * choice of the device paths, one upload; camera set-up), replication of the scene to further GPUs through SceneDev's one list of buffers, the render loop, the multi-device orchestration (one host thread + stream per GPU, ncclReduce of the
  * films over RCCL/xGMI) and the extern "C" entry points.  Not MFMA work: irregular traversal and gathers.
  * The product never includes, links or calls anything under oracle/.
  */
@@ -171,7 +171,9 @@ void spiralBlocks(int sizeX, int sizeY, int bs, std::vector<std::pair<int, int>>
 
 } // namespace
 /* Everything that lives on ONE GPU: the immutable scene arrays and the render-time buffers of the jobs that run there.
-   devs[0] of a phip_scene is the device of phip_scene_create; further entries are replicas made by device-to-device copies. */
+   devs[0] of a phip_scene is the device of phip_scene_create; further entries are replicas made by device-to-device copies.
+   A new scene buffer is declared below, added to forEachSceneBuffer (the one list replicateScene clones through) and given its line in bind()
+   (the only code that writes a buffer pointer into the DevScene); SceneBuild::uploadScene fills it. */
 struct SceneDev {
     int device = 0;
     /* ---- scene (immutable after build / replication) ---- */
@@ -205,9 +207,11 @@ struct SceneDev {
     /* phip_render's device-to-host copy of the film into PAGEABLE memory: two pinned staging chunks (filmToHost) */
     float *stage[2] = { nullptr, nullptr }; hipEvent_t stageDone[2] = { nullptr, nullptr };
 
-    template <typename F> void forEachSceneBuffer(F f) {
-        f(nodes); f(wnodes); f(tris); f(wtris); f(triShade); f(flatLeaves); f(materials); f(emitterTab); f(texTexels); f(texDesc);
-        f(envTexels); f(envLevels); f(envCdfRows); f(envCdfCols); f(envRowWeights);
+    /* THE list of the immutable scene buffers, as pointers to members */
+    template <typename F> static void forEachSceneBuffer(F f) {
+        f(&SceneDev::nodes); f(&SceneDev::wnodes); f(&SceneDev::tris); f(&SceneDev::wtris); f(&SceneDev::triShade); f(&SceneDev::flatLeaves);
+        f(&SceneDev::materials); f(&SceneDev::emitterTab); f(&SceneDev::texTexels); f(&SceneDev::texDesc);
+        f(&SceneDev::envTexels); f(&SceneDev::envLevels); f(&SceneDev::envCdfRows); f(&SceneDev::envCdfCols); f(&SceneDev::envRowWeights);
     }
     /* the pointer members of the DevScene (everything else in it is plain data, equal on every device) */
     void bind() {
@@ -216,6 +220,8 @@ struct SceneDev {
         dev.env.texels = envTexels.p; dev.env.levels = envLevels.p; dev.env.cdfRows = envCdfRows.p; dev.env.cdfCols = envCdfCols.p;
         dev.env.rowWeights = envRowWeights.p;
     }
+    /* the fixed per-device work counters of the render kernels */
+    void allocCounters() { counters.alloc(1); invalid.alloc(1); dynCounter.alloc(DYN_SHARDS * DYN_STRIDE); megaNext.alloc(1); }
     ~SceneDev() {
         (void) hipSetDevice(device);
         if (stream) (void) hipStreamDestroy(stream);
@@ -247,11 +253,15 @@ struct phip_scene {
 static std::vector<DevMaterial> convertMaterials(const phip_material *materials, uint32_t nMaterials, const std::vector<float> *textureMax = nullptr) {
     if (nMaterials && !materials) throw std::runtime_error("materials is NULL");
     std::vector<DevMaterial> mats(nMaterials);
+    /* the maximum of bitmap texture `id` (1-based, not 0) */
+    auto textureMaxOf = [&](uint32_t id) -> float {
+        if (!textureMax || id > textureMax->size()) throw std::runtime_error("material texture id out of range");
+        return (*textureMax)[id - 1];
+    };
     /* a `bitmap` texture on specularReflectance (dielectric.cpp:159-160, roughconductor.cpp:173-174,236: ensureEnergyConservation) */
     auto specularTexture = [&](const phip_material &m, DevMaterial &o) {
         if (m.reflectance_texture == 0) return;
-        if (!textureMax || m.reflectance_texture > textureMax->size()) throw std::runtime_error("material texture id out of range");
-        if ((*textureMax)[m.reflectance_texture - 1] > 1.0f) throw std::runtime_error("specularReflectance texture > 1 (ensureEnergyConservation)");
+        if (textureMaxOf(m.reflectance_texture) > 1.0f) throw std::runtime_error("specularReflectance texture > 1 (ensureEnergyConservation)");
         o.reflTexture = m.reflectance_texture;
     };
     for (uint32_t i = 0; i < nMaterials; ++i) {
@@ -265,8 +275,7 @@ static std::vector<DevMaterial> convertMaterials(const phip_material *materials,
             case PHIP_BSDF_DIFFUSE: {
                 float mx = std::max(m.reflectance[0], std::max(m.reflectance[1], m.reflectance[2]));
                 if (m.reflectance_texture != 0) {            /* m_reflectance->getMaximum().max() of the bitmap */
-                    if (!textureMax || m.reflectance_texture > textureMax->size()) throw std::runtime_error("material texture id out of range");
-                    mx = (*textureMax)[m.reflectance_texture - 1];
+                    mx = textureMaxOf(m.reflectance_texture);
                     o.reflTexture = m.reflectance_texture;
                 }
                 if (mx > 1.0f) throw std::runtime_error("diffuse reflectance > 1 (ensureEnergyConservation, diffuse.cpp:95)");
@@ -277,8 +286,7 @@ static std::vector<DevMaterial> convertMaterials(const phip_material *materials,
                 o.flags |= MF_TRANS_OR_BACK;
                 specularTexture(m, o);
                 if (m.transmittance_texture != 0) {          /* dielectric.cpp:161-162,207-208: ensureEnergyConservation(specularTransmittance) */
-                    if (!textureMax || m.transmittance_texture > textureMax->size()) throw std::runtime_error("material texture id out of range");
-                    if ((*textureMax)[m.transmittance_texture - 1] > 1.0f) throw std::runtime_error("specularTransmittance texture > 1 (ensureEnergyConservation)");
+                    if (textureMaxOf(m.transmittance_texture) > 1.0f) throw std::runtime_error("specularTransmittance texture > 1 (ensureEnergyConservation)");
                     o.transTexture = m.transmittance_texture;
                 }
                 break;
@@ -291,7 +299,7 @@ static std::vector<DevMaterial> convertMaterials(const phip_material *materials,
                 o.alphaV = std::max(V3(m.alpha_v).average(), 1e-4f);
                 /* a `bitmap` texture as the child "alpha" / "alphaU" / "alphaV" (roughconductor.cpp:424-431): evaluated per vertex */
                 for (uint32_t t : { m.alpha_u_texture, m.alpha_v_texture })
-                    if (t != 0 && (!textureMax || t > textureMax->size())) throw std::runtime_error("material texture id out of range");
+                    if (t != 0) (void) textureMaxOf(t);
                 o.alphaUTexture = m.alpha_u_texture; o.alphaVTexture = m.alpha_v_texture;
             } break;
             case PHIP_BSDF_TWOSIDED: {
@@ -308,213 +316,250 @@ static std::vector<DevMaterial> convertMaterials(const phip_material *materials,
     return mats;
 }
 
-static void buildScene(phip_scene *sc, const phip_scene_desc &d) {
-    SceneDev &sd = *sc->devs[0];
-    if (d.abi_version != PHIP_ABI_VERSION) throw std::runtime_error("phip_scene_desc.abi_version mismatch");
-    if (d.n_vertices && !d.positions) throw std::runtime_error("positions is NULL");
-    if (d.n_triangles && !d.indices) throw std::runtime_error("indices is NULL");
-    if (d.film.crop_width <= 0 || d.film.crop_height <= 0 || d.film.width <= 0 || d.film.height <= 0)
-        throw std::runtime_error("invalid film size");
-    if (d.film.crop_offset_x < 0 || d.film.crop_offset_y < 0 || d.film.crop_offset_x + d.film.crop_width > d.film.width ||
-        d.film.crop_offset_y + d.film.crop_height > d.film.height)
-        throw std::runtime_error("invalid crop window");          /* film.cpp:44-48 */
-    if (d.film.crop_width >= 65536 || d.film.crop_height >= 65536)
-        throw std::runtime_error("crop window of 65536 pixels or more per side (block origins are packed into 16 bits)");
-    if (!(d.film.filter_radius > 0)) throw std::runtime_error("filter radius must be > 0");
-    for (uint32_t i = 0; i < 3 * d.n_triangles; ++i)
-        if (d.indices[i] >= d.n_vertices) throw std::runtime_error("triangle index out of range");
-
-    /* shapes */
-    std::vector<DevShape> shapes(d.n_shapes);
-    std::vector<uint32_t> triShape(d.n_triangles);
-    std::vector<float> areaCdf;
-    uint32_t expect = 0;
-    for (uint32_t i = 0; i < d.n_shapes; ++i) {
-        const phip_shape &s = d.shapes[i];
-        if (s.first_triangle != expect) throw std::runtime_error("shape triangle ranges must tile the index array in order");
-        if (s.material >= d.n_materials) throw std::runtime_error("shape material id out of range");
-        if (s.emitter >= (int32_t) d.n_emitters) throw std::runtime_error("shape emitter id out of range");
-        if (s.emitter >= 0 && d.emitters[s.emitter].type != PHIP_EMITTER_AREA) throw std::runtime_error("a shape can only carry an area emitter");
-        if (s.has_normals && !d.normals) throw std::runtime_error("shape has_normals but normals is NULL");
-        expect += s.n_triangles;
-        DevShape &o = shapes[i];
-        if (s.has_texcoords && !d.texcoords) throw std::runtime_error("shape has_texcoords but texcoords is NULL");
-        o.material = s.material; o.emitter = s.emitter; o.hasNormals = s.has_normals ? 1 : 0;
-        o.firstTri = s.first_triangle; o.nTris = s.n_triangles; o.cdfOffset = 0; o.invSurfaceArea = 0; o.pad = s.has_texcoords ? 1 : 0;    /* pad: the mesh has texture coordinates */
-        for (uint32_t j = 0; j < s.n_triangles; ++j) triShape[s.first_triangle + j] = i;
-        if (s.emitter >= 0) {
-            /* TriMesh::prepareSamplingTable, trimesh.cpp:388-404 + DiscreteDistribution::normalize */
-            if (s.n_triangles == 0) throw std::runtime_error("area emitter on an empty mesh");
-            o.cdfOffset = (uint32_t) areaCdf.size();
-            std::vector<float> cdf(1, 0.0f);
-            for (uint32_t j = 0; j < s.n_triangles; ++j) {
-                const uint32_t *ix = d.indices + 3 * (size_t) (s.first_triangle + j);
-                const float *p0 = d.positions + 3 * (size_t) ix[0], *p1 = d.positions + 3 * (size_t) ix[1], *p2 = d.positions + 3 * (size_t) ix[2];
-                V3 a(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]), b(p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]);
-                cdf.push_back(cdf.back() + 0.5f * cross(a, b).length());
-            }
-            const float sum = cdf.back();
-            if (!(sum > 0)) throw std::runtime_error("area emitter with zero surface area");
-            const float norm = 1.0f / sum;
-            for (size_t j = 1; j < cdf.size(); ++j) cdf[j] *= norm;
-            cdf.back() = 1.0f;
-            o.invSurfaceArea = 1.0f / sum;
-            areaCdf.insert(areaCdf.end(), cdf.begin(), cdf.end());
+/* level sizes of a complete MIP pyramid down to 1x1 (mipmap.h:182-192); n_levels is 1 or that pyramid's own count.  `what` = "texture" / "envmap" */
+static void pyramidLevels(DevMipLevels &lv, int sx, int sy, uint32_t nLevels, int maxLevels, const std::string &what) {
+    int n = 1;
+    lv.lw[0] = sx; lv.lh[0] = sy;
+    if (nLevels > 1) {
+        while (sx > 1 || sy > 1) {
+            sx = std::max(1, (sx + 1) / 2); sy = std::max(1, (sy + 1) / 2);
+            if (n >= maxLevels) throw std::runtime_error(what + ": too many MIP levels");
+            lv.lw[n] = sx; lv.lh[n] = sy; ++n;
         }
+        if ((uint32_t) n != nLevels) throw std::runtime_error(what + ": n_levels must be 1 or the complete pyramid down to 1x1");
     }
-    if (expect != d.n_triangles) throw std::runtime_error("shape triangle ranges do not cover the index array");
+    lv.nLevels = n;
+}
+/* EWA weight table, mipmap.h:296-301 */
+static void ewaWeightLut(float *lut) { for (int k = 0; k < 64; ++k) { const float r2 = (float) k / 63.0f; lut[k] = pm_expf(-2.0f * r2) - pm_expf(-2.0f); } }
 
-    /* bitmap textures: every pyramid (as delivered) in one float4 texel array + one descriptor each */
-    std::vector<float4> texTexels; std::vector<DevMipLevels> texDesc(d.n_textures); std::vector<float> texMax(d.n_textures, 0.0f);
-    if (d.n_textures && !d.textures) throw std::runtime_error("textures is NULL");
-    for (uint32_t i = 0; i < d.n_textures; ++i) {
-        const phip_texture &t = d.textures[i];
-        if (t.width == 0 || t.height == 0 || !t.levels[0]) throw std::runtime_error("texture without level 0");
-        if (t.wrap_u > PHIP_WRAP_ONE || t.wrap_v > PHIP_WRAP_ONE || t.filter_type > PHIP_FILTER_EWA) throw std::runtime_error("bad texture wrap mode / filter type");
-        DevMipLevels &lv = texDesc[i]; memset(&lv, 0, sizeof(lv));
-        int sx = (int) t.width, sy = (int) t.height, n = 1;
-        lv.lw[0] = sx; lv.lh[0] = sy;
-        if (t.n_levels > 1) {
-            while (sx > 1 || sy > 1) {
-                sx = std::max(1, (sx + 1) / 2); sy = std::max(1, (sy + 1) / 2);
-                if (n >= PHIP_MIP_MAX_LEVELS) throw std::runtime_error("texture: too many MIP levels");
-                lv.lw[n] = sx; lv.lh[n] = sy; ++n;
+/* m_alphaU != m_alphaV as OBJECTS (one texture for both is isotropic, roughconductor.cpp:228-229); twosided.cpp:96-100 inherits the flag */
+static bool anisotropic(const phip_scene_desc &d, uint32_t m, int depth = 0) {
+    if (m >= d.n_materials || depth > 2) return false;
+    const phip_material &M = d.materials[m];
+    if (M.type == PHIP_BSDF_ROUGHCONDUCTOR)
+        return (M.alpha_u_texture | M.alpha_v_texture) ? M.alpha_u_texture != M.alpha_v_texture : std::max(M.alpha_u, 1e-4f) != std::max(M.alpha_v, 1e-4f);
+    if (M.type == PHIP_BSDF_TWOSIDED) return anisotropic(d, M.nested[0], depth + 1) || anisotropic(d, M.nested[1], depth + 1);
+    return false;
+}
+
+/* One phip_scene_create: what the stages of buildScene hand to each other.  Every stage up to chooseDevicePaths works on host arrays and calls no HIP
+   function; uploadScene is the only one that allocates or copies scene buffers. */
+struct SceneBuild {
+    phip_scene *sc; SceneDev &sd; const phip_scene_desc &d; DevScene &D;
+    std::vector<DevShape> shapes; std::vector<uint32_t> triShape; std::vector<float> areaCdf;
+    std::vector<float4> texTexels; std::vector<DevMipLevels> texDesc; std::vector<float> texMax;
+    std::vector<DevMaterial> mats;
+    std::vector<DevEmitter> ems; std::vector<float> ecdf; float emNorm = 0; int32_t envEmitter = -1; bool envIsMap = false;
+    std::vector<float4> ts; uint32_t stride = TRISHADE_FLOAT4S;     /* shading records */
+    std::vector<float> tab;                                         /* packed emitter table */
+    std::vector<float4> envTexels; DevMipLevels envLevels; std::vector<float> envCdfRows, envCdfCols, envRowWeights;
+    std::vector<float4> flat;                                       /* flat / packed leaf table (flatMode != 0) */
+    uint32_t walkStack = 0; bool treeInLds = false, fitsLdsBase = false;     /* ldsPlan -> flatLeafTable, chooseDevicePaths */
+
+    SceneBuild(phip_scene *sc, const phip_scene_desc &d) : sc(sc), sd(*sc->devs[0]), d(d), D(sd.dev) { memset(&D, 0, sizeof(D)); }
+
+    /* ABI version, NULL arrays, film / crop / filter, index range */
+    void validateDesc() {
+        if (d.abi_version != PHIP_ABI_VERSION) throw std::runtime_error("phip_scene_desc.abi_version mismatch");
+        if (d.n_vertices && !d.positions) throw std::runtime_error("positions is NULL");
+        if (d.n_triangles && !d.indices) throw std::runtime_error("indices is NULL");
+        if (d.film.crop_width <= 0 || d.film.crop_height <= 0 || d.film.width <= 0 || d.film.height <= 0)
+            throw std::runtime_error("invalid film size");
+        if (d.film.crop_offset_x < 0 || d.film.crop_offset_y < 0 || d.film.crop_offset_x + d.film.crop_width > d.film.width ||
+            d.film.crop_offset_y + d.film.crop_height > d.film.height)
+            throw std::runtime_error("invalid crop window");          /* film.cpp:44-48 */
+        if (d.film.crop_width >= 65536 || d.film.crop_height >= 65536)
+            throw std::runtime_error("crop window of 65536 pixels or more per side (block origins are packed into 16 bits)");
+        if (!(d.film.filter_radius > 0)) throw std::runtime_error("filter radius must be > 0");
+        for (uint32_t i = 0; i < 3 * d.n_triangles; ++i)
+            if (d.indices[i] >= d.n_vertices) throw std::runtime_error("triangle index out of range");
+    }
+
+    /* DevShapes, the triangle -> shape map, the area CDFs of the emitter meshes */
+    void flattenShapes() {
+        shapes.resize(d.n_shapes); triShape.resize(d.n_triangles);
+        uint32_t expect = 0;
+        for (uint32_t i = 0; i < d.n_shapes; ++i) {
+            const phip_shape &s = d.shapes[i];
+            if (s.first_triangle != expect) throw std::runtime_error("shape triangle ranges must tile the index array in order");
+            if (s.material >= d.n_materials) throw std::runtime_error("shape material id out of range");
+            if (s.emitter >= (int32_t) d.n_emitters) throw std::runtime_error("shape emitter id out of range");
+            if (s.emitter >= 0 && d.emitters[s.emitter].type != PHIP_EMITTER_AREA) throw std::runtime_error("a shape can only carry an area emitter");
+            if (s.has_normals && !d.normals) throw std::runtime_error("shape has_normals but normals is NULL");
+            expect += s.n_triangles;
+            DevShape &o = shapes[i];
+            if (s.has_texcoords && !d.texcoords) throw std::runtime_error("shape has_texcoords but texcoords is NULL");
+            o.material = s.material; o.emitter = s.emitter; o.hasNormals = s.has_normals ? 1 : 0;
+            o.firstTri = s.first_triangle; o.nTris = s.n_triangles; o.cdfOffset = 0; o.invSurfaceArea = 0; o.pad = s.has_texcoords ? 1 : 0;    /* pad: the mesh has texture coordinates */
+            for (uint32_t j = 0; j < s.n_triangles; ++j) triShape[s.first_triangle + j] = i;
+            if (s.emitter >= 0) {
+                /* TriMesh::prepareSamplingTable, trimesh.cpp:388-404 + DiscreteDistribution::normalize */
+                if (s.n_triangles == 0) throw std::runtime_error("area emitter on an empty mesh");
+                o.cdfOffset = (uint32_t) areaCdf.size();
+                std::vector<float> cdf(1, 0.0f);
+                for (uint32_t j = 0; j < s.n_triangles; ++j) {
+                    const uint32_t *ix = d.indices + 3 * (size_t) (s.first_triangle + j);
+                    const float *p0 = d.positions + 3 * (size_t) ix[0], *p1 = d.positions + 3 * (size_t) ix[1], *p2 = d.positions + 3 * (size_t) ix[2];
+                    V3 a(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]), b(p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]);
+                    cdf.push_back(cdf.back() + 0.5f * cross(a, b).length());
+                }
+                const float sum = cdf.back();
+                if (!(sum > 0)) throw std::runtime_error("area emitter with zero surface area");
+                const float norm = 1.0f / sum;
+                for (size_t j = 1; j < cdf.size(); ++j) cdf[j] *= norm;
+                cdf.back() = 1.0f;
+                o.invSurfaceArea = 1.0f / sum;
+                areaCdf.insert(areaCdf.end(), cdf.begin(), cdf.end());
             }
-            if ((uint32_t) n != t.n_levels) throw std::runtime_error("texture: n_levels must be 1 or the complete pyramid down to 1x1");
         }
-        lv.nLevels = n;
-        for (int l = 0; l < n; ++l) {
-            if (!t.levels[l]) throw std::runtime_error("texture: level pointer is NULL");
-            lv.offset[l] = (uint32_t) texTexels.size();
-            const size_t cnt = (size_t) lv.lw[l] * lv.lh[l];
-            for (size_t k = 0; k < cnt; ++k) {
-                const float *c = t.levels[l] + 3 * k;
-                texTexels.push_back(make_float4(c[0], c[1], c[2], 0.0f));
-                if (l == 0) texMax[i] = std::max(texMax[i], std::max(c[0], std::max(c[1], c[2])));
-            }
-        }
-        if (texTexels.size() >= (1ull << 32)) throw std::runtime_error("textures too large");
-        lv.bcu = t.wrap_u; lv.bcv = t.wrap_v; lv.filterType = t.filter_type; lv.maxAnisotropy = t.max_anisotropy;
-        lv.uvScale[0] = t.uv_scale[0]; lv.uvScale[1] = t.uv_scale[1]; lv.uvOffset[0] = t.uv_offset[0]; lv.uvOffset[1] = t.uv_offset[1];
-        for (int k = 0; k < 64; ++k) { const float r2 = (float) k / 63.0f; lv.weightLut[k] = pm_expf(-2.0f * r2) - pm_expf(-2.0f); }
+        if (expect != d.n_triangles) throw std::runtime_error("shape triangle ranges do not cover the index array");
     }
 
-    /* materials */
-    std::vector<DevMaterial> mats = convertMaterials(d.materials, d.n_materials, &texMax);
-    /* TriMesh::computeUVTangents, trimesh.cpp:683-693: an anisotropic BSDF (roughconductor.cpp:196-200,230-231: the clamped
-       alphaU != alphaV; twosided.cpp:96-100 inherits the flag) needs texture coordinates for its tangent frame -- an error there */
-    for (uint32_t i = 0; i < d.n_shapes; ++i) {
-        std::function<bool(uint32_t, int)> aniso = [&](uint32_t m, int depth) -> bool {
-            if (m >= d.n_materials || depth > 2) return false;
-            const phip_material &M = d.materials[m];
-            if (M.type == PHIP_BSDF_ROUGHCONDUCTOR)            /* m_alphaU != m_alphaV as OBJECTS: one texture for both is isotropic, roughconductor.cpp:228-229 */
-                return (M.alpha_u_texture | M.alpha_v_texture) ? M.alpha_u_texture != M.alpha_v_texture : std::max(M.alpha_u, 1e-4f) != std::max(M.alpha_v, 1e-4f);
-            if (M.type == PHIP_BSDF_TWOSIDED) return aniso(M.nested[0], depth + 1) || aniso(M.nested[1], depth + 1);
-            return false;
-        };
-        if (!d.shapes[i].has_texcoords && aniso(d.shapes[i].material, 0))
-            throw std::runtime_error("computeUVTangents(): texture coordinates are required to generate tangent vectors (anisotropic BSDF on a shape without them)");
-    }
-
-    /* emitters + selection pdf, scene.cpp:375-381 */
-    std::vector<DevEmitter> ems(d.n_emitters);
-    int32_t envEmitter = -1; bool envIsMap = false;
-    std::vector<float> ecdf(1, 0.0f);
-    for (uint32_t i = 0; i < d.n_emitters; ++i) {
-        const phip_emitter &e = d.emitters[i];
-        if (e.type == PHIP_EMITTER_CONSTANT || e.type == PHIP_EMITTER_ENVMAP) {
-            if (envEmitter >= 0) throw std::runtime_error("The scene may only contain one environment emitter");   /* scene.cpp:510-513 */
-            envEmitter = (int32_t) i;
-            envIsMap = e.type == PHIP_EMITTER_ENVMAP;
-        } else if (e.type != PHIP_EMITTER_AREA) throw std::runtime_error("unknown emitter type");
-        else if (e.shape >= d.n_shapes || d.shapes[e.shape].emitter != (int32_t) i) throw std::runtime_error("emitter/shape back reference mismatch");
-        memset(&ems[i], 0, sizeof(DevEmitter));
-        for (int k = 0; k < 3; ++k) ems[i].radiance[k] = e.radiance[k];
-        ems[i].samplingWeight = e.sampling_weight; ems[i].shape = e.type == PHIP_EMITTER_AREA ? e.shape : 0xFFFFFFFFu;
-        ecdf.push_back(ecdf.back() + e.sampling_weight);
-    }
-    float emNorm = 0;
-    if (d.n_emitters) {
-        const float sum = ecdf.back();
-        if (sum > 0) { emNorm = 1.0f / sum; for (size_t j = 1; j < ecdf.size(); ++j) ecdf[j] *= emNorm; ecdf.back() = 1.0f; }
-    }
-
-    /* acceleration structure */
-    {
-        const float camPos[3] = { d.camera.to_world[3], d.camera.to_world[7], d.camera.to_world[11] };
-        buildBVH(d.positions, d.indices, d.n_triangles, sc->bvh, camPos);
-    }
-    if (sc->bvh.tris.size() / 12 >= (1u << 28)) throw std::runtime_error("too many triangle records for the leaf reference encoding");
-    if (d.n_triangles > HIT_PRIM_MASK) throw std::runtime_error("too many triangles for the hit record (30-bit primitive index)");
-
-    /* upload */
-    HIP_TRY(hipSetDevice(sd.device));
-    /* shading records (dv_scene.h): the per-triangle constants come from the same __host__ __device__
-       functions the kernel would run, so precomputing them does not change a single bit */
-    bool anyTexcoords = false;
-    for (uint32_t i = 0; i < d.n_shapes; ++i) anyTexcoords |= d.shapes[i].has_texcoords != 0;
-    const uint32_t stride = anyTexcoords ? TRISHADE_FLOAT4S_UV : TRISHADE_FLOAT4S;
-    std::vector<float4> ts((size_t) stride * d.n_triangles, make_float4(0, 0, 0, 0));
-    for (uint32_t i = 0; i < d.n_triangles; ++i) {
-        const DevShape &sh = shapes[triShape[i]];
-        const DevMaterial &m = mats[sh.material];
-        const uint32_t *ix = d.indices + 3 * (size_t) i;
-        const V3 p0(d.positions[3 * ix[0]], d.positions[3 * ix[0] + 1], d.positions[3 * ix[0] + 2]);
-        const V3 p1(d.positions[3 * ix[1]], d.positions[3 * ix[1] + 1], d.positions[3 * ix[1] + 2]);
-        const V3 p2(d.positions[3 * ix[2]], d.positions[3 * ix[2] + 1], d.positions[3 * ix[2] + 2]);
-        const bool twosided = m.type == PHIP_BSDF_TWOSIDED, texcoords = sh.pad != 0;
-        const uint32_t front = twosided ? m.nested0 : sh.material, back = twosided ? m.nested1 : sh.material;
-        uint32_t flags = (sh.hasNormals ? TS_VERTEX_NORMALS : 0u) | (twosided ? TS_TWOSIDED : 0u) | (texcoords ? TS_TEXCOORDS : 0u)
-                       | ((m.flags & MF_SMOOTH) ? TS_MF_SMOOTH : 0u) | ((m.flags & MF_TRANS_OR_BACK) ? TS_TRANS_OR_BACK : 0u);
-        const V3 side1(p1 - p0), side2(p2 - p0);
-        V3 dpdu = side1, dpdv = side2;                      /* skdtree.h:378-379 */
-        float4 *r = ts.data() + (size_t) stride * i;
-        if (texcoords) {
-            /* TriMesh::computeUVTangents, trimesh.cpp:683-735 (zero tangents for degenerate triangles) */
-            const float *t0 = d.texcoords + 2 * (size_t) ix[0], *t1 = d.texcoords + 2 * (size_t) ix[1], *t2 = d.texcoords + 2 * (size_t) ix[2];
-            dpdu = V3(0.0f); dpdv = V3(0.0f);
-            const V2 dUV1(t1[0] - t0[0], t1[1] - t0[1]), dUV2(t2[0] - t0[0], t2[1] - t0[1]);
-            const V3 n = cross(side1, side2);
-            const float length = n.length();
-            if (length != 0) {
-                const float determinant = dUV1.x * dUV2.y - dUV1.y * dUV2.x;
-                if (determinant == 0) {
-                    coordinateSystem(n / length, dpdu, dpdv);
-                } else {
-                    const float invDet = 1.0f / determinant;
-                    dpdu = (side1 * dUV2.y - side2 * dUV1.y) * invDet;
-                    dpdv = (side1 * (-dUV2.x) + side2 * dUV1.x) * invDet;
+    /* bitmap textures: every pyramid (as delivered) in one float4 texel array + one descriptor each, the maximum of every level 0 */
+    void packTextures() {
+        texDesc.resize(d.n_textures); texMax.assign(d.n_textures, 0.0f);
+        if (d.n_textures && !d.textures) throw std::runtime_error("textures is NULL");
+        for (uint32_t i = 0; i < d.n_textures; ++i) {
+            const phip_texture &t = d.textures[i];
+            if (t.width == 0 || t.height == 0 || !t.levels[0]) throw std::runtime_error("texture without level 0");
+            if (t.wrap_u > PHIP_WRAP_ONE || t.wrap_v > PHIP_WRAP_ONE || t.filter_type > PHIP_FILTER_EWA) throw std::runtime_error("bad texture wrap mode / filter type");
+            DevMipLevels &lv = texDesc[i]; memset(&lv, 0, sizeof(lv));
+            pyramidLevels(lv, (int) t.width, (int) t.height, t.n_levels, PHIP_MIP_MAX_LEVELS, "texture");
+            for (int l = 0; l < lv.nLevels; ++l) {
+                if (!t.levels[l]) throw std::runtime_error("texture: level pointer is NULL");
+                lv.offset[l] = (uint32_t) texTexels.size();
+                const size_t cnt = (size_t) lv.lw[l] * lv.lh[l];
+                for (size_t k = 0; k < cnt; ++k) {
+                    const float *c = t.levels[l] + 3 * k;
+                    texTexels.push_back(make_float4(c[0], c[1], c[2], 0.0f));
+                    if (l == 0) texMax[i] = std::max(texMax[i], std::max(c[0], std::max(c[1], c[2])));
                 }
             }
-            r[6] = make_float4(t0[0], t0[1], t1[0], t1[1]);
-            r[7] = make_float4(t2[0], t2[1], dpdu.x, dpdu.y);
-            r[8] = make_float4(dpdu.z, dpdv.x, dpdv.y, dpdv.z);
+            if (texTexels.size() >= (1ull << 32)) throw std::runtime_error("textures too large");
+            lv.bcu = t.wrap_u; lv.bcv = t.wrap_v; lv.filterType = t.filter_type; lv.maxAnisotropy = t.max_anisotropy;
+            lv.uvScale[0] = t.uv_scale[0]; lv.uvScale[1] = t.uv_scale[1]; lv.uvOffset[0] = t.uv_offset[0]; lv.uvOffset[1] = t.uv_offset[1];
+            ewaWeightLut(lv.weightLut);
         }
-        V3 a, b, c;
-        if (sh.hasNormals) {
-            a = V3(d.normals[3 * ix[0]], d.normals[3 * ix[0] + 1], d.normals[3 * ix[0] + 2]);
-            b = V3(d.normals[3 * ix[1]], d.normals[3 * ix[1] + 1], d.normals[3 * ix[1] + 2]);
-            c = V3(d.normals[3 * ix[2]], d.normals[3 * ix[2] + 1], d.normals[3 * ix[2] + 2]);
-        } else {
-            Frame f; triShadingFrame(triFaceNormal(side1, side2), dpdu, f);
-            a = f.n; b = f.s; c = f.t;
-        }
-        r[0] = make_float4(p0.x, p0.y, p0.z, pm_from_bits(front));
-        r[1] = make_float4(p1.x, p1.y, p1.z, pm_from_bits(back));
-        r[2] = make_float4(p2.x, p2.y, p2.z, pm_from_bits((uint32_t) sh.emitter));
-        r[3] = make_float4(a.x, a.y, a.z, pm_from_bits(flags));
-        r[4] = make_float4(b.x, b.y, b.z, 0.0f);
-        r[5] = make_float4(c.x, c.y, c.z, 0.0f);
+        sc->hasTextures = d.n_textures > 0;
     }
+
+    /* DevMaterials, the leaf BSDF models present, the texture-coordinate requirement of anisotropic BSDFs */
+    void materials() {
+        mats = convertMaterials(d.materials, d.n_materials, &texMax);
+        /* TriMesh::computeUVTangents, trimesh.cpp:683-693: an anisotropic BSDF (roughconductor.cpp:196-200,230-231: the clamped
+           alphaU != alphaV) needs texture coordinates for its tangent frame -- an error there */
+        for (uint32_t i = 0; i < d.n_shapes; ++i)
+            if (!d.shapes[i].has_texcoords && anisotropic(d, d.shapes[i].material))
+                throw std::runtime_error("computeUVTangents(): texture coordinates are required to generate tangent vectors (anisotropic BSDF on a shape without them)");
+        sc->materialMask = 0;
+        for (const DevMaterial &m : mats) {
+            if (m.type == PHIP_BSDF_ROUGHCONDUCTOR) sc->materialMask |= MM_ROUGH;
+            if (m.type == PHIP_BSDF_DIELECTRIC) sc->materialMask |= MM_DIELECTRIC;
+        }
+        if (const char *e = expEnv("PHIP_SHADE_GENERIC")) if (atoi(e)) sc->materialMask = MM_ALL;
+    }
+
+    /* DevEmitters + selection pdf (scene.cpp:375-381), the single environment emitter */
+    void emitterSelection() {
+        ems.resize(d.n_emitters);
+        ecdf.assign(1, 0.0f);
+        for (uint32_t i = 0; i < d.n_emitters; ++i) {
+            const phip_emitter &e = d.emitters[i];
+            if (e.type == PHIP_EMITTER_CONSTANT || e.type == PHIP_EMITTER_ENVMAP) {
+                if (envEmitter >= 0) throw std::runtime_error("The scene may only contain one environment emitter");   /* scene.cpp:510-513 */
+                envEmitter = (int32_t) i;
+                envIsMap = e.type == PHIP_EMITTER_ENVMAP;
+            } else if (e.type != PHIP_EMITTER_AREA) throw std::runtime_error("unknown emitter type");
+            else if (e.shape >= d.n_shapes || d.shapes[e.shape].emitter != (int32_t) i) throw std::runtime_error("emitter/shape back reference mismatch");
+            memset(&ems[i], 0, sizeof(DevEmitter));
+            for (int k = 0; k < 3; ++k) ems[i].radiance[k] = e.radiance[k];
+            ems[i].samplingWeight = e.sampling_weight; ems[i].shape = e.type == PHIP_EMITTER_AREA ? e.shape : 0xFFFFFFFFu;
+            ecdf.push_back(ecdf.back() + e.sampling_weight);
+        }
+        if (d.n_emitters) {
+            const float sum = ecdf.back();
+            if (sum > 0) { emNorm = 1.0f / sum; for (size_t j = 1; j < ecdf.size(); ++j) ecdf[j] *= emNorm; ecdf.back() = 1.0f; }
+        }
+    }
+
+    /* acceleration structure (bvh.h) and the two limits of its encodings */
+    void buildAccel() {
+        const float camPos[3] = { d.camera.to_world[3], d.camera.to_world[7], d.camera.to_world[11] };
+        buildBVH(d.positions, d.indices, d.n_triangles, sc->bvh, camPos);
+        if (sc->bvh.tris.size() / 12 >= (1u << 28)) throw std::runtime_error("too many triangle records for the leaf reference encoding");
+        if (d.n_triangles > HIT_PRIM_MASK) throw std::runtime_error("too many triangles for the hit record (30-bit primitive index)");
+    }
+
+    /* shading records (dv_scene.h): the per-triangle constants come from the same __host__ __device__
+       functions the kernel would run, so precomputing them does not change a single bit */
+    void shadingRecords() {
+        bool anyTexcoords = false;
+        for (uint32_t i = 0; i < d.n_shapes; ++i) anyTexcoords |= d.shapes[i].has_texcoords != 0;
+        stride = anyTexcoords ? TRISHADE_FLOAT4S_UV : TRISHADE_FLOAT4S;
+        sc->triShadeStride = stride;
+        ts.assign((size_t) stride * d.n_triangles, make_float4(0, 0, 0, 0));
+        for (uint32_t i = 0; i < d.n_triangles; ++i) {
+            const DevShape &sh = shapes[triShape[i]];
+            const DevMaterial &m = mats[sh.material];
+            const uint32_t *ix = d.indices + 3 * (size_t) i;
+            const V3 p0(d.positions[3 * ix[0]], d.positions[3 * ix[0] + 1], d.positions[3 * ix[0] + 2]);
+            const V3 p1(d.positions[3 * ix[1]], d.positions[3 * ix[1] + 1], d.positions[3 * ix[1] + 2]);
+            const V3 p2(d.positions[3 * ix[2]], d.positions[3 * ix[2] + 1], d.positions[3 * ix[2] + 2]);
+            const bool twosided = m.type == PHIP_BSDF_TWOSIDED, texcoords = sh.pad != 0;
+            const uint32_t front = twosided ? m.nested0 : sh.material, back = twosided ? m.nested1 : sh.material;     /* (tagShadeClasses reads them back from the record) */
+            uint32_t flags = (sh.hasNormals ? TS_VERTEX_NORMALS : 0u) | (twosided ? TS_TWOSIDED : 0u) | (texcoords ? TS_TEXCOORDS : 0u)
+                           | ((m.flags & MF_SMOOTH) ? TS_MF_SMOOTH : 0u) | ((m.flags & MF_TRANS_OR_BACK) ? TS_TRANS_OR_BACK : 0u);
+            const V3 side1(p1 - p0), side2(p2 - p0);
+            V3 dpdu = side1, dpdv = side2;                      /* skdtree.h:378-379 */
+            float4 *r = ts.data() + (size_t) stride * i;
+            if (texcoords) {
+                /* TriMesh::computeUVTangents, trimesh.cpp:683-735 (zero tangents for degenerate triangles) */
+                const float *t0 = d.texcoords + 2 * (size_t) ix[0], *t1 = d.texcoords + 2 * (size_t) ix[1], *t2 = d.texcoords + 2 * (size_t) ix[2];
+                dpdu = V3(0.0f); dpdv = V3(0.0f);
+                const V2 dUV1(t1[0] - t0[0], t1[1] - t0[1]), dUV2(t2[0] - t0[0], t2[1] - t0[1]);
+                const V3 n = cross(side1, side2);
+                const float length = n.length();
+                if (length != 0) {
+                    const float determinant = dUV1.x * dUV2.y - dUV1.y * dUV2.x;
+                    if (determinant == 0) {
+                        coordinateSystem(n / length, dpdu, dpdv);
+                    } else {
+                        const float invDet = 1.0f / determinant;
+                        dpdu = (side1 * dUV2.y - side2 * dUV1.y) * invDet;
+                        dpdv = (side1 * (-dUV2.x) + side2 * dUV1.x) * invDet;
+                    }
+                }
+                r[6] = make_float4(t0[0], t0[1], t1[0], t1[1]);
+                r[7] = make_float4(t2[0], t2[1], dpdu.x, dpdu.y);
+                r[8] = make_float4(dpdu.z, dpdv.x, dpdv.y, dpdv.z);
+            }
+            V3 a, b, c;
+            if (sh.hasNormals) {
+                a = V3(d.normals[3 * ix[0]], d.normals[3 * ix[0] + 1], d.normals[3 * ix[0] + 2]);
+                b = V3(d.normals[3 * ix[1]], d.normals[3 * ix[1] + 1], d.normals[3 * ix[1] + 2]);
+                c = V3(d.normals[3 * ix[2]], d.normals[3 * ix[2] + 1], d.normals[3 * ix[2] + 2]);
+            } else {
+                Frame f; triShadingFrame(triFaceNormal(side1, side2), dpdu, f);
+                a = f.n; b = f.s; c = f.t;
+            }
+            r[0] = make_float4(p0.x, p0.y, p0.z, pm_from_bits(front));
+            r[1] = make_float4(p1.x, p1.y, p1.z, pm_from_bits(back));
+            r[2] = make_float4(p2.x, p2.y, p2.z, pm_from_bits((uint32_t) sh.emitter));
+            r[3] = make_float4(a.x, a.y, a.z, pm_from_bits(flags));
+            r[4] = make_float4(b.x, b.y, b.z, 0.0f);
+            r[5] = make_float4(c.x, c.y, c.z, 0.0f);
+        }
+    }
+
     /* shade class of every triangle in the spare word of its Wald record(s): 0 diffuse, 1 rough conductor, 2 dielectric -- the heavier
        of the two sides of a two-sided surface; k_rays_w passes it on in the hit record and k_shade deals its lanes by it (k_pool.h) */
-    {
+    void tagShadeClasses() {
         auto classOf = [&](uint32_t leaf) { const int t = mats[leaf].type; return t == PHIP_BSDF_ROUGHCONDUCTOR ? 1u : (t == PHIP_BSDF_DIELECTRIC ? 2u : 0u); };
         std::vector<uint8_t> cls(d.n_triangles);
         for (uint32_t i = 0; i < d.n_triangles; ++i) {
-            const DevMaterial &m = mats[shapes[triShape[i]].material];
-            const bool twosided = m.type == PHIP_BSDF_TWOSIDED;
-            const uint32_t a = classOf(twosided ? m.nested0 : shapes[triShape[i]].material), b = classOf(twosided ? m.nested1 : shapes[triShape[i]].material);
+            const float4 *r = ts.data() + (size_t) stride * i;          /* front and back material: shadingRecords */
+            const uint32_t a = classOf(pm_to_bits(r[0].w)), b = classOf(pm_to_bits(r[1].w));
             cls[i] = (uint8_t) ((a == 1u || b == 1u) ? 1u : std::max(a, b));
         }
         for (std::vector<float> *recs : { &sc->bvh.tris, &sc->bvh.wtris })
@@ -524,98 +569,71 @@ static void buildScene(phip_scene *sc, const phip_scene_desc &d) {
                 memcpy(&(*recs)[r + 11], &c, 4);
             }
     }
-    if (ts.empty()) sd.triShade.alloc(TRISHADE_FLOAT4S_UV); else sd.triShade.upload(ts.data(), ts.size());
-    if (texTexels.empty()) sd.texTexels.alloc(1); else sd.texTexels.upload(texTexels.data(), texTexels.size());
-    if (texDesc.empty()) sd.texDesc.alloc(1); else sd.texDesc.upload(texDesc.data(), texDesc.size());
-    sc->hasTextures = d.n_textures > 0; sc->triShadeStride = stride;
-    if (const char *e = expEnv("PHIP_TRAVERSAL")) sc->traversal = strcmp(e, "lane") == 0 ? 0 : 2;
-    /* the compressed 8-wide tree: every scene the packed leaf table of the LDS-resident kernels does not serve (more than 64 Wald records).  Round 6: it used to start at 64 BVH4
-       nodes; the scenes in between ran the round-1 BVH4 kernels (or, all-diffuse ones, k_mega's BVH4 walk in LDS) -- now they run k_mega on the wide tree / k_rays_w */
-    if (sc->bvh.nWNodes == 0) {      /* a scene without triangles: one node without children (all-zero meta bytes hit nothing) -- the ray kernels need a root to reject */
-        sc->bvh.wnodes.assign(20, 0u); sc->bvh.nWNodes = 1; sc->bvh.wMaxDepth = 1;
-    }
-    sc->wideOnly = sc->traversal == 2 && sc->bvh.nWNodes > 0 && (sc->bvh.nNodes >= 64 || sc->bvh.tris.size() / 12 > PHIP_WIDE_MIN_RECORDS);
-    if (const char *e = expEnv("PHIP_WIDE")) sc->wideOnly = sc->wideOnly && atoi(e) != 0;
-    /* ... and, round 6, EVERY scene has the wide tree on the device: the ray kernels of the wavefront path (k_rays_w) and phip_trace (k_raycast_w) walk nothing else -- the
-       round-1 BVH4 ray kernels are compiled by experiment builds only.  The LDS-resident scenes keep their BVH4-ordered records and leaf table for k_mega / k_shade_trace beside it */
-    sc->wide = sc->traversal == 2 && sc->bvh.nWNodes > 0 && (sc->wideOnly || !(PHIP_EXPERIMENTS && expEnv("PHIP_BVH4_RAYS")));
-    /* the stack of the structure that is going to be walked: three pushes per BVH4 level (the wide tree's group stack is checked below) */
-    if (!sc->wide && 3 * sc->bvh.maxDepth + 2 > STACK_DEPTH + SPILL_DEPTH) throw std::runtime_error("BVH too deep for the traversal stack");
-    if (sc->wide) {
-        if (WIDE_NODE_STRIDE == 5) sd.wnodes.upload((const uint4 *) sc->bvh.wnodes.data(), sc->bvh.wnodes.size() / 4);
-        else {                                               /* one node per WIDE_NODE_STRIDE * 16 bytes (a 128-byte line) */
-            const size_t n = sc->bvh.wnodes.size() / 20;
-            std::vector<uint4> padded(n * WIDE_NODE_STRIDE, make_uint4(0, 0, 0, 0));
-            for (size_t i = 0; i < n; ++i) memcpy(&padded[i * WIDE_NODE_STRIDE], &sc->bvh.wnodes[i * 20], 80);
-            sd.wnodes.upload(padded.data(), padded.size());
+
+    /* which structure the ray kernels walk (traversal, wideOnly, wide) and whether its depth fits their stacks */
+    void chooseTraversal() {
+        if (const char *e = expEnv("PHIP_TRAVERSAL")) sc->traversal = strcmp(e, "lane") == 0 ? 0 : 2;
+        /* the compressed 8-wide tree: every scene the packed leaf table of the LDS-resident kernels does not serve (more than 64 Wald records).  Round 6: it used to start at 64 BVH4
+           nodes; the scenes in between ran the round-1 BVH4 kernels (or, all-diffuse ones, k_mega's BVH4 walk in LDS) -- now they run k_mega on the wide tree / k_rays_w */
+        if (sc->bvh.nWNodes == 0) {      /* a scene without triangles: one node without children (all-zero meta bytes hit nothing) -- the ray kernels need a root to reject */
+            sc->bvh.wnodes.assign(20, 0u); sc->bvh.nWNodes = 1; sc->bvh.wMaxDepth = 1;
         }
-        if (sc->bvh.wtris.empty()) sd.wtris.alloc(3); else sd.wtris.upload((const float4 *) sc->bvh.wtris.data(), sc->bvh.wtris.size() / 4);
-    } else { sd.wnodes.alloc(5); sd.wtris.alloc(3); }
-    if (sc->wideOnly) {
-        sd.nodes.alloc(8); sd.tris.alloc(3); sd.trisAreWide = true;      /* (DevScene::tris = wtris: SceneDev::bind) */
-    } else {
-        if (sc->bvh.nodes.empty()) sd.nodes.alloc(8);
-        else sd.nodes.upload((const float4 *) sc->bvh.nodes.data(), sc->bvh.nodes.size() / 4);
-        sd.tris.upload((const float4 *) sc->bvh.tris.data(), sc->bvh.tris.size() / 4);
+        const char *wideSwitch = expEnv("PHIP_WIDE");
+        sc->wideOnly = sc->traversal == 2 && sc->bvh.nWNodes > 0 && (sc->bvh.nNodes >= 64 || sc->bvh.tris.size() / 12 > PHIP_WIDE_MIN_RECORDS)
+                    && (!wideSwitch || atoi(wideSwitch) != 0);
+        /* ... and, round 6, EVERY scene has the wide tree on the device: the ray kernels of the wavefront path (k_rays_w) and phip_trace (k_raycast_w) walk nothing else -- the
+           round-1 BVH4 ray kernels are compiled by experiment builds only.  The LDS-resident scenes keep their BVH4-ordered records and leaf table for k_mega / k_shade_trace beside it */
+        sc->wide = sc->traversal == 2 && sc->bvh.nWNodes > 0 && (sc->wideOnly || !(PHIP_EXPERIMENTS && expEnv("PHIP_BVH4_RAYS")));
+        /* the stack of the structure that is going to be walked: three pushes per BVH4 level, one group per level of the wide tree */
+        if (!sc->wide && 3 * sc->bvh.maxDepth + 2 > STACK_DEPTH + SPILL_DEPTH) throw std::runtime_error("BVH too deep for the traversal stack");
+        if (sc->wide && (int) sc->bvh.wMaxDepth + 2 > WIDE_STACK_LDS + SPILL_DEPTH / 2) throw std::runtime_error("wide BVH too deep for the traversal stack");
     }
-    sd.materials.upload(mats.data(), mats.size());
-    sc->materialMask = 0;
-    for (const DevMaterial &m : mats) {
-        if (m.type == PHIP_BSDF_ROUGHCONDUCTOR) sc->materialMask |= MM_ROUGH;
-        if (m.type == PHIP_BSDF_DIELECTRIC) sc->materialMask |= MM_DIELECTRIC;
-    }
-    if (const char *e = expEnv("PHIP_SHADE_GENERIC")) if (atoi(e)) sc->materialMask = MM_ALL;
+
     /* packed emitter table (dv_scene.h: EmitterTab) */
-    std::vector<float> tab(ecdf);
-    tab.resize(ecdf.size() + (size_t) EM_STRIDE * d.n_emitters, 0.0f);
-    const size_t cdfBase = tab.size();
-    size_t nEmTris = 0;
-    auto isArea = [&](uint32_t i) { return ems[i].shape != 0xFFFFFFFFu; };
-    for (uint32_t i = 0; i < d.n_emitters; ++i) if (isArea(i)) nEmTris += shapes[ems[i].shape].nTris;
-    const size_t recBase = (cdfBase + areaCdf.size() + 3) / 4 * 4;                /* 16-byte aligned */
-    const bool withRecs = recBase + nEmTris * 4 * TRISHADE_FLOAT4S <= EMITTER_LDS_FLOATS;
-    size_t recPos = recBase;
-    for (uint32_t i = 0; i < d.n_emitters; ++i) {
-        float *r = tab.data() + ecdf.size() + (size_t) EM_STRIDE * i;
-        for (int k = 0; k < 3; ++k) r[EM_RADIANCE + k] = ems[i].radiance[k];
-        r[EM_WEIGHT] = ems[i].samplingWeight;
-        r[EM_TYPE] = pm_from_bits(d.emitters[i].type);
-        if (!isArea(i)) continue;
-        const DevShape &sh = shapes[ems[i].shape];
-        r[EM_FIRST_TRI] = pm_from_bits(sh.firstTri); r[EM_N_TRIS] = pm_from_bits(sh.nTris);
-        r[EM_CDF] = pm_from_bits((uint32_t) (cdfBase + sh.cdfOffset));             /* area CDFs follow the records */
-        r[EM_INV_AREA] = sh.invSurfaceArea;
-        r[EM_REC] = pm_from_bits(withRecs ? (uint32_t) recPos : 0u);
-        recPos += (size_t) sh.nTris * 4 * TRISHADE_FLOAT4S;
-    }
-    tab.insert(tab.end(), areaCdf.begin(), areaCdf.end());
-    if (withRecs) {
-        tab.resize(recBase, 0.0f);
+    void packEmitterTable() {
+        tab = ecdf;
+        tab.resize(ecdf.size() + (size_t) EM_STRIDE * d.n_emitters, 0.0f);
+        const size_t cdfBase = tab.size();
+        size_t nEmTris = 0;
+        auto isArea = [&](uint32_t i) { return ems[i].shape != 0xFFFFFFFFu; };
+        for (uint32_t i = 0; i < d.n_emitters; ++i) if (isArea(i)) nEmTris += shapes[ems[i].shape].nTris;
+        const size_t recBase = (cdfBase + areaCdf.size() + 3) / 4 * 4;                /* 16-byte aligned */
+        const bool withRecs = recBase + nEmTris * 4 * TRISHADE_FLOAT4S <= EMITTER_LDS_FLOATS;
+        size_t recPos = recBase;
         for (uint32_t i = 0; i < d.n_emitters; ++i) {
+            float *r = tab.data() + ecdf.size() + (size_t) EM_STRIDE * i;
+            for (int k = 0; k < 3; ++k) r[EM_RADIANCE + k] = ems[i].radiance[k];
+            r[EM_WEIGHT] = ems[i].samplingWeight;
+            r[EM_TYPE] = pm_from_bits(d.emitters[i].type);
             if (!isArea(i)) continue;
             const DevShape &sh = shapes[ems[i].shape];
-            for (uint32_t k = 0; k < sh.nTris; ++k) {       /* the first six float4s of each record (positions, normal / vertex normals) */
-                const float *src = (const float *) (ts.data() + (size_t) stride * (sh.firstTri + k));
-                tab.insert(tab.end(), src, src + 4 * TRISHADE_FLOAT4S);
+            r[EM_FIRST_TRI] = pm_from_bits(sh.firstTri); r[EM_N_TRIS] = pm_from_bits(sh.nTris);
+            r[EM_CDF] = pm_from_bits((uint32_t) (cdfBase + sh.cdfOffset));             /* area CDFs follow the records */
+            r[EM_INV_AREA] = sh.invSurfaceArea;
+            r[EM_REC] = pm_from_bits(withRecs ? (uint32_t) recPos : 0u);
+            recPos += (size_t) sh.nTris * 4 * TRISHADE_FLOAT4S;
+        }
+        tab.insert(tab.end(), areaCdf.begin(), areaCdf.end());
+        if (withRecs) {
+            tab.resize(recBase, 0.0f);
+            for (uint32_t i = 0; i < d.n_emitters; ++i) {
+                if (!isArea(i)) continue;
+                const DevShape &sh = shapes[ems[i].shape];
+                for (uint32_t k = 0; k < sh.nTris; ++k) {       /* the first six float4s of each record (positions, normal / vertex normals) */
+                    const float *src = (const float *) (ts.data() + (size_t) stride * (sh.firstTri + k));
+                    tab.insert(tab.end(), src, src + 4 * TRISHADE_FLOAT4S);
+                }
             }
         }
+        if (tab.size() >= (1ull << 31)) throw std::runtime_error("emitter table too large");
+        tab.resize((tab.size() + 3) / 4 * 4, 0.0f);              /* whole float4s: the shading kernels stage the table in LDS with 16-byte loads */
     }
-    if (tab.size() >= (1ull << 31)) throw std::runtime_error("emitter table too large");
-    tab.resize((tab.size() + 3) / 4 * 4, 0.0f);              /* whole float4s: the shading kernels stage the table in LDS with 16-byte loads */
-    sd.emitterTab.upload(tab.data(), tab.size());
 
-    DevScene &D = sd.dev;
-    memset(&D, 0, sizeof(D));
-    D.nodes = sd.nodes.p; D.wtris = sd.wtris.p; D.tris = sd.trisAreWide ? sd.wtris.p : sd.tris.p; D.triShade = sd.triShade.p;
-    D.materials = sd.materials.p; D.nMaterials = (uint32_t) mats.size();
-    D.texTexels = sd.texTexels.p; D.textures = sd.texDesc.p; D.triShadeStride = sc->triShadeStride;
-    D.emitterTab = sd.emitterTab.p; D.emitterTabSize = (uint32_t) tab.size();
-    D.nEmitters = d.n_emitters; D.emitterNormalization = emNorm;
-    D.envEmitter = envEmitter;
-    if (envEmitter >= 0) {
-        /* ConstantBackgroundEmitter::createShape (constant.cpp:67-72) as seen from Scene::initializeBidirectional
-           (scene.cpp:384-413): bounding sphere (aabb.cpp:44-47) of the kd-tree's enlarged box expanded by the sensor
-           position (track.cpp:79-83), radius x 1.5 */
+    /* ConstantBackgroundEmitter::createShape (constant.cpp:67-72) as seen from Scene::initializeBidirectional
+       (scene.cpp:384-413): bounding sphere (aabb.cpp:44-47) of the kd-tree's enlarged box expanded by the sensor
+       position (track.cpp:79-83), radius x 1.5 */
+    void environmentSphere() {
+        if (envEmitter < 0) return;
         float mn[3], mx[3];
         for (int a = 0; a < 3; ++a) {
             mn[a] = d.n_triangles ? sc->bvh.sceneMin[a] : INFINITY; mx[a] = d.n_triangles ? sc->bvh.sceneMax[a] : -INFINITY;
@@ -630,38 +648,31 @@ static void buildScene(phip_scene *sc, const phip_scene_desc &d) {
         D.envCenter[0] = center.x; D.envCenter[1] = center.y; D.envCenter[2] = center.z;
         D.envRadius = std::max(PT_EPSILON, radius * 1.5f);
     }
-    if (envIsMap) {
-        /* EnvironmentMap::configure, envmap.cpp:262-328: marginal / conditional CDFs over luminance * sin(theta) */
+
+    /* EnvironmentMap::configure, envmap.cpp:262-328: the pyramid's texels, marginal / conditional CDFs over luminance * sin(theta), the transforms */
+    void buildEnvmap() {
+        if (!envIsMap) return;
         const phip_envmap &e = d.envmap;
         if (!e.texels || e.width == 0 || e.height == 0) throw std::runtime_error("envmap emitter without texels");
         if (std::max(e.width, e.height) > 0xFFFF) throw std::runtime_error("Environment maps images must be smaller than 65536 pixels in width and height");
         const int w = (int) e.width, h = (int) e.height;
-        std::vector<float4> tex((size_t) w * h);
+        std::vector<float4> &tex = envTexels;
+        tex.resize((size_t) w * h);
         for (size_t i = 0; i < tex.size(); ++i) tex[i] = make_float4(e.texels[3 * i], e.texels[3 * i + 1], e.texels[3 * i + 2], 0.0f);
-        /* MIP pyramid (level sizes of mipmap.h:182-192) + EWA weight table (mipmap.h:296-301) */
-        DevMipLevels lv; memset(&lv, 0, sizeof(lv));
-        lv.nLevels = 1; lv.lw[0] = w; lv.lh[0] = h; lv.offset[0] = 0;
+        /* MIP pyramid + EWA weight table */
+        DevMipLevels &lv = envLevels; memset(&lv, 0, sizeof(lv));
         lv.bcu = PHIP_WRAP_REPEAT; lv.bcv = PHIP_WRAP_CLAMP; lv.filterType = PHIP_FILTER_EWA; lv.maxAnisotropy = 10.0f;   /* envmap.cpp:138-139,176-178 */
-        if (e.n_levels > 1) {
-            int sx = w, sy = h, n = 1;
-            while (sx > 1 || sy > 1) {
-                sx = std::max(1, (sx + 1) / 2); sy = std::max(1, (sy + 1) / 2);
-                if (n >= PHIP_ENVMAP_MAX_LEVELS) throw std::runtime_error("envmap: too many MIP levels");
-                lv.lw[n] = sx; lv.lh[n] = sy; ++n;
-            }
-            if ((uint32_t) n != e.n_levels) throw std::runtime_error("envmap: n_levels must be 1 or the complete pyramid down to 1x1");
-            lv.nLevels = n;
-            for (int l = 1; l < n; ++l) {
-                if (!e.levels[l]) throw std::runtime_error("envmap: level pointer is NULL");
-                lv.offset[l] = (uint32_t) tex.size();
-                const size_t cnt = (size_t) lv.lw[l] * lv.lh[l];
-                for (size_t i = 0; i < cnt; ++i) tex.push_back(make_float4(e.levels[l][3 * i], e.levels[l][3 * i + 1], e.levels[l][3 * i + 2], 0.0f));
-            }
+        pyramidLevels(lv, w, h, e.n_levels, PHIP_ENVMAP_MAX_LEVELS, "envmap");
+        for (int l = 1; l < lv.nLevels; ++l) {
+            if (!e.levels[l]) throw std::runtime_error("envmap: level pointer is NULL");
+            lv.offset[l] = (uint32_t) tex.size();
+            const size_t cnt = (size_t) lv.lw[l] * lv.lh[l];
+            for (size_t i = 0; i < cnt; ++i) tex.push_back(make_float4(e.levels[l][3 * i], e.levels[l][3 * i + 1], e.levels[l][3 * i + 2], 0.0f));
         }
-        for (int i = 0; i < 64; ++i) { const float r2 = (float) i / 63.0f; lv.weightLut[i] = pm_expf(-2.0f * r2) - pm_expf(-2.0f); }
-        sd.envLevels.upload(&lv, 1);
+        ewaWeightLut(lv.weightLut);
         sc->envLevelCount = lv.nLevels;
-        std::vector<float> cdfCols((size_t) (w + 1) * h), cdfRows((size_t) h + 1), rowWeights((size_t) h);
+        std::vector<float> &cdfCols = envCdfCols, &cdfRows = envCdfRows, &rowWeights = envRowWeights;
+        cdfCols.resize((size_t) (w + 1) * h); cdfRows.resize((size_t) h + 1); rowWeights.resize((size_t) h);
         size_t colPos = 0, rowPos = 0;
         float rowSum = 0.0f;
         cdfRows[rowPos++] = 0;
@@ -689,153 +700,210 @@ static void buildScene(phip_scene *sc, const phip_scene_desc &d) {
         M4 tw, tl;
         for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) tw.m[i][j] = e.to_world[4 * i + j];
         if (!m4invert(tw, tl)) throw std::runtime_error("envmap toWorld is singular");
-        sd.envTexels.upload(tex.data(), tex.size());
-        sd.envCdfRows.upload(cdfRows.data(), cdfRows.size()); sd.envCdfCols.upload(cdfCols.data(), cdfCols.size());
-        sd.envRowWeights.upload(rowWeights.data(), rowWeights.size());
         DevEnvMap &E = D.env;
-        E.texels = sd.envTexels.p; E.levels = sd.envLevels.p; E.cdfRows = sd.envCdfRows.p; E.cdfCols = sd.envCdfCols.p; E.rowWeights = sd.envRowWeights.p;
         E.w = w; E.h = h; E.scale = e.scale;
         E.normalization = 1.0f / (rowSum * (2 * PT_PI / w) * (PT_PI / h));
         E.pixelSizeX = 2 * PT_PI / w; E.pixelSizeY = PT_PI / h;
         for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { E.toWorld[3 * i + j] = tw.m[i][j]; E.toLocal[3 * i + j] = tl.m[i][j]; }
     }
-    D.rootRef = sc->bvh.rootRef; D.nTriangles = d.n_triangles;
-    /* LDS staging plan: stack depth from the tree depth (3 pushes per BVH4 level), top-of-tree node cache
-       (nodes are in breadth-first order), all triangle records if there are few */
-    D.stackDepth = (uint32_t) std::min<int>(STACK_DEPTH, std::max<int>(4, 3 * ((int) sc->bvh.maxDepth - 1) + 1));
-    D.nodeCache = std::min<uint32_t>(sc->bvh.nNodes, NODE_CACHE_MAX);
-    D.triCache = (sc->bvh.tris.size() / 12 <= TRI_CACHE_MAX) ? (uint32_t) (sc->bvh.tris.size() / 12) : 0u;
-    if (const char *e = expEnv("PHIP_NODE_CACHE")) D.nodeCache = std::min<uint32_t>(sc->bvh.nNodes, (uint32_t) atoi(e));
-    if (D.nodeCache == 0) D.triCache = 0;
-    D.wnodes = sd.wnodes.p; D.wideNodeCache = 0;
-    D.preclip = sc->wide ? 1u : 0u;                          /* k_rays_w traverses rays the shading kernels have clipped (k_clip.h) */
-    /* the lane deal of k_shade pays where the expensive model is rare: rough conductors (microfacet sampling: atrium, 8 % of the vertices,
-       k_shade -7 %); on a diffuse + dielectric mix the extra round trip costs more than the cheap Fresnel branch (glass room: +8 %) */
-    D.shadeSort = (sc->wide && (sc->materialMask & MM_ROUGH)) ? 1u : 0u;
-    if (const char *e = expEnv("PHIP_SHADE_SORT")) D.shadeSort = D.shadeSort && atoi(e) != 0;       /* experiment hook */
-    if (sc->wide) {
-        if (sc->wideOnly) { D.nodeCache = 0; D.triCache = 0; }
-        D.wideNodeCache = std::min<uint32_t>(sc->bvh.nWNodes, WIDE_NODE_CACHE_MAX);
-        if (const char *e = expEnv("PHIP_NODE_CACHE")) D.wideNodeCache = std::min<uint32_t>(D.wideNodeCache, (uint32_t) atoi(e));
-        if ((int) sc->bvh.wMaxDepth + 2 > WIDE_STACK_LDS + SPILL_DEPTH / 2) throw std::runtime_error("wide BVH too deep for the traversal stack");
-    }
-    for (int a = 0; a < 3; ++a) { D.sceneMin[a] = sc->bvh.sceneMin[a]; D.sceneMax[a] = sc->bvh.sceneMax[a]; }
-    setupCamera(d.camera, d.film, D.cam);
-    D.film.width = d.film.crop_width; D.film.height = d.film.crop_height;
-    D.film.radius = d.film.filter_radius;
-    D.film.scaleFactor = PHIP_FILTER_RESOLUTION / d.film.filter_radius;     /* rfilter.cpp:50 */
-    D.film.border = (int) std::ceil(d.film.filter_radius - 0.5f);           /* rfilter.cpp:51 */
-    D.film.blockSize = 32;
-    for (int i = 0; i <= PHIP_FILTER_RESOLUTION; ++i) D.film.table[i] = d.film.filter_table[i];
 
-    sc->descCopy = d;
-    sc->descCopy.positions = nullptr; sc->descCopy.normals = nullptr; sc->descCopy.indices = nullptr;
-    sc->descCopy.shapes = nullptr; sc->descCopy.materials = nullptr; sc->descCopy.emitters = nullptr;
-    /* the fused kernel's LDS plan (k_mega.h): the whole tree, every Wald and shading record, the emitter table and the
-       materials in LDS, a stack that cannot spill; diffuse materials only (phip_mega.hip) */
-    /* (treeInLds: the whole tree and every Wald record are staged in LDS and the stack cannot spill -- also true of small scenes with glass, copper,
-       textures or an environment emitter, which k_shade_trace serves on the same packed leaf table: k_shade_trace.h) */
-    const bool treeInLds = D.nodeCache == sc->bvh.nNodes && D.triCache == sc->bvh.tris.size() / 12 && 3 * ((int) sc->bvh.maxDepth - 1) + 1 <= (int) D.stackDepth;
-    /* (leaf BSDF models: any -- round 5 -- when the tree is the packed leaf table; diffuse only for the trees the fused kernel walks or sweeps leaf by leaf: decided
-       below, once the table is built) */
-    const bool fitsLdsBase = !sc->hasTextures && envEmitter < 0 && stride == TRISHADE_FLOAT4S
-        && treeInLds && d.n_triangles <= MEGA_TRISHADE_MAX
-        && tab.size() <= EMITTER_LDS_FLOATS && mats.size() <= MATERIAL_LDS_MAX;
-    sc->fitsLds = fitsLdsBase && sc->materialMask == 0;
-    /* ... and, for trees of at most FLAT_LEAVES_MAX leaves (the Cornell box: 17), the leaves as a flat table: the fused kernel tests
-       every leaf box in one uniform pass instead of walking the 7-node tree (k_traverse.h: traverseFlat).  Entry = (min.xyz, bits(leaf
-       reference)) (max.xyz, 0), boxes as the BVH4 nodes hold them (padded). */
-    D.nFlatLeaves = 0; D.flatMode = 0; sd.flatLeaves.alloc(2); D.flatLeaves = sd.flatLeaves.p;
-    if (treeInLds && !sc->wideOnly && sc->bvh.nLeaves <= FLAT2_LEAVES_MAX && !expEnv("PHIP_NO_FLAT")) {
-        std::vector<float4> flat;
-        if (sc->bvh.rootRef < 0) {                         /* a single leaf: its box is the scene's */
-            flat.push_back(make_float4(sc->bvh.tightMin[0] - 1.0f, sc->bvh.tightMin[1] - 1.0f, sc->bvh.tightMin[2] - 1.0f, pm_from_bits((uint32_t) sc->bvh.rootRef)));
-            flat.push_back(make_float4(sc->bvh.tightMax[0] + 1.0f, sc->bvh.tightMax[1] + 1.0f, sc->bvh.tightMax[2] + 1.0f, 0.0f));
-        } else for (uint32_t n = 0; n < sc->bvh.nNodes; ++n) {
-            const float *nd = &sc->bvh.nodes[(size_t) n * 32];
-            for (int c = 0; c < 4; ++c) {
-                uint32_t ref; memcpy(&ref, &nd[24 + c], 4);
-                if (nd[c] == INFINITY || (int32_t) ref >= 0) continue;           /* empty slot / inner child */
-                flat.push_back(make_float4(nd[c], nd[4 + c], nd[8 + c], pm_from_bits(ref)));
-                flat.push_back(make_float4(nd[12 + c], nd[16 + c], nd[20 + c], 0.0f));
-            }
+    /* the plain-data fields of the DevScene: counts, box, camera, film; the scalar copy of the descriptor */
+    void sceneConstants() {
+        D.nMaterials = (uint32_t) mats.size(); D.triShadeStride = sc->triShadeStride;
+        D.emitterTabSize = (uint32_t) tab.size();
+        D.nEmitters = d.n_emitters; D.emitterNormalization = emNorm;
+        D.envEmitter = envEmitter;
+        D.rootRef = sc->bvh.rootRef; D.nTriangles = d.n_triangles;
+        for (int a = 0; a < 3; ++a) { D.sceneMin[a] = sc->bvh.sceneMin[a]; D.sceneMax[a] = sc->bvh.sceneMax[a]; }
+        setupCamera(d.camera, d.film, D.cam);
+        D.film.width = d.film.crop_width; D.film.height = d.film.crop_height;
+        D.film.radius = d.film.filter_radius;
+        D.film.scaleFactor = PHIP_FILTER_RESOLUTION / d.film.filter_radius;     /* rfilter.cpp:50 */
+        D.film.border = (int) std::ceil(d.film.filter_radius - 0.5f);           /* rfilter.cpp:51 */
+        D.film.blockSize = 32;
+        for (int i = 0; i <= PHIP_FILTER_RESOLUTION; ++i) D.film.table[i] = d.film.filter_table[i];
+        sc->descCopy = d;
+        sc->descCopy.positions = nullptr; sc->descCopy.normals = nullptr; sc->descCopy.indices = nullptr;
+        sc->descCopy.shapes = nullptr; sc->descCopy.materials = nullptr; sc->descCopy.emitters = nullptr;
+    }
+
+    /* LDS staging plan of the ray kernels: top-of-tree node cache (nodes are in breadth-first order), all triangle records if there are few, the
+       stack a walk of the BVH4 needs (3 pushes per level) -- and what follows from it for the fused kernel */
+    void ldsPlan() {
+        const HostBVH &bvh = sc->bvh;
+        const char *cacheSwitch = expEnv("PHIP_NODE_CACHE");
+        const uint32_t cacheMax = cacheSwitch ? (uint32_t) atoi(cacheSwitch) : 0xFFFFFFFFu;
+        walkStack = (uint32_t) std::min<int>(STACK_DEPTH, std::max<int>(4, 3 * ((int) bvh.maxDepth - 1) + 1));
+        D.nodeCache = sc->wideOnly ? 0u : std::min<uint32_t>(bvh.nNodes, cacheSwitch ? cacheMax : NODE_CACHE_MAX);
+        D.triCache = (!sc->wideOnly && D.nodeCache != 0 && bvh.tris.size() / 12 <= TRI_CACHE_MAX) ? (uint32_t) (bvh.tris.size() / 12) : 0u;
+        D.wideNodeCache = sc->wide ? std::min<uint32_t>(std::min<uint32_t>(bvh.nWNodes, WIDE_NODE_CACHE_MAX), cacheMax) : 0u;
+        D.preclip = sc->wide ? 1u : 0u;                          /* k_rays_w traverses rays the shading kernels have clipped (k_clip.h) */
+        /* the fused kernel's LDS plan (k_mega.h): the whole tree, every Wald and shading record, the emitter table and the
+           materials in LDS, a stack that cannot spill (phip_mega.hip) */
+        /* (treeInLds: the whole tree and every Wald record are staged in LDS and the stack cannot spill -- also true of small scenes with glass, copper,
+           textures or an environment emitter, which k_shade_trace serves on the same packed leaf table: k_shade_trace.h) */
+        treeInLds = D.nodeCache == bvh.nNodes && D.triCache == bvh.tris.size() / 12 && 3 * ((int) bvh.maxDepth - 1) + 1 <= (int) walkStack;
+        /* (leaf BSDF models: any -- round 5 -- when the tree is the packed leaf table; diffuse only for the trees the fused kernel walks or sweeps leaf by leaf:
+           chooseDevicePaths, once the table is built) */
+        fitsLdsBase = !sc->hasTextures && envEmitter < 0 && stride == TRISHADE_FLOAT4S
+            && treeInLds && d.n_triangles <= MEGA_TRISHADE_MAX
+            && tab.size() <= EMITTER_LDS_FLOATS && mats.size() <= MATERIAL_LDS_MAX;
+    }
+
+    /* the leaf boxes of flatLeafTable in the packed form with record masks (k_traverse.h: traverseFlat2).  A leaf reference is
+       ~((first record << 3) | records - 1); a triangle referenced by several leaves (spatial splits) has one record per
+       reference -- the copies carry the same 12 words, so only the first copy's bit is set.
+       Round 5: 33..64 records keep the packed form with a two-word mask (flatMode 3; the centre / half-extent table of the dealt
+       traversal only -- the high word rides in the centre's spare word) */
+    void packLeafTable(size_t nRec) {
+        std::vector<uint32_t> firstCopy(nRec);
+        for (size_t i = 0; i < nRec; ++i) {
+            firstCopy[i] = (uint32_t) i;
+            for (size_t j = 0; j < i; ++j) if (!memcmp(&sc->bvh.tris[12 * i], &sc->bvh.tris[12 * j], 48)) { firstCopy[i] = (uint32_t) j; break; }
         }
-        /* at most 32 Wald records: the packed form with record masks (k_traverse.h: traverseFlat2).  A leaf reference is
-           ~((first record << 3) | records - 1); a triangle referenced by several leaves (spatial splits) has one record per
-           reference -- the copies carry the same 12 words, so only the first copy's bit is set.
-           Round 5: 33..64 records keep the packed form with a two-word mask (flatMode 3; the centre / half-extent table of the dealt
-           traversal only -- the high word rides in the centre's spare word) */
-        const size_t nRec = sc->bvh.tris.size() / 12;
-        const size_t packedMax = (MEGA_FLAT_CH && MEGA_BALANCE && !expEnv("PHIP_NO_FLAT3")) ? 64 : 32;
-        if (flat.size() / 2 <= FLAT2_LEAVES_MAX && nRec <= packedMax && !expEnv("PHIP_NO_FLAT2")) {
-            std::vector<uint32_t> firstCopy(nRec);
-            for (size_t i = 0; i < nRec; ++i) {
-                firstCopy[i] = (uint32_t) i;
-                for (size_t j = 0; j < i; ++j) if (!memcmp(&sc->bvh.tris[12 * i], &sc->bvh.tris[12 * j], 48)) { firstCopy[i] = (uint32_t) j; break; }
-            }
-            std::vector<float4> packed;
-            for (size_t l = 0; l < flat.size() / 2; ++l) {
-                const float4 mn = flat[2 * l], mx = flat[2 * l + 1];
-                const uint32_t r = ~pm_to_bits(mn.w), first = r >> 3, count = (r & 7u) + 1u;
-                unsigned long long bits64 = 0;
-                for (uint32_t i = 0; i < count; ++i) bits64 |= 1ull << firstCopy[first + i];
-                const uint32_t bits = (uint32_t) bits64, bitsHi = (uint32_t) (bits64 >> 32);
+        std::vector<float4> packed;
+        for (size_t l = 0; l < flat.size() / 2; ++l) {
+            const float4 mn = flat[2 * l], mx = flat[2 * l + 1];
+            const uint32_t r = ~pm_to_bits(mn.w), first = r >> 3, count = (r & 7u) + 1u;
+            unsigned long long bits64 = 0;
+            for (uint32_t i = 0; i < count; ++i) bits64 |= 1ull << firstCopy[first + i];
+            const uint32_t bits = (uint32_t) bits64, bitsHi = (uint32_t) (bits64 >> 32);
 #if MEGA_FLAT_CH
-                /* centre / half extent (k_traverse.h: flat2Pass1).  c -+ h must cover the (padded) box whatever the rounding of c, and the
-                   distances c' -+ h |rcp| are rounded differently from the plane form the pad of bvh.h was sized for (two roundings of
-                   magnitude |c rcp| + |o rcp| instead of one): h gets the rounding of c and another 4e-6 of the scene's extent on top */
-                const float ext = std::max(sc->bvh.tightMax[0] - sc->bvh.tightMin[0], std::max(sc->bvh.tightMax[1] - sc->bvh.tightMin[1], sc->bvh.tightMax[2] - sc->bvh.tightMin[2]));
-                const float camMax = std::max(std::fabs(d.camera.to_world[3]), std::max(std::fabs(d.camera.to_world[7]), std::fabs(d.camera.to_world[11])));
-                float c[3], h[3];
-                const float lo[3] = { mn.x, mn.y, mn.z }, hi[3] = { mx.x, mx.y, mx.z };
-                for (int a = 0; a < 3; ++a) {
-                    c[a] = (float) (0.5 * ((double) lo[a] + (double) hi[a]));
-                    const double need = std::max((double) c[a] - (double) lo[a], (double) hi[a] - (double) c[a]);
-                    /* ... and the rounding of o rcp, which grows with the ORIGIN's magnitude (two roundings of |o rcp| move a plane by ~2^-23 |o|): the only rays
-                       that start outside the scene box are the camera's, so the camera position pays for it (a camera 60 scene extents away used to lose
-                       leaf boxes; tests/test_gpu_parity.py: far camera) */
-                    h[a] = std::nextafter((float) need, INFINITY) + 2.4e-7f * std::fabs(c[a]) + 4e-6f * ext + 4.8e-7f * camMax;      /* (the largest component on every axis: bvh.h, buildBVH) */
-                }
-                packed.push_back(make_float4(c[0], c[1], c[2], pm_from_bits(bitsHi)));
-                packed.push_back(make_float4(h[0], h[1], h[2], pm_from_bits(bits)));
-#else
-                (void) bitsHi;
-                packed.push_back(make_float4(mn.x, mx.x, mn.y, mx.y));
-                packed.push_back(make_float4(mn.z, mx.z, pm_from_bits(bits), 0.0f));
-#endif
+            /* centre / half extent (k_traverse.h: flat2Pass1).  c -+ h must cover the (padded) box whatever the rounding of c, and the
+               distances c' -+ h |rcp| are rounded differently from the plane form the pad of bvh.h was sized for (two roundings of
+               magnitude |c rcp| + |o rcp| instead of one): h gets the rounding of c and another 4e-6 of the scene's extent on top */
+            const float ext = std::max(sc->bvh.tightMax[0] - sc->bvh.tightMin[0], std::max(sc->bvh.tightMax[1] - sc->bvh.tightMin[1], sc->bvh.tightMax[2] - sc->bvh.tightMin[2]));
+            const float camMax = std::max(std::fabs(d.camera.to_world[3]), std::max(std::fabs(d.camera.to_world[7]), std::fabs(d.camera.to_world[11])));
+            float c[3], h[3];
+            const float lo[3] = { mn.x, mn.y, mn.z }, hi[3] = { mx.x, mx.y, mx.z };
+            for (int a = 0; a < 3; ++a) {
+                c[a] = (float) (0.5 * ((double) lo[a] + (double) hi[a]));
+                const double need = std::max((double) c[a] - (double) lo[a], (double) hi[a] - (double) c[a]);
+                /* ... and the rounding of o rcp, which grows with the ORIGIN's magnitude (two roundings of |o rcp| move a plane by ~2^-23 |o|): the only rays
+                   that start outside the scene box are the camera's, so the camera position pays for it (a camera 60 scene extents away used to lose
+                   leaf boxes; tests/test_gpu_parity.py: far camera) */
+                h[a] = std::nextafter((float) need, INFINITY) + 2.4e-7f * std::fabs(c[a]) + 4e-6f * ext + 4.8e-7f * camMax;      /* (the largest component on every axis: bvh.h, buildBVH) */
             }
-            flat.swap(packed); D.flatMode = nRec <= 32 ? 2 : 3;
-            /* k_mega deals the Wald tests over the wave through LDS buffers that lie over the (then unused) traversal stack (k_traverse.h: traverseFlat2W) */
-            D.stackDepth = std::max<uint32_t>(D.stackDepth, ((BLOCK / 64) * BAL_WAVE_BYTES + BLOCK * sizeof(uint32_t) - 1) / (BLOCK * sizeof(uint32_t)));
-        } else if (sc->fitsLds && flat.size() / 2 <= FLAT_LEAVES_MAX)
-            D.flatMode = 1;
-        if (D.flatMode) {
-            sd.flatLeaves.upload(flat.data(), flat.size());
-            D.flatLeaves = sd.flatLeaves.p; D.nFlatLeaves = (uint32_t) (flat.size() / 2);
+            packed.push_back(make_float4(c[0], c[1], c[2], pm_from_bits(bitsHi)));
+            packed.push_back(make_float4(h[0], h[1], h[2], pm_from_bits(bits)));
+#else
+            (void) bitsHi;
+            packed.push_back(make_float4(mn.x, mx.x, mn.y, mx.y));
+            packed.push_back(make_float4(mn.z, mx.z, pm_from_bits(bits), 0.0f));
+#endif
         }
+        flat.swap(packed);
     }
-    if (fitsLdsBase && sc->materialMask != 0 && D.flatMode >= 2 && !expEnv("PHIP_NO_MEGA_MATERIALS")) {
-        sc->fitsLds = true;
-        /* k_mega<MM_ALL> keeps its mailbox of copper vertices (QMC build: the exchange buffer of its class deal) in MEGA_DEAL_DWORDS x BLOCK dwords of LDS that lie over the traversal stack (k_mega.h) */
-        D.stackDepth = std::max<uint32_t>(D.stackDepth, MEGA_DEAL_DWORDS);
+
+    /* for trees of few leaves (the Cornell box: 17), the leaves as a flat table: the fused kernel tests every leaf box in one uniform pass instead
+       of walking the 7-node tree (k_traverse.h: traverseFlat).  Entry = (min.xyz, bits(leaf reference)) (max.xyz, 0), boxes as the BVH4 nodes hold
+       them (padded).  flatMode: 0 no table, 1 these boxes, 2 / 3 the packed form of at most 32 / 64 Wald records */
+    void flatLeafTable() {
+        int mode = 0;
+        if (treeInLds && !sc->wideOnly && sc->bvh.nLeaves <= FLAT2_LEAVES_MAX && !expEnv("PHIP_NO_FLAT")) {
+            if (sc->bvh.rootRef < 0) {                         /* a single leaf: its box is the scene's */
+                flat.push_back(make_float4(sc->bvh.tightMin[0] - 1.0f, sc->bvh.tightMin[1] - 1.0f, sc->bvh.tightMin[2] - 1.0f, pm_from_bits((uint32_t) sc->bvh.rootRef)));
+                flat.push_back(make_float4(sc->bvh.tightMax[0] + 1.0f, sc->bvh.tightMax[1] + 1.0f, sc->bvh.tightMax[2] + 1.0f, 0.0f));
+            } else for (uint32_t n = 0; n < sc->bvh.nNodes; ++n) {
+                const float *nd = &sc->bvh.nodes[(size_t) n * 32];
+                for (int c = 0; c < 4; ++c) {
+                    uint32_t ref; memcpy(&ref, &nd[24 + c], 4);
+                    if (nd[c] == INFINITY || (int32_t) ref >= 0) continue;           /* empty slot / inner child */
+                    flat.push_back(make_float4(nd[c], nd[4 + c], nd[8 + c], pm_from_bits(ref)));
+                    flat.push_back(make_float4(nd[12 + c], nd[16 + c], nd[20 + c], 0.0f));
+                }
+            }
+            const size_t nRec = sc->bvh.tris.size() / 12;
+            const size_t packedMax = (MEGA_FLAT_CH && MEGA_BALANCE && !expEnv("PHIP_NO_FLAT3")) ? 64 : 32;
+            if (flat.size() / 2 <= FLAT2_LEAVES_MAX && nRec <= packedMax && !expEnv("PHIP_NO_FLAT2")) {
+                packLeafTable(nRec); mode = nRec <= 32 ? 2 : 3;
+            } else if (fitsLdsBase && sc->materialMask == 0 && flat.size() / 2 <= FLAT_LEAVES_MAX)
+                mode = 1;
+        }
+        if (!mode) flat.clear();
+        D.flatMode = mode; D.nFlatLeaves = (uint32_t) (flat.size() / 2);
     }
-    /* round 6: the fused kernel on a tree that does not fit LDS (k_wide_wave.h) -- every scene on the 8-wide tree whose emitter table fits LDS and that needs none of the
-       feature sets k_mega is not compiled with (bitmap textures, an environment emitter) */
-    sc->fusedWide = (sc->wideOnly && !sc->hasTextures && envEmitter < 0 && stride == TRISHADE_FLOAT4S && tab.size() <= EMITTER_LDS_FLOATS
-                     && sc->bvh.wtris.size() / 12 < WP_TRI_MAX && !expEnv("PHIP_NO_MEGA_WIDE"))
-                  ? (mats.size() <= MATERIAL_LDS_MAX ? 4 : 5) : 0;
-    const bool traceable = D.flatMode >= 2 && tab.size() <= EMITTER_LDS_FLOATS && mats.size() <= MATERIAL_LDS_MAX && !expEnv("PHIP_NO_SHADE_TRACE");
-    sc->flatTrace = !sc->fitsLds && traceable; sc->flatTraceToo = sc->fitsLds && traceable;
-    /* ... whose lanes are dealt by BSDF model where there is more than one (the kernel traces its own rays and leaves the class in the hit word) */
-    if ((sc->flatTrace || sc->flatTraceToo) && sc->materialMask != 0) { D.shadeSort = 1u; if (const char *e = expEnv("PHIP_SHADE_SORT")) D.shadeSort = atoi(e) != 0 ? 1u : 0u; }
-    sd.counters.alloc(1);
-    sd.invalid.alloc(1);
-    sd.dynCounter.alloc(DYN_SHARDS * DYN_STRIDE);
-    sd.megaNext.alloc(1);
-    std::vector<float>().swap(sc->bvh.nodes); std::vector<float>().swap(sc->bvh.tris);      /* keep the statistics, drop the arrays */
-    std::vector<uint32_t>().swap(sc->bvh.wnodes); std::vector<float>().swap(sc->bvh.wtris);
-    HIP_TRY(hipHostMalloc((void **) &sc->cancelFlag, sizeof(int), hipHostMallocPortable | hipHostMallocMapped));
-    *sc->cancelFlag = 0;
+
+    /* which device path serves the scene: fitsLds (k_mega on the LDS-resident tree), fusedWide (k_mega on the 8-wide tree), flatTrace (k_shade_trace);
+       the stack the LDS plans of those kernels need, the lane deal of the shading kernels */
+    void chooseDevicePaths() {
+        const int mask = sc->materialMask;
+        /* leaf BSDF models: diffuse only for the trees the fused kernel walks or sweeps leaf by leaf, any (round 5) on the packed leaf table */
+        sc->fitsLds = fitsLdsBase && (mask == 0 || (D.flatMode >= 2 && !expEnv("PHIP_NO_MEGA_MATERIALS")));
+        /* round 6: the fused kernel on a tree that does not fit LDS (k_wide_wave.h) -- every scene on the 8-wide tree whose emitter table fits LDS and that needs none of the
+           feature sets k_mega is not compiled with (bitmap textures, an environment emitter) */
+        sc->fusedWide = (sc->wideOnly && !sc->hasTextures && envEmitter < 0 && stride == TRISHADE_FLOAT4S && tab.size() <= EMITTER_LDS_FLOATS
+                         && sc->bvh.wtris.size() / 12 < WP_TRI_MAX && !expEnv("PHIP_NO_MEGA_WIDE"))
+                      ? (mats.size() <= MATERIAL_LDS_MAX ? 4 : 5) : 0;
+        const bool traceable = D.flatMode >= 2 && tab.size() <= EMITTER_LDS_FLOATS && mats.size() <= MATERIAL_LDS_MAX && !expEnv("PHIP_NO_SHADE_TRACE");
+        sc->flatTrace = !sc->fitsLds && traceable; sc->flatTraceToo = sc->fitsLds && traceable;
+        /* the walk of the BVH4; k_mega deals the Wald tests of the packed table over the wave through LDS buffers that lie over the (then unused) traversal stack
+           (k_traverse.h: traverseFlat2W); k_mega<MM_ALL> keeps its mailbox of copper vertices (QMC build: the exchange buffer of its class deal) in MEGA_DEAL_DWORDS x BLOCK
+           dwords of LDS that lie there too (k_mega.h) */
+        const uint32_t dealStack = D.flatMode >= 2 ? (uint32_t) (((BLOCK / 64) * BAL_WAVE_BYTES + BLOCK * sizeof(uint32_t) - 1) / (BLOCK * sizeof(uint32_t))) : 0u;
+        const uint32_t mailboxStack = (sc->fitsLds && mask != 0) ? (uint32_t) MEGA_DEAL_DWORDS : 0u;
+        D.stackDepth = std::max(walkStack, std::max(dealStack, mailboxStack));
+        /* the lane deal of k_shade pays where the expensive model is rare: rough conductors (microfacet sampling: atrium, 8 % of the vertices,
+           k_shade -7 %); on a diffuse + dielectric mix the extra round trip costs more than the cheap Fresnel branch (glass room: +8 %).
+           k_shade_trace deals its lanes by BSDF model where there is more than one (the kernel traces its own rays and leaves the class in the hit word) */
+        const char *sortSwitch = expEnv("PHIP_SHADE_SORT");       /* experiment hook */
+        D.shadeSort = (((sc->wide && (mask & MM_ROUGH)) || (traceable && mask != 0)) && (!sortSwitch || atoi(sortSwitch) != 0)) ? 1u : 0u;
+    }
+
+    /* every immutable scene buffer of the device (placeholders where a kernel argument must not be NULL), the DevScene's pointers, the per-device counters */
+    void uploadScene() {
+        HostBVH &bvh = sc->bvh;
+        HIP_TRY(hipSetDevice(sd.device));
+        if (ts.empty()) sd.triShade.alloc(TRISHADE_FLOAT4S_UV); else sd.triShade.upload(ts.data(), ts.size());
+        if (texTexels.empty()) sd.texTexels.alloc(1); else sd.texTexels.upload(texTexels.data(), texTexels.size());
+        if (texDesc.empty()) sd.texDesc.alloc(1); else sd.texDesc.upload(texDesc.data(), texDesc.size());
+        if (sc->wide) {
+            if (WIDE_NODE_STRIDE == 5) sd.wnodes.upload((const uint4 *) bvh.wnodes.data(), bvh.wnodes.size() / 4);
+            else {                                               /* one node per WIDE_NODE_STRIDE * 16 bytes (a 128-byte line) */
+                const size_t n = bvh.wnodes.size() / 20;
+                std::vector<uint4> padded(n * WIDE_NODE_STRIDE, make_uint4(0, 0, 0, 0));
+                for (size_t i = 0; i < n; ++i) memcpy(&padded[i * WIDE_NODE_STRIDE], &bvh.wnodes[i * 20], 80);
+                sd.wnodes.upload(padded.data(), padded.size());
+            }
+            if (bvh.wtris.empty()) sd.wtris.alloc(3); else sd.wtris.upload((const float4 *) bvh.wtris.data(), bvh.wtris.size() / 4);
+        } else { sd.wnodes.alloc(5); sd.wtris.alloc(3); }
+        sd.trisAreWide = sc->wideOnly;                           /* DevScene::tris = wtris: SceneDev::bind */
+        if (sc->wideOnly) { sd.nodes.alloc(8); sd.tris.alloc(3); }
+        else {
+            if (bvh.nodes.empty()) sd.nodes.alloc(8);
+            else sd.nodes.upload((const float4 *) bvh.nodes.data(), bvh.nodes.size() / 4);
+            sd.tris.upload((const float4 *) bvh.tris.data(), bvh.tris.size() / 4);
+        }
+        sd.materials.upload(mats.data(), mats.size());
+        sd.emitterTab.upload(tab.data(), tab.size());
+        if (envIsMap) {
+            sd.envLevels.upload(&envLevels, 1);
+            sd.envTexels.upload(envTexels.data(), envTexels.size());
+            sd.envCdfRows.upload(envCdfRows.data(), envCdfRows.size()); sd.envCdfCols.upload(envCdfCols.data(), envCdfCols.size());
+            sd.envRowWeights.upload(envRowWeights.data(), envRowWeights.size());
+        }
+        if (flat.empty()) sd.flatLeaves.alloc(2); else sd.flatLeaves.upload(flat.data(), flat.size());
+        sd.bind();
+        sd.allocCounters();
+        std::vector<float>().swap(bvh.nodes); std::vector<float>().swap(bvh.tris);      /* keep the statistics, drop the arrays */
+        std::vector<uint32_t>().swap(bvh.wnodes); std::vector<float>().swap(bvh.wtris);
+        HIP_TRY(hipHostMalloc((void **) &sc->cancelFlag, sizeof(int), hipHostMallocPortable | hipHostMallocMapped));
+        *sc->cancelFlag = 0;
+    }
+};
+
+/* phip_scene_create: descriptor -> host arrays -> the decisions which kernels serve the scene -> one upload */
+static void buildScene(phip_scene *sc, const phip_scene_desc &d) {
+    SceneBuild B(sc, d);
+    B.validateDesc();
+    B.flattenShapes(); B.packTextures(); B.materials(); B.emitterSelection();
+    B.buildAccel();
+    B.shadingRecords(); B.tagShadeClasses();
+    B.chooseTraversal();
+    B.packEmitterTable(); B.environmentSphere(); B.buildEnvmap();
+    B.sceneConstants();
+    B.ldsPlan(); B.flatLeafTable(); B.chooseDevicePaths();
+    B.uploadScene();
 }
 
 
@@ -913,14 +981,11 @@ static SceneDev *replicateScene(phip_scene *sc, int device) {
     std::unique_ptr<SceneDev> dst(new SceneDev());
     dst->device = device;
     HIP_TRY(hipSetDevice(device));
-    dst->nodes.cloneFrom(src.nodes); dst->wnodes.cloneFrom(src.wnodes); dst->tris.cloneFrom(src.tris); dst->wtris.cloneFrom(src.wtris); dst->trisAreWide = src.trisAreWide; dst->triShade.cloneFrom(src.triShade); dst->flatLeaves.cloneFrom(src.flatLeaves);
-    dst->materials.cloneFrom(src.materials); dst->emitterTab.cloneFrom(src.emitterTab);
-    dst->texTexels.cloneFrom(src.texTexels); dst->texDesc.cloneFrom(src.texDesc);
-    dst->envTexels.cloneFrom(src.envTexels); dst->envLevels.cloneFrom(src.envLevels);
-    dst->envCdfRows.cloneFrom(src.envCdfRows); dst->envCdfCols.cloneFrom(src.envCdfCols); dst->envRowWeights.cloneFrom(src.envRowWeights);
+    SceneDev::forEachSceneBuffer([&](auto buf) { ((*dst).*buf).cloneFrom(src.*buf); });
+    dst->trisAreWide = src.trisAreWide;
     dst->dev = src.dev;
     dst->bind();
-    dst->counters.alloc(1); dst->invalid.alloc(1); dst->dynCounter.alloc(DYN_SHARDS * DYN_STRIDE); dst->megaNext.alloc(1);
+    dst->allocCounters();
     HIP_TRY(hipDeviceSynchronize());
     sc->devs.emplace_back(std::move(dst));
     return sc->devs.back().get();
