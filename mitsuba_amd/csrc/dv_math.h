@@ -20,15 +20,9 @@
 #include "../../include/phip_fmath.h"
 
 #define DV __host__ __device__ __forceinline__
-/* PHIP_EXPERIMENTS (tools/build_variant.sh -DPHIP_EXPERIMENTS=1): the alternatives that were measured against the product -- earlier kernel generations,
-   algorithm-selecting environment variables -- are compiled in; the shipped library carries one algorithm per job and reads no environment beyond the
-   documented knobs */
-#ifndef PHIP_EXPERIMENTS
-#define PHIP_EXPERIMENTS 0
-#endif
-/* the Sobol' row loops of sobolseq.h (one table read per index bit): the device code of the product draws through the byte tables only; the host keeps both
+/* the Sobol' row loops of sobolseq.h (one table read per index bit): the device code draws through the byte tables only; the host keeps both
    forms (tests/test_host_parity.py holds them against each other) */
-#if defined(__HIP_DEVICE_COMPILE__) && !PHIP_EXPERIMENTS
+#if defined(__HIP_DEVICE_COMPILE__)
 #define SOBOL_ROW_LOOPS 0
 #else
 #define SOBOL_ROW_LOOPS 1

@@ -47,9 +47,6 @@ struct PathPool {
     uint32_t capacity, nWaves;
     uint32_t spillLanes;              /* lanes the spill buffer covers (the host sizes it by its bound on the stack depth: phip.hip) */
 };
-/* the spill region of a lane of a BVH4 kernel, or NULL when the host's depth bound said that it cannot spill and the buffer does not cover the lane: a push beyond the LDS
-   entries then traps (TravStack::push) instead of writing out of bounds */
-__device__ __forceinline__ uint32_t *spillOf(const PathPool &P, size_t lane) { return lane < P.spillLanes ? P.spill + lane * 96u /* SPILL_DEPTH */ : nullptr; }
 
 /* The closest-hit record of a slot is (t, u, v, w) with w = bits(prim) | shade class << 30 (PHIP_NO_HIT stays all ones): the ray kernel
  * of the big scenes (k_rays_w) passes on the class it finds in the spare word of the Wald record it hit -- 0 diffuse, 1 rough
@@ -73,14 +70,8 @@ enum { ST_CLOSEST_RAYS = 0, ST_NODE, ST_TRI, ST_SHADOW_RAYS, ST_SH_NODE, ST_SH_T
 #define MEGA_WAVES 4                 /* k_mega: waves per SIMD (= blocks of 256 per CU): 128 VGPRs, no scratch -- with MachineLICM off for that unit (_ffi.py);
                                         with it on the kernel needs 168 VGPRs (3 waves: measured 2020 vs 2171 Msamples/s at 4 waves even with 148 B of scratch) */
 #endif
-#ifndef MEGA_MAILBOX
-#define MEGA_MAILBOX 1               /* k_mega<MM_ALL>, counter stream: a serving wave behind two LDS mailboxes (k_mega.h) */
-#endif
-#define MB_NS 64u                    /* entries of the S-box (dynamic LDS) and dwords per entry: the host sizes k_mega's launch with them */
+#define MB_NS 64u                    /* k_mega<MM_ALL>'s mailboxes (k_mega.h): entries of the S-box (dynamic LDS) and dwords per entry: the host sizes k_mega's launch with them */
 #define MB_DW 24u                    /* (22 words of path state + the sample's 64-bit sequence index, which the QMC builds carry along) */
-#ifndef MEGA_POOL
-#define MEGA_POOL 1                  /* k_mega<.., FLAT >= 4, ..>: one shared task stack per wave (k_wide_wave.h: traceWidePool); the host sizes the launch's LDS by it */
-#endif
 #ifndef MEGA_WIDE_NODE_CACHE
 #define MEGA_WIDE_NODE_CACHE 48u     /* k_mega<.., FLAT >= 4, ..>: top-of-tree nodes (BFS order) a block stages in LDS (80 B each) */
 #endif
@@ -102,7 +93,7 @@ struct MegaParams {
     uint32_t nWaves;
     /* k_mega<.., FLAT >= 4, ..> (the tree in memory: k_wide_wave.h) */
     uint32_t nodeCache;              /* top-of-tree nodes (BFS order) every block stages in LDS */
-    uint32_t *spill;                 /* overflow of the group stacks: SPILL_DEPTH words per lane of the grid */
+    uint32_t *spill;                 /* overflow of the waves' task stacks: SPILL_DEPTH words per lane of the grid */
 #if MEGA_MB_FAULT
     uint32_t faultWaves;             /* fault injection (phip.hip reads PHIP_TEST_FAULT_*): 0 none, 1 wave 0, 2 the four waves of block 0, 3 every wave reports that it gave up */
     uint32_t faultShort;             /* 1: the poisoned waves also under-report one sample (a mailbox time-out leaves the pass incomplete); 2: they only under-report */

@@ -14,9 +14,6 @@ __device__ __forceinline__ float miWeight(float pdfA, float pdfB) {
 #ifndef SHADE_WAVES
 #define SHADE_WAVES 4
 #endif
-#ifndef SHADE_STAGE_DUMMY
-#define SHADE_STAGE_DUMMY 0         /* A/B: 1 = the FEAT-16 kernels (materials in memory) issue the two look-alike staging loads of the materials as before round 5 */
-#endif
 #ifndef SHADE_WAVES_PLAIN
 #define SHADE_WAVES_PLAIN 5         /* scenes with more than one BSDF model but no environment emitter and no textures (the other instantiations spill
                                        100-200 B per lane at this bound): 95-102 VGPRs without the bound, 96 + 12..28 B of scratch with it.  The kernel waits
@@ -573,7 +570,7 @@ template <int MM, bool STRICT, int FEAT> __global__ __launch_bounds__(BLOCK, MM 
     v.rayD = P.rayD[lslot];
     v.thr = P.thr[lslot];
     v.mis = P.mis[lslot];
-    ShadeTables tab = stageShadeTables<(FEAT & 16) == 0 || SHADE_STAGE_DUMMY>(S, ldsEm, ldsMat);
+    ShadeTables tab = stageShadeTables<(FEAT & 16) == 0>(S, ldsEm, ldsMat);
     if (FEAT & 4) { tab.T.t = ldsEm; tab.materials = ldsMat; }     /* the host checked that both tables fit: LDS addressing (ds_read), no flat loads */
     else if (FEAT & 16) {
         /* the emitter table fits, the materials do not (the atrium: 252 materials = 24 KB): the emitter look-ups -- two dozen per NEE sample --

@@ -1,6 +1,6 @@
 /*
- * k_traverse.h -- per-lane BVH4 traversal as a state machine: scene-box clip, LDS-staged stack and tree cache, node step, traverse<>
- * Included by phip.hip (before k_rays.h, the ray kernels) and phip_mega.hip (traverse<> inside the fused kernel); see the header of phip.hip.
+ * k_traverse.h -- the LDS-resident trees: the block's staged tree and Wald records (setupTraversal), the packed leaf table with the Wald tests dealt
+ * over the wave (traverseFlat2W).  Included by phip.hip, phip_mega.hip and phip_shade.hip; see the header of phip.hip.
  */
 
 /* ======================================================================================
@@ -29,20 +29,10 @@ struct TravStack {
     lds_cf4 *tris;          /* LDS copy of triangle records [0, triCache) */
     uint32_t nodeCache, triCache;
     int depth, sp;
-    __device__ __forceinline__ void push(uint32_t v) {
-        if (sp < depth) lds[sp * BLOCK] = v;
-        else { if (!spill) __builtin_trap(); spill[sp - depth] = v; }     /* (no spill region: the host's depth bound was wrong -- stop, do not write out of bounds) */
-        ++sp;
-    }
-    __device__ __forceinline__ uint32_t pop() {
-        --sp;
-        return sp < depth ? lds[sp * BLOCK] : spill[sp - depth];
-    }
-    __device__ __forceinline__ uint32_t popLds() { --sp; return lds[sp * BLOCK]; }    /* the caller knows that nothing spilled */
 };
 
-/* k_mega<MM_ALL>: the region [0, 12 KB) of the dynamic LDS, over the traversal stack (phip.hip sizes it) -- MEGA_CLASS_DEAL (QMC build): dwords per lane and exchange round;
-   MEGA_MAILBOX: the four waves' work lists (6 KB), then the S-box */
+/* k_mega<MM_ALL>: the region [0, 12 KB) of the dynamic LDS, over the traversal stack (phip.hip sizes it) --
+   the four waves' work lists (6 KB), then the S-box of the mailboxes */
 #define MEGA_DEAL_DWORDS 12u
 /* bytes of dynamic LDS setupTraversal() uses; k_mega appends its shading tables (megaLdsBytesOf) */
 __host__ __device__ __forceinline__ size_t traversalLdsBytesOf(const DevScene &S) {
@@ -74,216 +64,16 @@ __device__ __forceinline__ void setupTraversal(const DevScene &S, unsigned char 
     stk.nodeCache = S.nodeCache; stk.triCache = S.triCache; stk.depth = (int) S.stackDepth; stk.sp = 0;
 }
 
-/* ALL_LDS (a constant in the scope of the caller): the whole tree, every record and the whole stack are in LDS (k_mega) --
-   no residency test, no spill path.
-   TYPED (a constant in the scope of the caller): true = separate LDS (ds_read_b128) and global paths -- right when (almost)
-   everything is cached (small scenes); false = one flat_load path with a selected address -- fewer registers and no
-   divergence when most lanes read global memory (big scenes; measured 1-3 % faster there, 14 % slower on the Cornell box) */
-#define LOAD_NODE(stack, S, cur, mnx, mny, mnz, mxx, mxy, mxz, chf)                                   \
-    float4 mnx, mny, mnz, mxx, mxy, mxz, chf;                                                         \
-    if (TYPED) {                                                                                      \
-        if (ALL_LDS || (uint32_t) (cur) < (stack).nodeCache) {                                        \
-            lds_cf4 *n_ = (stack).nodes + (uint32_t) (cur) * NODE_LDS_STRIDE;                         \
-            mnx = ldsLoad4(n_); mny = ldsLoad4(n_ + 1); mnz = ldsLoad4(n_ + 2); mxx = ldsLoad4(n_ + 3); \
-            mxy = ldsLoad4(n_ + 4); mxz = ldsLoad4(n_ + 5); chf = ldsLoad4(n_ + 6);                   \
-        } else {                                                                                      \
-            const float4 *n_ = (S).nodes + 8 * (size_t) (cur);                                        \
-            mnx = n_[0]; mny = n_[1]; mnz = n_[2]; mxx = n_[3]; mxy = n_[4]; mxz = n_[5]; chf = n_[6]; \
-        }                                                                                             \
-    } else {                                                                                          \
-        const float4 *n_ = (uint32_t) (cur) < (stack).nodeCache                                       \
-            ? (const float4 *) ((stack).nodes + (uint32_t) (cur) * NODE_LDS_STRIDE) : (S).nodes + 8 * (size_t) (cur); \
-        mnx = n_[0]; mny = n_[1]; mnz = n_[2]; mxx = n_[3]; mxy = n_[4]; mxz = n_[5]; chf = n_[6];    \
-    }
-#define LOAD_TRI(stack, S, idx, a, b, c)                                                              \
-    float4 a, b, c;                                                                                   \
-    if (TYPED) {                                                                                      \
-        if (ALL_LDS || (uint32_t) (idx) < (stack).triCache) {                                         \
-            lds_cf4 *t_ = (stack).tris + 3 * (uint32_t) (idx); a = ldsLoad4(t_); b = ldsLoad4(t_ + 1); c = ldsLoad4(t_ + 2); \
-        } else {                                                                                      \
-            const float4 *t_ = (S).tris + 3 * (size_t) (idx); a = t_[0]; b = t_[1]; c = t_[2];        \
-        }                                                                                             \
-    } else {                                                                                          \
-        const float4 *t_ = (uint32_t) (idx) < (stack).triCache ? (const float4 *) ((stack).tris + 3 * (uint32_t) (idx)) : (S).tris + 3 * (size_t) (idx); \
-        a = t_[0]; b = t_[1]; c = t_[2];                                                              \
-    }
 #define SPILL_DEPTH 96
-static_assert(SPILL_DEPTH == 96, "k_pool.h: spillOf");
 
 
-__device__ __forceinline__ void cswap(float &ka, uint32_t &ra, float &kb, uint32_t &rb) {
-    const bool sw = kb < ka;
-    const float k0 = sw ? kb : ka, k1 = sw ? ka : kb;
-    const uint32_t r0 = sw ? rb : ra, r1 = sw ? ra : rb;
-    ka = k0; kb = k1; ra = r0; rb = r1;
-}
-
-#define SHADOW_UNSORTED 1
-#ifndef MEGA_UNSORTED
-#define MEGA_UNSORTED 1          /* k_mega (whole tree in LDS, 7 nodes on the Cornell box): closest-hit rays visit the children unsorted too -- the sorting network costs more than the culling it buys: 106.9 -> 103.7 ms per C2 frame (the answer does not depend on the order: winsTie) */
-#endif
-#define DONE_REF ((int32_t) 0x80000000)   /* 'no more nodes' marker; as a leaf reference it would need 2^28 triangle records */
-
-/* One BVH4 node step: slab test of the four children, nearest-first order, push the farther hits,
-   continue with the nearest (or pop).  Shared by the per-slot and the persistent kernels. */
-#define NODE_STEP(stack, S, cur, rcp, ordr, mint, maxt, nodeVisits)                                       \
-    {                                                                                                     \
-        LOAD_NODE(stack, S, cur, mnx, mny, mnz, mxx, mxy, mxz, chf)                                       \
-        ++nodeVisits;                                                                                     \
-        float key[4]; uint32_t ref[4];                                                                    \
-        SLAB(0, x) SLAB(1, y) SLAB(2, z) SLAB(3, w)                                                       \
-        /* nearest child first (also a good any-hit order); misses (INFINITY) sort to the end */         \
-        cswap(key[0], ref[0], key[1], ref[1]); cswap(key[2], ref[2], key[3], ref[3]);                     \
-        cswap(key[0], ref[0], key[2], ref[2]); cswap(key[1], ref[1], key[3], ref[3]);                     \
-        cswap(key[1], ref[1], key[2], ref[2]);                                                            \
-        if (key[0] < INFINITY) {                                                                          \
-            if (ALL_LDS || stack.sp + 3 <= stack.depth) {      /* branch-free pushes: hits are a prefix of the sorted keys */ \
-                stack.lds[stack.sp * BLOCK] = ref[3]; stack.sp += key[3] < INFINITY ? 1 : 0;              \
-                stack.lds[stack.sp * BLOCK] = ref[2]; stack.sp += key[2] < INFINITY ? 1 : 0;              \
-                stack.lds[stack.sp * BLOCK] = ref[1]; stack.sp += key[1] < INFINITY ? 1 : 0;              \
-            } else {                                                                                      \
-                if (key[3] < INFINITY) stack.push(ref[3]);                                                \
-                if (key[2] < INFINITY) stack.push(ref[2]);                                                \
-                if (key[1] < INFINITY) stack.push(ref[1]);                                                \
-            }                                                                                             \
-            cur = (int32_t) ref[0];                                                                       \
-        } else {                                                                                          \
-            cur = stack.sp == 0 ? DONE_REF : (int32_t) (ALL_LDS ? stack.popLds() : stack.pop());          \
-        }                                                                                                 \
-    }
-/* Any-hit variant: the visiting order of the children does not matter for an unoccluded ray (all of them are
-   visited) -- no sorting network.  Branch-free: every hit child is written at the current stack top, the top only
-   advances once a later hit shows that the entry has to be kept; the last hit child becomes the next node. */
-#define NODE_STEP_ANY(stack, S, cur, rcp, ordr, mint, maxt, nodeVisits)                                   \
-    {                                                                                                     \
-        LOAD_NODE(stack, S, cur, mnx, mny, mnz, mxx, mxy, mxz, chf)                                       \
-        ++nodeVisits;                                                                                     \
-        float key[4]; uint32_t ref[4];                                                                    \
-        SLAB(0, x) SLAB(1, y) SLAB(2, z) SLAB(3, w)                                                       \
-        const bool h0 = key[0] < INFINITY, h1 = key[1] < INFINITY, h2 = key[2] < INFINITY, h3 = key[3] < INFINITY; \
-        if (h0 || h1 || h2 || h3) {                                                                       \
-            uint32_t nxt = ref[0]; bool have = h0;                                                        \
-            if (ALL_LDS || stack.sp + 3 <= stack.depth) {                                                 \
-                stack.lds[stack.sp * BLOCK] = nxt; stack.sp += (h1 && have) ? 1 : 0; nxt = h1 ? ref[1] : nxt; have = have || h1; \
-                stack.lds[stack.sp * BLOCK] = nxt; stack.sp += (h2 && have) ? 1 : 0; nxt = h2 ? ref[2] : nxt; have = have || h2; \
-                stack.lds[stack.sp * BLOCK] = nxt; stack.sp += (h3 && have) ? 1 : 0; nxt = h3 ? ref[3] : nxt;                     \
-            } else {                                                                                      \
-                if (h1) { if (have) stack.push(nxt); nxt = ref[1]; have = true; }                         \
-                if (h2) { if (have) stack.push(nxt); nxt = ref[2]; have = true; }                         \
-                if (h3) { if (have) stack.push(nxt); nxt = ref[3]; have = true; }                         \
-            }                                                                                             \
-            cur = (int32_t) nxt;                                                                          \
-        } else {                                                                                          \
-            cur = stack.sp == 0 ? DONE_REF : (int32_t) (ALL_LDS ? stack.popLds() : stack.pop());          \
-        }                                                                                                 \
-    }
-#define SLAB(K, C)                                                                                        \
-    {                                                                                                     \
-        const float x0 = fmaf(mnx.C, rcp.x, -ordr.x), x1 = fmaf(mxx.C, rcp.x, -ordr.x);                   \
-        const float y0 = fmaf(mny.C, rcp.y, -ordr.y), y1 = fmaf(mxy.C, rcp.y, -ordr.y);                   \
-        const float z0 = fmaf(mnz.C, rcp.z, -ordr.z), z1 = fmaf(mxz.C, rcp.z, -ordr.z);                   \
-        const float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), mint));          \
-        const float tf = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), maxt));          \
-        key[K] = (tn <= tf) ? tn : INFINITY;                                                              \
-        ref[K] = pm_to_bits(chf.C);                                                                       \
-    }
-
-/* Traversal as a per-lane state machine whose loop body is ONE node step and ONE triangle test: a lane
- * inside a leaf tests one Wald record per iteration while its neighbours go on with node
- * steps.  (Looping over the whole leaf inside the body made every lane of the wave wait for up to eight
- * triangle tests per iteration although only ~15 % of the lanes sit in a leaf: measured 2x the issue slots.)
- * The order in which a ray tests its triangles is unchanged, hence so are the results. */
-template <bool SHADOW, bool ALL_LDS = false>
-__device__ __forceinline__ bool traverse(const DevScene &S, const V3 &o, const V3 &d, const V3 &rcp /* clipToScene's slab reciprocal */, float mint, float maxt,
-                                         TravStack &stack, TravResult &res,
-                                         uint32_t &nodeVisits, uint32_t &triTests) {
-    constexpr bool TYPED = true;
-    /* the slab tests use the reciprocal direction (conservative: boxes are padded); the Wald test uses o,d */
-    const V3 ordr(o.x * rcp.x, o.y * rcp.y, o.z * rcp.z);
-    stack.sp = 0;
-    int32_t cur = S.rootRef;
-    bool found = false;
-    res.prim = PHIP_NO_HIT; res.t = INFINITY; res.u = res.v = 0;
-    while (cur != DONE_REF) {
-        if (cur >= 0) {
-            if ((SHADOW && SHADOW_UNSORTED) || (ALL_LDS && MEGA_UNSORTED)) NODE_STEP_ANY(stack, S, cur, rcp, ordr, mint, maxt, nodeVisits)
-            else NODE_STEP(stack, S, cur, rcp, ordr, mint, maxt, nodeVisits)
-        }
-        if (cur < 0 && cur != DONE_REF) {
-            /* a leaf reference doubles as the lane's progress inside the leaf: ~((next record << 3) | records left - 1) */
-            const uint32_t r = ~(uint32_t) cur, idx = r >> 3, left = r & 7u;
-            LOAD_TRI(stack, S, idx, a, b, c)
-            ++triTests;
-            float tu, tv, tt;
-            if (waldIntersect(a, b, c, o, d, mint, maxt, tu, tv, tt)) {
-                if (SHADOW) return true;
-                if (winsTie(tt, pm_to_bits(c.z), res.t, res.prim)) { maxt = tt; res.t = tt; res.u = tu; res.v = tv; res.prim = pm_to_bits(c.z); }
-                found = true;
-            }
-            cur = left ? (int32_t) ~(((idx + 1u) << 3) | (left - 1u)) : (stack.sp == 0 ? DONE_REF : (int32_t) (ALL_LDS ? stack.popLds() : stack.pop()));
-        }
-    }
-    return found;
-}
-
-/* Trees of at most FLAT_LEAVES_MAX leaves in LDS (k_mega; the Cornell box has 17 leaves over 7 nodes): no walk at all.
- *   pass 1, uniform: every lane tests the SAME leaf box per step (the table entry is one LDS broadcast) -> a bit mask of the leaves
- *           its ray enters; 16 VALU per leaf at full lane utilisation instead of 3.3 divergent node steps of ~85;
- *   pass 2, per lane: the Wald records of the leaves in the mask, one test per iteration (the loop body is the triangle block alone,
- *           not node step + triangle block).
- * Leaves are visited in table order, not front to back: with the tie rule (winsTie) the answer does not depend on it; a leaf whose
- * box lies behind a hit found earlier is still tested (its records fail the t <= maxt test). */
-template <bool SHADOW>
-__device__ __forceinline__ bool traverseFlat(const DevScene &S, lds_cf4 *flat, uint32_t nFlat, const V3 &o, const V3 &d, const V3 &rcp, float mint, float maxt,
-                                             TravStack &stack, TravResult &res, uint32_t &nodeVisits, uint32_t &triTests) {
-    constexpr bool ALL_LDS = true, TYPED = true;
-    const V3 ordr(o.x * rcp.x, o.y * rcp.y, o.z * rcp.z);
-    uint32_t mask = 0;
-    for (uint32_t c = 0; c < nFlat; ++c) {
-        const float4 mn = ldsLoad4(flat + 2 * c), mx = ldsLoad4(flat + 2 * c + 1);      /* (scalar loads from the kernel argument instead: 87.6 vs 80.4 ms per C2 frame) */
-        const float x0 = fmaf(mn.x, rcp.x, -ordr.x), x1 = fmaf(mx.x, rcp.x, -ordr.x);
-        const float y0 = fmaf(mn.y, rcp.y, -ordr.y), y1 = fmaf(mx.y, rcp.y, -ordr.y);
-        const float z0 = fmaf(mn.z, rcp.z, -ordr.z), z1 = fmaf(mx.z, rcp.z, -ordr.z);
-        const float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), mint));
-        const float tf = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), maxt));
-        mask |= (tn <= tf) ? (1u << c) : 0u;
-    }
-    ++nodeVisits;
-    bool found = false;
-    res.prim = PHIP_NO_HIT; res.t = INFINITY; res.u = res.v = 0;
-    int32_t cur = DONE_REF;
-    for (;;) {
-        if (cur == DONE_REF) {
-            if (mask == 0) break;
-            const uint32_t c = (uint32_t) __ffs((int) mask) - 1u;
-            mask &= mask - 1u;
-            cur = (int32_t) pm_to_bits(ldsLoad4(flat + 2 * c).w);
-        }
-        /* a leaf reference doubles as the lane's progress inside the leaf: ~((next record << 3) | records left - 1) */
-        const uint32_t r = ~(uint32_t) cur, idx = r >> 3, left = r & 7u;
-        LOAD_TRI(stack, S, idx, a, b, c)
-        ++triTests;
-        float tu, tv, tt;
-        if (waldIntersect(a, b, c, o, d, mint, maxt, tu, tv, tt)) {
-            if (SHADOW) return true;
-            if (winsTie(tt, pm_to_bits(c.z), res.t, res.prim)) { maxt = tt; res.t = tt; res.u = tu; res.v = tv; res.prim = pm_to_bits(c.z); }
-            found = true;
-        }
-        cur = left ? (int32_t) ~(((idx + 1u) << 3) | (left - 1u)) : DONE_REF;
-    }
-    return found;
-}
-
-/* Second form of the flat table, for trees of at most 32 Wald records (the Cornell box: 32 triangles in 17 leaves): entry c =
- *   A = (min.x, max.x, min.y, max.y)   B = (min.z, max.z, bits(mask of the leaf's records), 0)
- * so that (a) the two planes of an axis are one packed multiply-add (v_pk_fma_f32), and (b) pass 1 yields a bit mask of RECORDS: pass 2
- * is `while (mask) test record ffs(mask)` -- no leaf reference to fetch and decode between records, a record referenced by two leaves is
- * tested once.  Pass 1 takes the entries four at a time (eight LDS broadcasts in flight instead of a wait per leaf), the rest one by one.  The Wald test is branch-free here (waldIntersectSel: the axis permutation as twelve
- * selects instead of three divergent branches -- inside traverseFlat the exec-mask bookkeeping was 40 scalar instructions per record).
- * Same arithmetic on the same operands, so (t, u, v, prim) are the same bits; records in index order instead of leaf order: winsTie. */
-#ifndef MEGA_WALD_PAIR
-#define MEGA_WALD_PAIR 0
-#endif
+/* The packed leaf table of trees of at most 64 Wald records (the Cornell box: 32 triangles in 17 leaves): no walk at all.
+ *   pass 1, uniform: every lane tests the SAME leaf box per step (the table entry is one LDS broadcast) and collects a bit mask of the RECORDS of the
+ *           leaves its ray enters; the entries four at a time (eight LDS broadcasts in flight instead of a wait per leaf), the rest one by one;
+ *   pass 2: the Wald tests of the records in the masks (traverseFlat2W below) -- no leaf reference to fetch and decode between records, a record
+ *           referenced by two leaves is tested once.  The Wald test is branch-free here (waldIntersectSel: the axis permutation as twelve selects
+ *           instead of three divergent branches).
+ * Same arithmetic on the same operands as the walk of the tree, so (t, u, v, prim) are the same bits; records in index order instead of leaf order: winsTie. */
 typedef float f2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ bool waldIntersectSel(const float4 &a, const float4 &b, const float4 &c, const V3 &o, const V3 &d,
                                                  float mint, float maxt, float &u, float &v, float &t) {
@@ -302,25 +92,15 @@ __device__ __forceinline__ bool waldIntersectSel(const float4 &a, const float4 &
 }
 
 
-/* Pass 1 of the packed flat table (DevScene::flatMode 2): the bit mask of the Wald records whose leaf box the ray enters.  Two forms of the
- * table, a compile-time choice shared with the host code that packs it (phip.hip):
- *   MEGA_FLAT_CH = 0: entry = (min.x, max.x, min.y, max.y) (min.z, max.z, bits(records), 0): an axis is one v_pk_fma_f32, then the pair is
- *      ordered with a min and a max -- 15.3 VALU per box;
- *   MEGA_FLAT_CH = 1: entry = (c.x, c.y, c.z, 0) (h.x, h.y, h.z, bits(records)), centre and half extent: with c' = c * rcp - o * rcp the slab
- *      distances of an axis are c' -+ h * |rcp| -- ALREADY ordered, one v_pk_fma_f32 whose source modifiers negate h for the low half and
- *      replicate h, |rcp| and c' into both halves (inline assembly: the compiler does not form them) -- 11.3 VALU per box.  The two forms
- *      round differently; the test only has to be conservative, and the host pads h for it (phip.hip). */
-#ifndef MEGA_FLAT_CH
-#define MEGA_FLAT_CH 1
-#endif
-#ifndef MEGA_BALANCE
-#define MEGA_BALANCE 1               /* k_mega, packed flat table: the Wald tests of a traversal are dealt over the lanes of the wave (traverseFlat2W below) instead of looping per lane */
-#endif
+/* Pass 1 of the packed flat table (DevScene::flatMode 2 / 3): the bit mask of the Wald records whose leaf box the ray enters.  The table's form is shared
+ * with the host code that packs it (phip.hip): entry = (c.x, c.y, c.z, 0) (h.x, h.y, h.z, bits(records)), centre and half extent: with
+ * c' = c * rcp - o * rcp the slab distances of an axis are c' -+ h * |rcp| -- ALREADY ordered, one v_pk_fma_f32 whose source modifiers negate h for the
+ * low half and replicate h, |rcp| and c' into both halves (inline assembly: the compiler does not form them) -- 11.3 VALU per box, against 15.3 for a
+ * table of planes whose pairs are ordered with a min and a max (HISTORY.md).  The test only has to be conservative, and the host pads h for it (phip.hip). */
 /* R64 (DevScene::flatMode 3, trees of 33..64 Wald records): the record mask has a second word, kept in the centre's spare word (A.w) */
 template <bool R64 = false>
 __device__ __forceinline__ uint32_t flat2Pass1(lds_cf4 *flat, uint32_t nFlat, const V3 &o, const V3 &rcp, float mint, float maxt, uint32_t *maskHi = nullptr) {
     uint32_t mask = 0, hi = 0;
-#if MEGA_FLAT_CH
     const f2v rxy = { rcp.x, rcp.y }, oxy = { -(o.x * rcp.x), -(o.y * rcp.y) };
     const f2v rz2 = { rcp.z, 0.0f }, oz2 = { -(o.z * rcp.z), 0.0f };
     f2v axy = { fabsf(rcp.x), fabsf(rcp.y) }, az2 = { fabsf(rcp.z), 0.0f };
@@ -342,18 +122,6 @@ __device__ __forceinline__ uint32_t flat2Pass1(lds_cf4 *flat, uint32_t nFlat, co
             mask |= (tn <= tf) ? pm_to_bits(B.w) : 0u;                                                                                 \
             if (R64) hi |= (tn <= tf) ? pm_to_bits(A.w) : 0u;                                                                          \
         }
-#else
-    const f2v rx = { rcp.x, rcp.x }, ry = { rcp.y, rcp.y }, rz = { rcp.z, rcp.z };
-    const f2v ox = { -(o.x * rcp.x), -(o.x * rcp.x) }, oy = { -(o.y * rcp.y), -(o.y * rcp.y) }, oz = { -(o.z * rcp.z), -(o.z * rcp.z) };
-#define FLAT2_BOX(c_)                                                                                                                  \
-        {                                                                                                                              \
-            const f4v A = flat[2 * (c_)], B = flat[2 * (c_) + 1];                                                                      \
-            const f2v x = __builtin_elementwise_fma(A.xy, rx, ox), y = __builtin_elementwise_fma(A.zw, ry, oy), z = __builtin_elementwise_fma(B.xy, rz, oz); \
-            const float tn = fmaxf(fmaxf(fminf(x.x, x.y), fminf(y.x, y.y)), fmaxf(fminf(z.x, z.y), mint));                             \
-            const float tf = fminf(fminf(fmaxf(x.x, x.y), fmaxf(y.x, y.y)), fminf(fmaxf(z.x, z.y), maxt));                             \
-            mask |= (tn <= tf) ? pm_to_bits(B.z) : 0u;                                                                                 \
-        }
-#endif
     /* groups of four entries (eight LDS broadcasts in flight), then the rest one by one: the Cornell box has 17 leaves -- padded to 20 it paid for three
        boxes no ray can enter, 15 % of a pass that is a third of the traversal */
     const uint32_t nFlat4 = nFlat & ~3u;
@@ -367,71 +135,8 @@ __device__ __forceinline__ uint32_t flat2Pass1(lds_cf4 *flat, uint32_t nFlat, co
     return mask;
 }
 
-template <bool SHADOW>
-__device__ __forceinline__ bool traverseFlat2(lds_cf4 *flat, uint32_t nFlat, lds_cf4 *tris, const V3 &o, const V3 &d, const V3 &rcp,
-                                              float mint, float maxt, TravResult &res, uint32_t &nodeVisits, uint32_t &triTests) {
-    uint32_t mask = flat2Pass1<false>(flat, nFlat, o, rcp, mint, maxt);
-    ++nodeVisits;
-    bool found = false;
-    res.prim = PHIP_NO_HIT; res.t = INFINITY; res.u = res.v = 0;
-#define FLAT2_TEST(a, b, c)                                                                                        \
-    {                                                                                                              \
-        ++triTests;                                                                                                \
-        float tu, tv, tt;                                                                                          \
-        const bool hit = waldIntersectSel(a, b, c, o, d, mint, maxt, tu, tv, tt);                                  \
-        if (SHADOW) {                                                                                              \
-            found = found | hit;                                                                                   \
-            mask = hit ? 0u : mask;                                                                                \
-        } else {                                                                                                   \
-            const bool win = hit & winsTie(tt, pm_to_bits(c.z), res.t, res.prim);                                  \
-            maxt = win ? tt : maxt; res.t = win ? tt : res.t; res.u = win ? tu : res.u; res.v = win ? tv : res.v;  \
-            res.prim = win ? pm_to_bits(c.z) : res.prim;                                                           \
-            found = found | hit;                                                                                   \
-        }                                                                                                          \
-    }
-#if MEGA_WALD_PAIR
-    /* two records per pass of the loop: two independent dependency chains (each Wald test is ~35 dependent instructions behind an LDS round
-       trip, and four waves per SIMD do not cover that).  The second record is judged after the first, against the interval the first may have
-       shortened -- the sequential loop's decisions in the sequential loop's order.  A lane with one record left tests it twice. */
-    while (mask) {
-        const uint32_t i0 = (uint32_t) __builtin_ctz(mask);
-        mask &= mask - 1u;
-        const bool two = mask != 0;
-        const uint32_t i1 = two ? (uint32_t) __builtin_ctz(mask) : i0;
-        mask &= mask - 1u;
-        const float4 a0 = ldsLoad4(tris + 3 * i0), b0 = ldsLoad4(tris + 3 * i0 + 1), c0 = ldsLoad4(tris + 3 * i0 + 2);
-        const float4 a1 = ldsLoad4(tris + 3 * i1), b1 = ldsLoad4(tris + 3 * i1 + 1), c1 = ldsLoad4(tris + 3 * i1 + 2);
-        float u0, v0, t0, u1, v1, t1;
-        const bool h0 = waldIntersectSel(a0, b0, c0, o, d, mint, maxt, u0, v0, t0);
-        bool h1 = two & waldIntersectSel(a1, b1, c1, o, d, mint, maxt, u1, v1, t1);
-        if (SHADOW) {
-            triTests += (two & !h0) ? 2u : 1u;                   /* the sequential loop stops at the first hit */
-            found = found | h0 | h1;
-            mask = (h0 | h1) ? 0u : mask;
-        } else {
-            triTests += two ? 2u : 1u;
-            const bool w0 = h0 & winsTie(t0, pm_to_bits(c0.z), res.t, res.prim);
-            maxt = w0 ? t0 : maxt; res.t = w0 ? t0 : res.t; res.u = w0 ? u0 : res.u; res.v = w0 ? v0 : res.v; res.prim = w0 ? pm_to_bits(c0.z) : res.prim;
-            h1 = h1 & !(t1 > maxt);
-            const bool w1 = h1 & winsTie(t1, pm_to_bits(c1.z), res.t, res.prim);
-            maxt = w1 ? t1 : maxt; res.t = w1 ? t1 : res.t; res.u = w1 ? u1 : res.u; res.v = w1 ? v1 : res.v; res.prim = w1 ? pm_to_bits(c1.z) : res.prim;
-            found = found | h0 | h1;
-        }
-    }
-#else
-    while (mask) {
-        const uint32_t idx = (uint32_t) __builtin_ctz(mask);
-        mask &= mask - 1u;
-        lds_cf4 *t_ = tris + 3 * idx;
-        const float4 a = ldsLoad4(t_), b = ldsLoad4(t_ + 1), c = ldsLoad4(t_ + 2);
-        FLAT2_TEST(a, b, c)
-    }
-#endif
-#undef FLAT2_TEST
-    return found;
-}
 
-/* traverseFlat2 with pass 2 DEALT OVER THE WAVE (k_mega, MEGA_BALANCE).  The per-lane loop above runs for the wave's slowest lane -- about
+/* Pass 2 DEALT OVER THE WAVE.  A per-lane loop `while (mask) test record ffs(mask)` runs for the wave's slowest lane -- about
  * eight Wald tests where the average ray needs 3.1, and in the shadow phase 30 of 64 lanes have no ray at all.  Here the (ray, record) pairs
  * of the whole wave are written to a work list in LDS and every lane tests one pair per step, whoever the ray belongs to:
  *   1. a prefix sum of popcount(mask) over the wave (six DPP steps) gives every lane its segment of the list; it writes (lane << 5 | record)

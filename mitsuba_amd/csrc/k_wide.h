@@ -1,7 +1,6 @@
 /*
  * k_wide.h -- traversal of the compressed 8-wide BVH (bvh.h: buildWide) for the big scenes: k_rays_w (persistent waves with
- * refill; closest-hit and any-hit rays of an iteration in one launch) and k_raycast_w (phip_trace).  Included by phip.hip
- * after k_rays.h, whose ray sources (ShadowSource / TraceSource) it shares.
+ * refill; closest-hit and any-hit rays of an iteration in one launch) and k_raycast_w (phip_trace).  Included by phip.hip.
  *
  * Why a second structure: the BVH4 ray kernel of the 250k-triangle scenes was measured (round 2, SQ counters) at 34 % VALU
  * issue with 64 % of its wave cycles waiting -- every lane of a wave fetches its own node, i.e. 64 different cache lines per
@@ -11,7 +10,7 @@
  * dependent round trips per ray, paid for with ALU work there is room for.
  *
  * Per-lane state machine, as in k_traverse.h: one node step per loop iteration; the triangle tests the lanes of a wave have pending are dealt
- * over the whole wave (round 4: persistentTraverseWide under WIDE_DEAL, below; k_raycast_w keeps one test per lane and iteration).  The traversal stack
+ * over the whole wave (round 4: persistentTraverseWide, below; k_raycast_w keeps one test per lane and iteration).  The traversal stack
  * holds GROUPS, 8 bytes each: a node group (childBase, hit bits 24..31 | imask) or a triangle group (triBase, hit bits 0..23),
  * so a node pushes at most one entry however many of its children are hit and the stack is as deep as the tree (LDS:
  * WIDE_STACK_LDS entries per lane, the rest spills to HBM).  Children are visited in the order slot ^ rayOctant, which the
@@ -21,6 +20,17 @@
 
 #include "k_wide_node.h"
 
+#define INVALID_RAY 0xFFFFFFFFu
+
+/* L[id] += c for an unoccluded NEE entry (no other lane touches L[id] during the ray kernel).  Measured alternatives,
+ * both reverted (HISTORY.md 3.4): three fire-and-forget float atomics (+1..3 % on the big scenes, but the Cornell shadow
+ * kernel doubled), a per-slot accumulator flushed once per sample (k_shade then pays for it).  Scenes that fit LDS avoid
+ * the read-modify-write altogether: k_mega keeps the accumulator in a register. */
+__device__ __forceinline__ void addRadiance(float4 *L, uint32_t id, const float4 &c) {
+    float4 l = L[id];
+    l.x += c.x; l.y += c.y; l.z += c.z;
+    L[id] = l;
+}
 
 /* ---- work distribution of k_rays_w: chunks of 64 slots (closest-hit rays) and blocks of the shadow queue are DRAWN from sharded
  *      counters instead of being dealt statically (wave w: chunks w, w + W, ...).  Rays differ in cost by an order of magnitude, so
@@ -125,24 +135,12 @@ struct ShadowSourceDyn {
 };
 
 
-/* ---- persistent waves with refill: closest-hit AND any-hit rays of one iteration in ONE launch (as k_rays_p) ----
+/* ---- persistent waves with refill: closest-hit AND any-hit rays of one iteration in ONE launch ----
  * Per-lane state is kept small (the kernel's speed follows its resident waves: it is bound by memory latency and by the CU's
  * vector-memory path, WIDE_WAVES): `steps` = node steps | triangle tests << 16 of the ray in flight, the hit word carries the shade
- * class, the any-hit flag is a lane mask.  (nested variant below: `meta` = handle | any-hit flag << 31) */
+ * class, the any-hit flag is a lane mask. */
 enum { WW_RAYS = 0, WW_STEPS, WW_SH_RAYS, WW_SH_STEPS, WW_COUNT };     /* 64-bit LDS counters of a wave: rays, node steps | triangle tests << 32 */
-#define WM_HANDLE 0x0FFFFFFFu
-#define WM_SHADOW 0x80000000u
-#ifndef WIDE_FLAT
-#ifndef WIDE_WALD_SEL
-#define WIDE_WALD_SEL 1                  /* the Wald test's axis permutation as selects (k_traverse.h: waldIntersectSel) instead of three divergent branches */
-#endif
-#define WIDE_FLAT 1                      /* ONE loop (refill test, then one traversal iteration of the live lanes) instead of a traversal loop nested in a refill loop */
-#endif
-#ifndef WIDE_DEAL
-#define WIDE_DEAL 1                      /* the triangle tests of an iteration dealt over the lanes of the wave (0: the flat loop, one record per lane and iteration) */
-#endif
-#if WIDE_DEAL
-/* The flat loop below tests ONE Wald record per lane and iteration: a ray that entered leaves with four triangles stays four iterations
+/* A loop that tests ONE Wald record per lane and iteration (rounds 2-3; HISTORY.md) keeps a ray that entered leaves with four triangles for four iterations
  * before it may take its next node step, while every iteration executes the node block AND the triangle block for whoever needs them
  * (tools/wave_sim.py: 45 of 64 lanes in a node block, 21 in a triangle block).  Here the pending (ray, record) pairs of the whole wave go
  * to a work list in LDS and every lane tests one pair per step, as k_mega does (k_traverse.h: traverseFlat2W): all the triangles a ray has
@@ -190,7 +188,7 @@ __device__ __forceinline__ void persistentTraverseWide(const DevScene &S, WideSt
                 }
             }
         } else if (idle == ~0ull) break;
-        if (active && tg.y == 0u && (ng.y & 0xff000000u)) { constexpr bool wideCullOn = true; (void) wideCullOn; WIDE_NODE_STEP(stack, S, ray, ng, tg, steps) }   /* (any-hit rays carry the bound too: their interval never shrinks, so it never culls -- a lane-varying switch costs more) */
+        if (active && tg.y == 0u && (ng.y & 0xff000000u)) WIDE_NODE_STEP(stack, S, ray, ng, tg, steps)
 
         /* ---- the triangle round: every lane takes part ---- */
         const uint32_t pending = active ? tg.y : 0u;
@@ -263,8 +261,8 @@ __device__ __forceinline__ void persistentTraverseWide(const DevScene &S, WideSt
             if (!finished && tg.y == 0u && !(ng.y & 0xff000000u)) {
                 if (stack.sp == 0) finished = true;
                 else {
-                    uint2 e = stack.pop();
-                    if (e.y & 0xff000000u) { WIDE_CULL_POP(e, ray) ng = e; } else { tg = e; ng = make_uint2(0u, 0u); }
+                    const uint2 e = stack.pop();
+                    if (e.y & 0xff000000u) ng = e; else { tg = e; ng = make_uint2(0u, 0u); }
                 }
             }
             if (finished) {
@@ -287,188 +285,6 @@ __device__ __forceinline__ void persistentTraverseWide(const DevScene &S, WideSt
         }
     }
 }
-#elif !PHIP_EXPERIMENTS
-#error "WIDE_DEAL=0 (the flat / nested loops of rounds 2-3) is an experiment build: add -DPHIP_EXPERIMENTS=1"
-#elif WIDE_FLAT
-/* The loop is flat: every pass tests the refill condition (two scalar instructions on the ballot of the idle lanes) and then runs one
-   traversal iteration -- one node step, one triangle test, one pop -- for the lanes that have a ray.  The nested form (an inner loop the
-   live lanes stay in until enough of them have finished) made the compiler keep two register images of the lane state, one per loop,
-   and copy between them at every entry and exit; flat, the state has one home and the kernel fits 96 VGPRs (5 waves per SIMD)
-   without spilling. */
-__device__ __forceinline__ void persistentTraverseWide(const DevScene &S, WideStackT<WIDE_BLOCK> &stack, ShadowSourceDyn &ss, TraceSourceDyn &ts,
-                                                       unsigned long long *wc /* LDS: WC_COUNT counters of this wave */) {
-    bool active = false, shadow = false;
-    uint32_t handle = 0, steps = 0;
-    WideRay ray; ray.o = ray.d = ray.rcp = V3(0.0f); ray.mint = ray.maxt = 0; ray.octinv4 = 0;
-    uint2 ng = make_uint2(0u, 0u), tg = make_uint2(0u, 0u);
-    TravResult res; res.prim = PHIP_NO_HIT; res.t = INFINITY; res.u = res.v = 0;
-    for (;;) {
-        const unsigned long long idle = __ballot(!active);
-        const bool moreS = ss.more(), moreAny = moreS || ts.more();              /* wave-uniform */
-        if (moreAny) {
-            if (__popcll(idle) >= REFILL_LANES) {
-                const uint32_t h = moreS ? ss.assign(!active, idle) : ts.assign(!active, idle);
-                if (!active && h != INVALID_RAY) {
-                    V3 o, d; float mint, maxt;                   /* (already clipped to the scene box) */
-                    const bool ok = moreS ? ss.load(h, o, d, mint, maxt) : ts.load(h, o, d, mint, maxt);
-                    if (ok) {
-                        const unsigned long long got = __ballot(1);
-                        if (__lane_id() == (uint32_t) __ffsll((long long) got) - 1u) wc[moreS ? WW_SH_RAYS : WW_RAYS] += (uint32_t) __popcll(got);
-                        res.prim = PHIP_NO_HIT; res.t = INFINITY; res.u = res.v = 0;
-                        if (maxt > mint) {
-                            wideRaySetup(ray, o, d, V3(slabRcpFast(d.x), slabRcpFast(d.y), slabRcpFast(d.z)), mint, maxt);
-                            ng = wideRootGroup(); tg = make_uint2(0u, 0u);
-                            stack.sp = 0; handle = h; shadow = moreS; active = true; steps = 0;
-                        } else if (moreS) {
-                            ss.commit(h, false, res);
-                        } else {
-                            ts.commit(h, false, res);
-                        }
-                    }
-                }
-            }
-        } else if (idle == ~0ull) break;
-        if (active) {
-            /* one node step and one triangle test per iteration */
-            { constexpr bool wideCullOn = false; (void) wideCullOn;        /* (WIDE_CULL: the dealt loop only -- ADVICE r5: the macro names it in every loop) */
-              if (tg.y == 0u && (ng.y & 0xff000000u)) WIDE_NODE_STEP(stack, S, ray, ng, tg, steps) }
-            bool finished = false;
-            if (tg.y) {
-                const uint32_t bit = (uint32_t) __ffs((int) tg.y) - 1u;
-                tg.y &= tg.y - 1u;
-                WIDE_LOAD_TRI(S, tg.x + bit, a, b, c)
-                steps += 0x10000u;
-                float tu, tv, tt;
-                if (WIDE_WALD_SEL ? waldIntersectSel(a, b, c, ray.o, ray.d, ray.mint, ray.maxt, tu, tv, tt) : waldIntersect(a, b, c, ray.o, ray.d, ray.mint, ray.maxt, tu, tv, tt)) {
-                    if (shadow) { res.prim = 0; finished = true; }
-                    else if (winsTie(tt, pm_to_bits(c.z), res.t, res.prim & HIT_PRIM_MASK)) {      /* (res.prim is the packed hit word: one register for primitive and class) */
-                        ray.maxt = tt; res.t = tt; res.u = tu; res.v = tv; res.prim = pm_to_bits(c.z) | (pm_to_bits(c.w) << HIT_CLASS_SHIFT);
-                    }
-                }
-            }
-            if (!finished && tg.y == 0u && !(ng.y & 0xff000000u)) {
-                if (stack.sp == 0) finished = true;
-                else {
-                    const uint2 e = stack.pop();
-                    if (e.y & 0xff000000u) ng = e; else { tg = e; ng = make_uint2(0u, 0u); }
-                }
-            }
-            if (finished) {
-                if (shadow) ss.commit(handle, res.prim != PHIP_NO_HIT, res);
-                else ts.commit(handle, false, res);
-                /* node steps (low word) and triangle tests (high word) of the ray in ONE 64-bit LDS add */
-                atomicAdd(&wc[shadow ? WW_SH_STEPS : WW_STEPS], (unsigned long long) (steps & 0xFFFFu) | ((unsigned long long) (steps >> 16) << 32));
-                active = false;
-            }
-        }
-    }
-}
-#else
-__device__ __forceinline__ void persistentTraverseWide(const DevScene &S, WideStackT<WIDE_BLOCK> &stack, ShadowSourceDyn &ss, TraceSourceDyn &ts,
-                                                       unsigned long long *wc /* LDS: WC_COUNT counters of this wave */) {
-    bool active = false;
-    uint32_t meta = 0, steps = 0;
-    WideRay ray; ray.o = ray.d = ray.rcp = V3(0.0f); ray.mint = ray.maxt = 0; ray.octinv4 = 0;
-    uint2 ng = make_uint2(0u, 0u), tg = make_uint2(0u, 0u);
-    TravResult res; res.prim = PHIP_NO_HIT; res.t = INFINITY; res.u = res.v = 0;
-
-#if WIDE_PROFILE
-    /* measurement build: wave clock spent in the refill branch, refills, loop iterations (reported in the rows of the any-hit
-       counters, which this build therefore falsifies) */
-    unsigned long long pfRefill = 0, pfAssign = 0, pfLoad = 0, pfStart = clock64(); uint32_t pfRefills = 0, pfIters = 0;
-#endif
-    for (;;) {
-        const unsigned long long idle = __ballot(!active);
-        const bool moreS = ss.more(), moreAny = moreS || ts.more();              /* wave-uniform */
-        if (idle && moreAny && (__popcll(idle) >= REFILL_LANES || idle == ~0ull)) {
-#if WIDE_PROFILE
-            const unsigned long long pf0 = clock64(); ++pfRefills;
-#endif
-            const uint32_t h = moreS ? ss.assign(!active, idle) : ts.assign(!active, idle);
-#if WIDE_PROFILE
-            __builtin_amdgcn_s_waitcnt(0); const unsigned long long pf1 = clock64(); pfAssign += pf1 - pf0;
-#endif
-            if (!active && h != INVALID_RAY) {
-                V3 o, d; float mint, maxt;                   /* (already clipped to the scene box) */
-                const bool ok = moreS ? ss.load(h, o, d, mint, maxt) : ts.load(h, o, d, mint, maxt);
-#if WIDE_PROFILE
-                __builtin_amdgcn_s_waitcnt(0); pfLoad += clock64() - pf1;
-#endif
-                if (ok) {
-                    const unsigned long long got = __ballot(1);
-                    if (__lane_id() == (uint32_t) __ffsll((long long) got) - 1u) wc[moreS ? WW_SH_RAYS : WW_RAYS] += (uint32_t) __popcll(got);
-                    res.prim = PHIP_NO_HIT; res.t = INFINITY; res.u = res.v = 0;
-                    if (maxt > mint) {
-                        wideRaySetup(ray, o, d, V3(slabRcpFast(d.x), slabRcpFast(d.y), slabRcpFast(d.z)), mint, maxt);
-                        ng = wideRootGroup(); tg = make_uint2(0u, 0u);
-                        stack.sp = 0; meta = h | (moreS ? WM_SHADOW : 0u); active = true; steps = 0;
-                    } else if (moreS) {
-                        ss.commit(h, false, res);
-                    } else {
-                        ts.commit(h, false, res);
-                    }
-                }
-            }
-#if WIDE_PROFILE
-            __builtin_amdgcn_s_waitcnt(0); pfRefill += clock64() - pf0;
-#endif
-        }
-        if (!__any(active)) { if (!(ss.more() || ts.more())) break; continue; }
-        if (active) {
-            for (;;) {
-#if WIDE_PROFILE
-                if (__builtin_amdgcn_readfirstlane(__lane_id()) == __lane_id()) ++pfIters;
-#endif
-                /* one node step and one triangle test per iteration */
-                { constexpr bool wideCullOn = false; (void) wideCullOn;
-                  if (tg.y == 0u && (ng.y & 0xff000000u)) WIDE_NODE_STEP(stack, S, ray, ng, tg, steps) }
-                bool finished = false;
-                if (tg.y) {
-                    const uint32_t bit = (uint32_t) __ffs((int) tg.y) - 1u;
-                    tg.y &= tg.y - 1u;
-                    WIDE_LOAD_TRI(S, tg.x + bit, a, b, c)
-                    steps += 0x10000u;
-                    float tu, tv, tt;
-                    if (waldIntersect(a, b, c, ray.o, ray.d, ray.mint, ray.maxt, tu, tv, tt)) {
-                        if (meta & WM_SHADOW) { res.prim = 0; finished = true; }
-                        else if (winsTie(tt, pm_to_bits(c.z), res.t, res.prim & HIT_PRIM_MASK)) {      /* (res.prim is the packed hit word: one register for primitive and class) */
-                            ray.maxt = tt; res.t = tt; res.u = tu; res.v = tv; res.prim = pm_to_bits(c.z) | (pm_to_bits(c.w) << HIT_CLASS_SHIFT);
-                        }
-                    }
-                }
-                if (!finished && tg.y == 0u && !(ng.y & 0xff000000u)) {
-                    if (stack.sp == 0) finished = true;
-                    else {
-                        const uint2 e = stack.pop();
-                        if (e.y & 0xff000000u) ng = e; else { tg = e; ng = make_uint2(0u, 0u); }
-                    }
-                }
-                if (finished) {
-                    const bool shadow = (meta & WM_SHADOW) != 0;
-                    if (shadow) ss.commit(meta & WM_HANDLE, res.prim != PHIP_NO_HIT, res);
-                    else ts.commit(meta & WM_HANDLE, false, res);
-                    /* node steps (low word) and triangle tests (high word) of the ray in ONE 64-bit LDS add */
-                    atomicAdd(&wc[shadow ? WW_SH_STEPS : WW_STEPS], (unsigned long long) (steps & 0xFFFFu) | ((unsigned long long) (steps >> 16) << 32));
-                    active = false;
-                    break;
-                }
-                if ((ss.more() || ts.more()) && __popcll(__ballot(1)) <= 64 - REFILL_LANES) break;     /* enough idle lanes: refill */
-            }
-        }
-    }
-#if WIDE_PROFILE
-    {
-        const unsigned long long tot = clock64() - pfStart;
-        uint32_t it = pfIters;
-        for (int off = 32; off > 0; off >>= 1) it += __shfl_down(it, off);          /* one lane per iteration counted: the sum is the wave's iterations */
-        uint32_t ld = (uint32_t) pfLoad;
-        for (int off = 32; off > 0; off >>= 1) { const uint32_t o_ = __shfl_down(ld, off); ld = o_ > ld ? o_ : ld; }      /* the lane that waited longest */
-        if (__lane_id() == 0) { wc[WW_SH_STEPS] = (pfRefill & 0xFFFFFFFFull) | (tot << 32); wc[WW_SH_RAYS] = pfRefills; wc[WW_STEPS] = (unsigned long long) (uint32_t) pfAssign | ((unsigned long long) it << 32); wc[WW_RAYS] = ld; }
-    }
-#endif
-}
-
-#endif  /* WIDE_FLAT */
 
 __global__ __launch_bounds__(WIDE_BLOCK, WIDE_WAVES) void k_rays_w(DevScene S, PathPool P, float4 *L, unsigned int *drawCounters /* 2 * RAY_SHARDS lines, zeroed */) {
     __shared__ unsigned long long wcnt[WIDE_BLOCK / 64][WW_COUNT];
@@ -481,11 +297,7 @@ __global__ __launch_bounds__(WIDE_BLOCK, WIDE_WAVES) void k_rays_w(DevScene S, P
     ss.q.init(drawCounters, blockIdx.x % RAY_SHARDS, nBlk, waveId, nWavesGrid);
     ts.q.init(drawCounters + RAY_SHARDS * RAY_SHARD_STRIDE, blockIdx.x % RAY_SHARDS, nChunk, waveId, nWavesGrid);
     ss.start(); ts.start();
-#if WIDE_DEAL
     persistentTraverseWide(S, stk, ss, ts, wcnt[wave], g_smem + wideLdsBytes(S.wideNodeCache, WIDE_BLOCK) + wave * WD_WAVE_BYTES);
-#else
-    persistentTraverseWide(S, stk, ss, ts, wcnt[wave]);
-#endif
     if (__lane_id() == 0) {
         const unsigned long long v[6] = { wcnt[wave][WW_RAYS], wcnt[wave][WW_STEPS] & 0xFFFFFFFFull, wcnt[wave][WW_STEPS] >> 32,
                                           wcnt[wave][WW_SH_RAYS], wcnt[wave][WW_SH_STEPS] & 0xFFFFFFFFull, wcnt[wave][WW_SH_STEPS] >> 32 };

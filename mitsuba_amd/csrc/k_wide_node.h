@@ -6,7 +6,7 @@
 #pragma once
 
 #ifndef WIDE_STACK_LDS
-#define WIDE_STACK_LDS 6                 /* 8-byte entries per lane in LDS (12 KB per block of 256; nine until the triangle rounds of WIDE_DEAL took 6 KB per block: measured the same, 153.2 ms per C3 frame either way) */
+#define WIDE_STACK_LDS 6                 /* 8-byte entries per lane in LDS (12 KB per block of 256; nine until the dealt triangle rounds took 6 KB per block: measured the same, 153.2 ms per C3 frame either way) */
 #endif
 #ifndef WIDE_BLOCK
 #define WIDE_BLOCK 256                   /* threads per block of k_rays_w.  Measured (round 2): ONE block of 1024 per CU, whose LDS then holds a single copy of the
@@ -19,27 +19,11 @@
 #define WIDE_NODE_CACHE_MAX 48           /* top-of-tree nodes (BFS order) staged in LDS by k_rays_w: 3.75 KB per block */
 #endif
 #define WIDE_NODE_CACHE_RAYCAST 64       /* ... by k_raycast_w (blocks of 256, several per CU) */
-#ifndef WIDE_TYPED
-#define WIDE_TYPED 1                     /* cached nodes are read with ds_read_b128 (LDS pipe) instead of flat_load (which sends LDS addresses through the
-                                            texture addresser / data path the kernel is bound by: TD busy 95 %, round-2 counters) */
-#endif
 #ifndef WIDE_NODE_STRIDE
 #define WIDE_NODE_STRIDE 5               /* uint4 per node in HBM: 5 = packed 80-byte nodes (half of them straddle two 128-byte lines), 8 = one node per 128-byte line */
 #endif
-#ifndef WIDE_DUMMY_LOADS
-#define WIDE_DUMMY_LOADS 0               /* measurement: extra 16-byte loads of the node's own line per node step (L1 hits): what does one more vector-memory instruction cost? */
-#endif
-#ifndef WIDE_DUMMY_VALU
-#define WIDE_DUMMY_VALU 0                /* measurement: extra VALU instructions per node step (independent v_fma_f32 on a scratch register): what does the ALU work cost? */
-#endif
 #ifndef WIDE_PROFILE
 #define WIDE_PROFILE 0
-#endif
-#ifndef WIDE_CULL
-#define WIDE_CULL 0                      /* experiment (round 5): a node group carries, in the 16 free bits of its hit word, the entry distance (rounded down to
-                                            bfloat16) of the child that is visited SECOND; when the group is popped and a hit found meanwhile lies in front of it, that child
-                                            is skipped without fetching its node.  (The entry distance of the node that pushed the group cannot cull: every hit found between
-                                            push and pop lies inside that node.)  ~30 VALU per node step with two or more inner hits, closest-hit rays only. */
 #endif
 #ifndef WIDE_WAVES
 #define WIDE_WAVES 7                     /* waves per SIMD of k_rays_w = blocks of 256 per CU.  Round 3: 74 VGPRs (flat loop, wave-uniform state in SGPRs, stack
@@ -47,7 +31,7 @@
                                             ms per frame: nested loop at 4 waves (110 VGPRs) 191.8 / 385.4 -- flat loop at 4 waves 188.7 / 376.6 -- 5 waves
                                             169.1 / 343.0 -- 6 waves 158.9 / 327.5 -- 7 waves (72 VGPRs, 9-entry stack, 48-node cache) 167.0 / 336.9 -- 8 waves
                                             (64 VGPRs + 52 B of scratch) 241.0 / 488.3.  Round 4: with the Wald test's axis permutation as selects
-                                            (WIDE_WALD_SEL) the kernel needs 64 VGPRs without scratch, and the seventh wave pays (profiles/r04_gpu_call_e_*):
+                                            (waldIntersectSel) the kernel needs 64 VGPRs without scratch, and the seventh wave pays (profiles/r04_gpu_call_e_*):
                                             branches, 6 waves 159.3 / 327.5 -- selects, 6 waves 156.1 / 321.6 -- 7 waves (9-entry stack, 48-node cache)
                                             152.6 / 317.1 -- 8 waves (8-entry stack, 32-node cache) 155.6 / 323.5.  Its 91 SGPRs admit 7 blocks per CU (MI355X
                                             guide: 82..96 SGPRs -> 7), 7 x (18 KB stack + 3.75 KB node cache) fit the CU's 160 KB of LDS.
@@ -93,10 +77,7 @@ typedef WideStackT<BLOCK> WideStack;
 __host__ __device__ __forceinline__ size_t wideLdsBytes(uint32_t nodeCache, uint32_t blockThreads) {
     return (size_t) WIDE_STACK_LDS * blockThreads * sizeof(uint2) + (size_t) nodeCache * 5 * sizeof(uint4);
 }
-#ifndef WIDE_DEAL
-#define WIDE_DEAL 1
-#endif
-__host__ __device__ __forceinline__ size_t wideDealBytes(uint32_t blockThreads) { return WIDE_DEAL ? (size_t) (blockThreads / 64u) * (64u * 8u + 64u * 8u + 256u * 2u) : 0; }   /* k_rays_w: WD_WAVE_BYTES per wave */
+__host__ __device__ __forceinline__ size_t wideDealBytes(uint32_t blockThreads) { return (size_t) (blockThreads / 64u) * (64u * 8u + 64u * 8u + 256u * 2u); }   /* k_rays_w: WD_WAVE_BYTES per wave */
 __host__ __device__ __forceinline__ uint32_t wideRaycastCache(uint32_t nodeCache) { return nodeCache < WIDE_NODE_CACHE_RAYCAST ? nodeCache : WIDE_NODE_CACHE_RAYCAST; }
 
 /* carve the block's dynamic LDS and stage the top of the tree (all threads of the block must call) */
@@ -126,10 +107,7 @@ DV float ubyte(uint32_t v, int k) { return (float) ((v >> (8 * k)) & 0xffu); }  
 
 /* One node: slab test of the eight quantised child boxes.  Returns the hit bits: 24..31 inner children in traversal order
    (highest bit = first), 0..23 the leaf triangles of the hit leaves. */
-/* WIDE_CULL: *second = (priority << 16 | bfloat16(entry distance, rounded down)) of the hit inner child that is visited SECOND (0: fewer than two) -- the two
-   largest keys of the eight children, kept with a max and a median per child */
-DV uint32_t wideNodeHits(const uint4 &n0, const uint4 &n1, const uint4 &n2, const uint4 &n3, const uint4 &n4, const WideRay &r, uint32_t *second = nullptr) {
-    uint32_t key1 = 0, key2 = 0;
+DV uint32_t wideNodeHits(const uint4 &n0, const uint4 &n1, const uint4 &n2, const uint4 &n3, const uint4 &n4, const WideRay &r) {
     /* child box plane = p + q * 2^(e-127): t = q * (2^e * rcp) + (p - o) * rcp */
     const float sx = pm_from_bits((n0.w & 0xffu) << 23) * r.rcp.x, sy = pm_from_bits(((n0.w >> 8) & 0xffu) << 23) * r.rcp.y,
                 sz = pm_from_bits(((n0.w >> 16) & 0xffu) << 23) * r.rcp.z;
@@ -139,12 +117,6 @@ DV uint32_t wideNodeHits(const uint4 &n0, const uint4 &n1, const uint4 &n2, cons
     const uint32_t lox[2] = { n2.x, n2.y }, loy[2] = { n2.z, n2.w }, loz[2] = { n3.x, n3.y }, hix[2] = { n3.z, n3.w }, hiy[2] = { n4.x, n4.y }, hiz[2] = { n4.z, n4.w };
     const uint32_t meta[2] = { n1.z, n1.w };
     uint32_t hits = 0;
-#if WIDE_DUMMY_VALU && defined(__HIP_DEVICE_COMPILE__)
-    { float dv_ = sx;
-#pragma unroll
-      for (int i_ = 0; i_ < WIDE_DUMMY_VALU; ++i_) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(dv_) : "v"(sy), "v"(sz));
-      asm volatile("" :: "v"(dv_)); }
-#endif
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -169,34 +141,20 @@ DV uint32_t wideNodeHits(const uint4 &n0, const uint4 &n1, const uint4 &n2, cons
             const float tf = fminf(fminf(tfx, tfy), fminf(tfz, r.maxt));
             const uint32_t bits = (childBits4 >> (8 * k)) & 0xffu, idx = (bitIndex4 >> (8 * k)) & 0xffu;
             hits |= (tn <= tf) ? (bits << idx) : 0u;
-#if WIDE_CULL
-            if (second) {
-                const uint32_t key = (tn <= tf && idx >= 24u) ? ((idx << 16) | (pm_to_bits(tn) >> 16)) : 0u;     /* (tn >= mint >= 0: truncation rounds down) */
-                const uint32_t lo = key1 < key ? key1 : key, hi2 = key2 > lo ? key2 : lo;
-                key2 = hi2; key1 = key1 > key ? key1 : key;
-            }
-#endif
         }
     }
-#if WIDE_CULL
-    if (second) *second = key2;
-#endif
-    (void) key1; (void) key2;
     return hits;
 }
 
 __device__ __forceinline__ uint4 ldsLoadU4(lds_cu4 *p) { const u4v v = *p; return make_uint4(v.x, v.y, v.z, v.w); }
 #define WIDE_LOAD_NODE(stack, S, idx, n0, n1, n2, n3, n4)                                             \
     uint4 n0, n1, n2, n3, n4;                                                                         \
-    if (WIDE_TYPED && (idx) < (stack).nodeCache) {                                                    \
+    if ((idx) < (stack).nodeCache) {               /* ds_read_b128: a flat_load would send LDS addresses through the texture addresser the kernel is bound by */ \
         lds_cu4 *l_ = (stack).nodes + 5u * (idx);                                                     \
         n0 = ldsLoadU4(l_); n1 = ldsLoadU4(l_ + 1); n2 = ldsLoadU4(l_ + 2); n3 = ldsLoadU4(l_ + 3); n4 = ldsLoadU4(l_ + 4); \
     } else {                                                                                          \
-        const uint4 *g_ = (!WIDE_TYPED && (idx) < (stack).nodeCache) ? (const uint4 *) ((stack).nodes + 5u * (idx)) : (S).wnodes + WIDE_NODE_STRIDE * (size_t) (idx); \
+        const uint4 *g_ = (S).wnodes + WIDE_NODE_STRIDE * (size_t) (idx);                             \
         n0 = g_[0]; n1 = g_[1]; n2 = g_[2]; n3 = g_[3]; n4 = g_[4];                                   \
-        for (int dl_ = 0; dl_ < WIDE_DUMMY_LOADS; ++dl_) {                                            \
-            f4v dv_; asm volatile("global_load_dwordx4 %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=&v"(dv_) : "v"(g_) : "memory"); asm volatile("" :: "v"(dv_)); \
-        }                                                                                             \
     }
 
 /* a Wald record = three 16-byte loads.  Written as inline assembly: the compiler narrows the loads to the eleven dwords in use
@@ -223,22 +181,10 @@ __device__ __forceinline__ uint4 ldsLoadU4(lds_cu4 *p) { const u4v v = *p; retur
         const uint32_t idx_ = (ng).x + (uint32_t) __popc((ng).y & ((1u << slot_) - 1u) & 0xffu);      \
         WIDE_LOAD_NODE(stack, S, idx_, n0, n1, n2, n3, n4)                                            \
         ++nodeVisits;                                                                                 \
-        uint32_t second_ = 0u;                                                                        \
-        const uint32_t hits_ = wideNodeHits(n0, n1, n2, n3, n4, ray, (WIDE_CULL && wideCullOn) ? &second_ : nullptr); \
-        (ng) = make_uint2(n1.x, (hits_ & 0xff000000u) | (n0.w >> 24) | ((second_ & 0xffffu) << 8));   \
+        const uint32_t hits_ = wideNodeHits(n0, n1, n2, n3, n4, ray);                                 \
+        (ng) = make_uint2(n1.x, (hits_ & 0xff000000u) | (n0.w >> 24));                                \
         (tg) = make_uint2(n1.y, hits_ & 0x00ffffffu);                                                 \
     }
-#if WIDE_CULL
-/* a popped node group: skip its next child when that child's entry lies behind the closest hit so far; the bound has then served */
-#define WIDE_CULL_POP(e, ray)                                                                         \
-        {                                                                                             \
-            if (pm_from_bits(((e).y & 0x00ffff00u) << 8) > (ray).maxt) (e).y &= ~(0x80000000u >> __clz((int) (e).y)); \
-            (e).y &= 0xff0000ffu;                                                                     \
-        }
-#else
-#define WIDE_CULL_POP(e, ray)
-#endif
-
 /* the root: node 0 is entered as the only child of a virtual group (child base 0, no inner slots below it: rank 0) */
 __device__ __forceinline__ uint2 wideRootGroup() { return make_uint2(0u, 0x80000000u); }
 
@@ -250,7 +196,6 @@ __device__ __forceinline__ bool traverseWide(const DevScene &S, const V3 &o, con
     stack.sp = 0;
     uint2 ng = wideRootGroup(), tg = make_uint2(0u, 0u);
     bool found = false;
-    constexpr bool wideCullOn = false; (void) wideCullOn;        /* (WIDE_CULL: the persistent kernel only) */
     res.prim = PHIP_NO_HIT; res.t = INFINITY; res.u = res.v = 0;
     for (;;) {
         if (tg.y == 0u && (ng.y & 0xff000000u)) WIDE_NODE_STEP(stack, S, ray, ng, tg, nodeVisits)
@@ -275,13 +220,13 @@ __device__ __forceinline__ bool traverseWide(const DevScene &S, const V3 &o, con
     return found;
 }
 
-/* ---- the dealt triangle rounds (k_wide.h: persistentTraverseWide; k_wide_wave.h: traceWideW): thresholds and the per-wave LDS buffers ---- */
+/* ---- the dealt triangle rounds (k_wide.h: persistentTraverseWide): thresholds and the per-wave LDS buffers ---- */
 #ifndef WD_THRESHOLD
 #define WD_THRESHOLD 32u                 /* pairs that must be pending before a round runs (0: every iteration that has any).  Ray kernel, C3 at 64 spp / C4 at 128 spp:
                                             flat loop 153.4 / 318.5 ms -- dealt, threshold 0: 148.3 / 306.7 -- 24: 143.6 / 293.4 -- 40: 143.7 / 292.9 -- 56: 149.0 / 302.2 */
 #endif
 #ifndef WD_REFILL
-#define WD_REFILL 8                      /* idle lanes at which the wave fetches new rays (the flat loop: REFILL_LANES = 16; here 8 / 16 / 24 measured 140.5 / 142.0 / 149.0 ms per C3 frame) */
+#define WD_REFILL 8                      /* idle lanes at which the wave fetches new rays (8 / 16 / 24 measured 140.5 / 142.0 / 149.0 ms per C3 frame) */
 #endif
 #define WD_CAP 256u                      /* list entries per wave (a multiple of 64); lanes whose pairs do not fit wait for the next iteration */
 #define WD_WAVE_BYTES (64u * 8u + 64u * 8u + WD_CAP * 2u)

@@ -1,170 +1,33 @@
 /*
- * k_wide_wave.h -- traceWideW: the rays of a wave's 64 paths traversed TO COMPLETION on the compressed 8-wide tree (k_wide_node.h), inside the fused
+ * k_wide_wave.h -- traceWidePool: the rays of a wave's 64 paths traversed TO COMPLETION on the compressed 8-wide tree (k_wide_node.h), inside the fused
  * kernel (k_mega<.., FLAT = 4 / 5, ..>: scenes whose tree does not fit LDS -- round 6).
  *
  * k_rays_w (k_wide.h) is a ray SERVER: persistent waves fetch rays from the pool in HBM, refill their idle lanes, and write hits back -- the wavefront's
  * ~350 B of path state per vertex and three launches per iteration are what a scene of 1 000 triangles pays 3.2 x for against the LDS-resident boxes
  * (profiles/r05_gpu_call_w_*), not its traversal (2.1 - 2.6 node steps per ray on a tree that lives in L2).  Here the rays never leave the registers of the lane
  * that owns the path: every lane brings up to two rays -- the shadow ray of the vertex it has just shaded and the next ray of its path (sahkdtree3.h:178-308
- * answers both) -- and the wave runs k_rays_w's flat loop until all of them are decided:
- *   - one node step per iteration for the lanes that have one to take (WIDE_NODE_STEP: five 16-byte loads, the top of the tree from the block's LDS cache);
- *   - the Wald tests the wave has pending dealt over its lanes through a work list in LDS (the same round as persistentTraverseWide: smallest t, at equal
- *     t the highest triangle index -- winsTie -- whatever the order; any-hit: the first hit in group order, so the work counters are those of the
- *     sequential loop);
- *   - a lane whose shadow ray is decided starts its second ray in the next iteration WITHOUT waiting for the wave: the "refill" of k_rays_w, from the lane's
- *     own registers.  One traversal phase per path vertex instead of two: the wave waits for its slowest lane once, and a lane with a short shadow ray and a
- *     long next ray (or the reverse) evens out.
+ * answers both) -- and the wave works until all of them are decided.
  * Rays arrive clipped to the scene box (k_clip.h: the reference's arithmetic, IEEE divisions); the slab reciprocal is v_rcp_f32 (slabRcpFast: boxes are
  * conservative, the hit is decided by the Wald test on (o, d, mint', maxt')).  Every lane of the wave must call, converged.
  */
 #pragma once
 
-/* bytes of dynamic LDS of a block of k_mega<.., FLAT >= 4, ..>: [group stack | top-of-tree node cache | the four waves' round buffers | S-box (mailbox builds) |
-   emitter table | materials (FLAT 4)] -- phip.hip sizes the launch with it, k_mega carves it */
-__host__ __device__ __forceinline__ size_t megaWideDealOffset(uint32_t nodeCache) { return wideLdsBytes(nodeCache, BLOCK); }
-__host__ __device__ __forceinline__ size_t megaWideLdsBytesOf(const DevScene &S, uint32_t nodeCache, bool mailbox, bool matsInLds, size_t sboxBytes) {
-    return megaWideDealOffset(nodeCache) + (size_t) (BLOCK / 64u) * WD_WAVE_BYTES + (mailbox ? sboxBytes : 0)
-         + (size_t) ((S.emitterTabSize + 3u) & ~3u) * sizeof(float) + (matsInLds ? (size_t) S.nMaterials * sizeof(DevMaterial) : 0) + 16;
-}
-
-template <bool HAVE_S, bool HAVE_C>
-__device__ __forceinline__ void traceWideW(const DevScene &S, WideStackT<BLOCK> &stack, unsigned char *dealLds /* WD_WAVE_BYTES of this wave */, const uint32_t lane,
-                                           bool goS, const V3 &oS, const V3 &dS, const float mintS, const float maxtS,      /* the any-hit ray, clipped */
-                                           bool goC, const V3 &oC, const V3 &dC, const float mintC, const float maxtC,      /* the closest-hit ray, clipped */
-                                           bool &occluded, TravResult &res,
-                                           unsigned long long *wcS, unsigned long long *wcC /* LDS, per wave: node steps | triangle tests << 32 of its any-hit / closest-hit rays (as k_rays_w) */) {
-    lds_w64 *slot = (lds_w64 *) dealLds; lds_u2 *uvs = (lds_u2 *) (dealLds + 64u * 8u); lds_w16 *list = (lds_w16 *) (dealLds + 2u * 64u * 8u);
-    bool active = false, shadow = false;
-    uint32_t steps = 0;
-    WideRay ray; ray.o = ray.d = ray.rcp = V3(0.0f); ray.mint = ray.maxt = 0; ray.octinv4 = 0;
-    uint2 ng = make_uint2(0u, 0u), tg = make_uint2(0u, 0u);
-    occluded = false;
-    res.prim = PHIP_NO_HIT; res.t = INFINITY; res.u = res.v = 0; res.cls = 0;
-    if (!HAVE_S) goS = false;
-    if (!HAVE_C) goC = false;
-    for (;;) {
-        /* ---- a lane without a ray in flight starts the next one it brought: the shadow ray first ---- */
-        if (!active && (goS || goC)) {
-            const bool s = HAVE_S && goS;
-            const V3 o = (HAVE_S && HAVE_C) ? (s ? oS : oC) : (HAVE_S ? oS : oC), d = (HAVE_S && HAVE_C) ? (s ? dS : dC) : (HAVE_S ? dS : dC);
-            const float mint = (HAVE_S && HAVE_C) ? (s ? mintS : mintC) : (HAVE_S ? mintS : mintC), maxt = (HAVE_S && HAVE_C) ? (s ? maxtS : maxtC) : (HAVE_S ? maxtS : maxtC);
-            wideRaySetup(ray, o, d, V3(slabRcpFast(d.x), slabRcpFast(d.y), slabRcpFast(d.z)), mint, maxt);
-            ng = wideRootGroup(); tg = make_uint2(0u, 0u);
-            stack.sp = 0; shadow = s; active = true; steps = 0;
-            slot[lane] = ~0ull;
-            if (s) goS = false; else goC = false;
-        }
-        if (!__ballot(active)) break;                            /* (wave-uniform: a lane that has nothing in flight here has nothing left to start) */
-        { constexpr bool wideCullOn = false; (void) wideCullOn;
-          if (active && tg.y == 0u && (ng.y & 0xff000000u)) WIDE_NODE_STEP(stack, S, ray, ng, tg, steps) }
-
-        /* ---- the triangle round: every lane takes part (k_wide.h: persistentTraverseWide -- the same statements) ---- */
-        const uint32_t pending = active ? tg.y : 0u;
-        const uint32_t pc = (uint32_t) __popc(pending);
-        bool mine = false;                                       /* this lane's group is decided in this round */
-        if (__ballot(pc != 0u)) {                                /* (wave-uniform) */
-        uint32_t incl = pc;
-        incl += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) incl, 0x111 /* row_shr:1 */, 0xf, 0xf, true);
-        incl += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) incl, 0x112 /* row_shr:2 */, 0xf, 0xf, true);
-        incl += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) incl, 0x114 /* row_shr:4 */, 0xf, 0xf, true);
-        incl += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) incl, 0x118 /* row_shr:8 */, 0xf, 0xf, true);
-        incl += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) incl, 0x142 /* row_bcast:15 */, 0xa, 0xf, false);
-        incl += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) incl, 0x143 /* row_bcast:31 */, 0xc, 0xf, false);
-        const uint32_t nPairs = (uint32_t) __builtin_amdgcn_readlane((int) incl, 63);
-        /* a round costs its instructions whatever the number of pairs: it is held back while few pairs are pending and enough other lanes have node steps to take */
-        const bool roundNow = WD_THRESHOLD == 0u || nPairs >= WD_THRESHOLD || 2u * (uint32_t) __popcll(__ballot(pc != 0u)) >= (uint32_t) __popcll(__ballot(active));
-        if (nPairs && roundNow) {                                /* (wave-uniform) */
-            const bool fits = incl <= WD_CAP;                    /* a prefix of the lanes, never empty: a group has at most 24 records */
-            const uint32_t nFit = (uint32_t) __popcll(__ballot(fits));
-            const uint32_t total = (uint32_t) __builtin_amdgcn_readlane((int) incl, (int) (nFit - 1u));
-            mine = pc != 0u && fits;
-            if (mine) {
-                const uint32_t tag = (shadow ? 0x800u : 0u) | (lane << 5);
-                lds_w16 *w = list + (incl - pc);
-                uint32_t m = pending;
-                do { *w++ = (uint16_t) (tag | (uint32_t) __builtin_ctz(m)); m &= m - 1u; } while (m);
-            }
-            WD_SYNC()
-            for (uint32_t base = 0; base < total; base += 64u) {
-                const uint32_t i = base + lane;
-                const uint32_t item = list[i];                   /* (behind `total`: stale entries, fetched -- every lane must be active in a ds_bpermute -- and not tested) */
-                const uint32_t owner = (item >> 5) & 63u, bit = item & 31u;
-                const bool anyHit = (item & 0x800u) != 0u;
-                const int src = (int) (owner << 2);
-#define WW_FETCH(x) pm_from_bits((uint32_t) __builtin_amdgcn_ds_bpermute(src, (int) pm_to_bits(x)))
-                const V3 po(WW_FETCH(ray.o.x), WW_FETCH(ray.o.y), WW_FETCH(ray.o.z)), pd(WW_FETCH(ray.d.x), WW_FETCH(ray.d.y), WW_FETCH(ray.d.z));
-                const float pmint = WW_FETCH(ray.mint), pmaxt = WW_FETCH(ray.maxt);
-#undef WW_FETCH
-                const uint32_t tbase = (uint32_t) __builtin_amdgcn_ds_bpermute(src, (int) tg.x);
-                if (i < total) {                                 /* (only the last step of a round is partial) */
-                    WIDE_LOAD_TRI(S, tbase + bit, a, b, c)
-                    float tu, tv, tt;
-                    if (waldIntersectSel(a, b, c, po, pd, pmint, pmaxt, tu, tv, tt)) {
-                        const unsigned long long key = anyHit ? (unsigned long long) bit
-                            : (((unsigned long long) pm_to_bits(tt) << 32) | (unsigned long long) (((HIT_PRIM_MASK - pm_to_bits(c.z)) << 2) | (pm_to_bits(c.w) & 3u)));
-                        __hip_atomic_fetch_min(slot + owner, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        if (!anyHit && slot[owner] == key) { u2v q; q.x = pm_to_bits(tu); q.y = pm_to_bits(tv); uvs[owner] = q; }
-                    }
-                }
-            }
-            WD_SYNC()
-        }
-        }
-        if (active) {
-            bool finished = false;
-            if (mine) {
-                const unsigned long long best = slot[lane];
-                if (shadow) {
-                    const bool occ = best != ~0ull;
-                    steps += (uint32_t) __popc(occ ? (tg.y & ((2u << ((uint32_t) best & 31u)) - 1u)) : tg.y) << 16;
-                    finished = occ;
-                } else {
-                    steps += pc << 16;
-                    if (best != ~0ull) ray.maxt = pm_from_bits((uint32_t) (best >> 32));
-                }
-                tg.y = 0u;
-            }
-            if (!finished && tg.y == 0u && !(ng.y & 0xff000000u)) {
-                if (stack.sp == 0) finished = true;
-                else {
-                    const uint2 e = stack.pop();
-                    if (e.y & 0xff000000u) ng = e; else { tg = e; ng = make_uint2(0u, 0u); }
-                }
-            }
-            if (finished) {
-                const unsigned long long best = slot[lane];
-                if (shadow) occluded = best != ~0ull;
-                else {
-                    if (best != ~0ull) {
-                        const u2v q = uvs[lane];
-                        const uint32_t lo = (uint32_t) best;
-                        res.t = pm_from_bits((uint32_t) (best >> 32)); res.u = pm_from_bits(q.x); res.v = pm_from_bits(q.y);
-                        res.prim = HIT_PRIM_MASK - (lo >> 2); res.cls = lo & 3u;
-                    }
-                }
-                /* node steps (low word) and triangle tests (high word) of the ray in ONE 64-bit LDS add */
-                atomicAdd(shadow ? wcS : wcC, (unsigned long long) (steps & 0xFFFFu) | ((unsigned long long) (steps >> 16) << 32));
-                active = false;
-            }
-        }
-    }
-}
 
 /* ======================================================================================
  *  traceWidePool: the wave's rays traversed through ONE SHARED TASK STACK (round 6)
  * ======================================================================================
- * traceWideW keeps k_rays_w's per-lane state machine: a lane walks ITS ray, and the wave leaves the loop when its slowest lane does.  Measured on the Cornell box
+ * The first form of this traversal (traceWideW, HISTORY.md) kept k_rays_w's per-lane state machine: a lane walked ITS ray, and the wave left the loop with its slowest lane.  Measured on the Cornell box
  * with two 500-triangle spheres (profiles/r06_valu_*): 2.1 node visits per ray on average, ~7 loop iterations per traversal phase -- the node step, 210 VALU
  * instructions, runs at a third of its lanes; lane utilisation of the whole kernel 0.43.  (k_rays_w hides that behind refills from a pool of rays in HBM; a lane that
  * owns a path has no other ray to take.)  Here the unit of work is not a ray but a NODE VISIT, and any lane takes any ray's:
  *   - the wave keeps one stack of tasks in LDS (8 bytes: node index | ray, or -- on overflow of the pair list -- a group of leaf triangles | ray);
  *   - an iteration pops the top 64 tasks, one per lane; a lane fetches the task's ray (closest-hit rays from their owners' registers through ds_bpermute, any-hit
  *     rays from a table in LDS), tests the node's eight quantised child boxes (wideNodeHits: the same statement), pushes one task per inner child it hit -- far
- *     children first, so that the nearest is on top -- and hands the leaf triangles it hit to the iteration's triangle round (the dealt Wald tests of traceWideW:
+ *     children first, so that the nearest is on top -- and hands the leaf triangles it hit to the iteration's triangle round (the dealt Wald tests of k_rays_w:
  *     LDS min of (t, highest triangle index) on the ray's result slot);
  *   - the result slot IS the ray's interval: it starts as (bits(maxt), no hit), every closer hit lowers its high word, and every later task of the ray is tested
  *     against it (tasks pushed before are rejected by their own box test); an any-hit ray that was occluded gets an empty interval -- its remaining tasks die at the fetch.
- * A lane brings up to TWO rays (MEGA_JOINT): the shadow ray of the vertex it shaded in the previous pass and the next ray of its path -- 64 + ~34 rays keep the 64
+ * A lane brings up to TWO rays: the shadow ray of the vertex it shaded in the previous pass and the next ray of its path -- 64 + ~34 rays keep the 64
  * lanes busy where the ~34 shadow rays of a pass alone left every iteration half empty.
  * Results do not depend on the order of the visits (boxes are conservative; the hit is the minimum over all candidates by winsTie), so they are the bits of the
  * sequential walk; the work counters are those of THIS order (a node visited before a closer hit was known counts), not the sequential walk's.
@@ -178,9 +41,6 @@ __device__ __forceinline__ void traceWideW(const DevScene &S, WideStackT<BLOCK> 
 #define WP_SPILL_CAP (64u * SPILL_DEPTH / 2u)       /* task-stack entries per wave in the spill buffer (8 B each): the wave's 64 lanes' share of it, all of it */
 #endif
 static_assert(WP_SPILL_CAP <= 64u * SPILL_DEPTH / 2u, "a wave's task stack spills into its own lanes' share of the spill buffer only");
-#ifndef WP_NEAR_FIRST
-#define WP_NEAR_FIRST 1                  /* the nearest child of every lane on top of the stack (0: every lane's children together, far to near) */
-#endif
 #define WP_PAIRS 256u                    /* (ray, triangle) pairs per round and wave (4 B each: ray << 25 | record) */
 #define WP_TRI_MAX (1u << 25)            /* records the pair list can address (phip.hip checks) */
 #define WP_WAVE_BYTES (128u * 8u + 64u * 8u + 64u * 32u + WP_PAIRS * 4u)      /* per wave: result slots of 128 rays, (u, v) of the closest hits, the any-hit rays, pair list */
@@ -323,10 +183,10 @@ __device__ __forceinline__ void traceWidePool(const DevScene &S, const WidePool 
         }
         /* ---- push: the inner children hit.  The NEAREST child of every lane goes to the top segment of the stack, its other children (far to near) and a triangle group the
                 queue had no room for below the top segments of all lanes: the next iteration then pops nearest children of MANY rays rather than all children of a few --
-                depth first, front to back per ray, which is what lets a hit found in the near child reject the far ones (WP_NEAR_FIRST: node visits per closest ray of the
-                atrium 11.3 -> 10.9, of the glass room 10.9 -> 10.4; the per-lane walk makes 10.0) ---- */
+                depth first, front to back per ray, which is what lets a hit found in the near child reject the far ones (pushing every lane's children together, far to near: node visits per closest ray of the
+                atrium 11.3 instead of 10.9, of the glass room 10.9 instead of 10.4; the per-lane walk makes 10.0) ---- */
         const uint32_t nInner = (uint32_t) __popc(inner);
-        const bool hasTop = WP_NEAR_FIRST && nInner != 0u;
+        const bool hasTop = nInner != 0u;
         const uint32_t k = nInner - (hasTop ? 1u : 0u) + (keep ? 1u : 0u);
         const unsigned long long topMask = __ballot(hasTop);
         if (__ballot(k != 0u) | topMask) {                       /* (wave-uniform) */

@@ -16,10 +16,8 @@
  *
  * libphip.so is 26 objects of three sources (phip_common.h).  Kernels and where they live:
  *   k_pool.h      PathPool (HBM layout of the slots), slot flags, RenderConst, per-wave statistics, the sample streams' entry points
- *   k_traverse.h  per-lane BVH4 traversal as a state machine, the flat / packed leaf tables of the LDS-resident trees with the Wald tests dealt over
- *                 the wave (traverseFlat2W), LDS-staged stacks and top-of-tree cache                     [this unit, phip_mega.hip, phip_shade.hip]
- *   k_rays.h      k_trace / k_shadow_p (BVH4: trees of fewer than 64 nodes rendered by `direct` or with PHIP_FLAG_NO_FUSED), k_raycast (phip_trace);
- *                 experiment builds also carry the BVH4 ray kernels of rounds 1-2 for big trees                  [this unit]
+ *   k_traverse.h  the packed leaf tables of the LDS-resident trees with the Wald tests dealt over the wave (traverseFlat2W), the LDS-staged tree
+ *                 and Wald records                                                                        [this unit, phip_mega.hip, phip_shade.hip]
  *   k_wide.h      the ray kernels over the compressed 8-wide BVH (80-byte nodes, quantised child boxes) that the big scenes use: k_rays_w
  *                 (triangle tests dealt over the wave), k_raycast_w                                               [this unit]
  *   k_shade.h     shadeVertex + k_shade<materials, strictNormals, features>: emitter-hit / environment MIS term, Russian roulette, emission, NEE sample
@@ -41,7 +39,6 @@
 #include "phip_common.h"
 #include "bvh.h"
 #include "k_traverse.h"
-#include "k_rays.h"
 #include "k_wide.h"
 #include "k_wide_wave.h"
 #include "k_film.h"
@@ -59,10 +56,7 @@
  *  error handling
  * ====================================================================================== */
 /* Environment: the shipped library reads PHIP_DEBUG_TIMING (host-side phase times on stderr), PHIP_MAX_PASS_SAMPLES (the sample-buffer budget: the tests force several
-   passes with it) and the builder parameters PHIP_BVH_* (bvh.h) -- nothing that selects an algorithm.  Every switch an A/B row of profiles/ was made with is
-   read by experiment builds only (-DPHIP_EXPERIMENTS=1, tools/build_variant.sh): in the product expEnv() is a constant and its names are not even
-   in the binary. */
-static inline const char *expEnv(const char *name) { return PHIP_EXPERIMENTS ? getenv(name) : nullptr; }
+   passes with it) and the builder parameters PHIP_BVH_* (bvh.h) -- nothing that selects an algorithm. */
 static thread_local std::string g_err;
 static int setErr(int code, const std::string &msg) { g_err = msg; return code; }
 
@@ -201,7 +195,6 @@ struct SceneDev {
     uint32_t lastSpp = 0, nLocalTiles = 0; unsigned long long localPixels = 0;
     int tileKey[3] = { -1, -1, -1 };
     bool haveSamples = false;
-    bool mergedRays = false;         /* last render used k_rays_p (closest + any hit in one launch) */
     bool fused = false;              /* last render used k_mega */
     hipStream_t stream = nullptr;
     /* phip_render's device-to-host copy of the film into PAGEABLE memory: two pinned staging chunks (filmToHost) */
@@ -232,14 +225,12 @@ struct SceneDev {
 struct phip_scene {
     phip_scene_desc descCopy;        /* scalar fields only */
     HostBVH bvh;                     /* tree statistics (the node / record arrays are released after the upload) */
-    int traversal = 2;               /* 2 = persistent per-lane BVH4 traversal with dynamic refill (default), 0 = one launch lane per slot (PHIP_TRAVERSAL=lane) */
     bool hasTextures = false; uint32_t triShadeStride = TRISHADE_FLOAT4S;
     int envLevelCount = 0;           /* MIP levels of the envmap (0: no envmap) */
     int materialMask = MM_ALL;       /* leaf BSDF models present: selects the k_shade instantiation */
     bool flatTraceToo = false;       /* a scene of k_mega that k_shade_trace could serve as well (PHIP_FLAG_NO_MEGA) */
     bool flatTrace = false;          /* not a scene of k_mega, but its tree is the packed leaf table (<= 64 Wald records) and emitter table + materials fit LDS: k_shade_trace */
-    bool wide = false;               /* the ray kernels walk the compressed 8-wide BVH: every scene since round 6 */
-    bool wideOnly = false;           /* ... and the device holds nothing else (trees of >= 64 BVH4 nodes or more than 64 Wald records): no BVH4, no leaf table, no LDS-resident kernels */
+    bool wideOnly = false;           /* the device holds the compressed 8-wide BVH the ray kernels walk (every scene has it) and nothing else (trees of >= 64 BVH4 nodes or more than 64 Wald records): no BVH4, no leaf table, no LDS-resident kernels */
     bool fitsLds = false;            /* tree, Wald records, shading records, emitter table and materials fit the fused kernel's LDS plan */
     int fusedWide = 0;               /* round 6: 4 / 5 = the fused kernel walks the 8-wide tree from memory (k_mega<.., FLAT 4 / 5, ..>: emitter table in LDS; materials in LDS / in memory) */
     std::vector<std::unique_ptr<SceneDev>> devs;
@@ -457,7 +448,6 @@ struct SceneBuild {
             if (m.type == PHIP_BSDF_ROUGHCONDUCTOR) sc->materialMask |= MM_ROUGH;
             if (m.type == PHIP_BSDF_DIELECTRIC) sc->materialMask |= MM_DIELECTRIC;
         }
-        if (const char *e = expEnv("PHIP_SHADE_GENERIC")) if (atoi(e)) sc->materialMask = MM_ALL;
     }
 
     /* DevEmitters + selection pdf (scene.cpp:375-381), the single environment emitter */
@@ -570,23 +560,18 @@ struct SceneBuild {
             }
     }
 
-    /* which structure the ray kernels walk (traversal, wideOnly, wide) and whether its depth fits their stacks */
+    /* what the device holds beside the 8-wide tree the ray kernels walk (wideOnly) and whether that tree's depth fits their stacks */
     void chooseTraversal() {
-        if (const char *e = expEnv("PHIP_TRAVERSAL")) sc->traversal = strcmp(e, "lane") == 0 ? 0 : 2;
         /* the compressed 8-wide tree: every scene the packed leaf table of the LDS-resident kernels does not serve (more than 64 Wald records).  Round 6: it used to start at 64 BVH4
            nodes; the scenes in between ran the round-1 BVH4 kernels (or, all-diffuse ones, k_mega's BVH4 walk in LDS) -- now they run k_mega on the wide tree / k_rays_w */
         if (sc->bvh.nWNodes == 0) {      /* a scene without triangles: one node without children (all-zero meta bytes hit nothing) -- the ray kernels need a root to reject */
             sc->bvh.wnodes.assign(20, 0u); sc->bvh.nWNodes = 1; sc->bvh.wMaxDepth = 1;
         }
-        const char *wideSwitch = expEnv("PHIP_WIDE");
-        sc->wideOnly = sc->traversal == 2 && sc->bvh.nWNodes > 0 && (sc->bvh.nNodes >= 64 || sc->bvh.tris.size() / 12 > PHIP_WIDE_MIN_RECORDS)
-                    && (!wideSwitch || atoi(wideSwitch) != 0);
-        /* ... and, round 6, EVERY scene has the wide tree on the device: the ray kernels of the wavefront path (k_rays_w) and phip_trace (k_raycast_w) walk nothing else -- the
-           round-1 BVH4 ray kernels are compiled by experiment builds only.  The LDS-resident scenes keep their BVH4-ordered records and leaf table for k_mega / k_shade_trace beside it */
-        sc->wide = sc->traversal == 2 && sc->bvh.nWNodes > 0 && (sc->wideOnly || !(PHIP_EXPERIMENTS && expEnv("PHIP_BVH4_RAYS")));
-        /* the stack of the structure that is going to be walked: three pushes per BVH4 level, one group per level of the wide tree */
-        if (!sc->wide && 3 * sc->bvh.maxDepth + 2 > STACK_DEPTH + SPILL_DEPTH) throw std::runtime_error("BVH too deep for the traversal stack");
-        if (sc->wide && (int) sc->bvh.wMaxDepth + 2 > WIDE_STACK_LDS + SPILL_DEPTH / 2) throw std::runtime_error("wide BVH too deep for the traversal stack");
+        sc->wideOnly = sc->bvh.nNodes >= 64 || sc->bvh.tris.size() / 12 > PHIP_WIDE_MIN_RECORDS;
+        /* ... and, round 6, EVERY scene has the wide tree on the device: the ray kernels of the wavefront path (k_rays_w) and phip_trace (k_raycast_w) walk nothing else.
+           The LDS-resident scenes keep their BVH4-ordered records and leaf table for k_mega / k_shade_trace beside it */
+        /* the stack of the wide tree: one group per level */
+        if ((int) sc->bvh.wMaxDepth + 2 > WIDE_STACK_LDS + SPILL_DEPTH / 2) throw std::runtime_error("wide BVH too deep for the traversal stack");
     }
 
     /* packed emitter table (dv_scene.h: EmitterTab) */
@@ -731,13 +716,11 @@ struct SceneBuild {
        stack a walk of the BVH4 needs (3 pushes per level) -- and what follows from it for the fused kernel */
     void ldsPlan() {
         const HostBVH &bvh = sc->bvh;
-        const char *cacheSwitch = expEnv("PHIP_NODE_CACHE");
-        const uint32_t cacheMax = cacheSwitch ? (uint32_t) atoi(cacheSwitch) : 0xFFFFFFFFu;
         walkStack = (uint32_t) std::min<int>(STACK_DEPTH, std::max<int>(4, 3 * ((int) bvh.maxDepth - 1) + 1));
-        D.nodeCache = sc->wideOnly ? 0u : std::min<uint32_t>(bvh.nNodes, cacheSwitch ? cacheMax : NODE_CACHE_MAX);
+        D.nodeCache = sc->wideOnly ? 0u : std::min<uint32_t>(bvh.nNodes, NODE_CACHE_MAX);
         D.triCache = (!sc->wideOnly && D.nodeCache != 0 && bvh.tris.size() / 12 <= TRI_CACHE_MAX) ? (uint32_t) (bvh.tris.size() / 12) : 0u;
-        D.wideNodeCache = sc->wide ? std::min<uint32_t>(std::min<uint32_t>(bvh.nWNodes, WIDE_NODE_CACHE_MAX), cacheMax) : 0u;
-        D.preclip = sc->wide ? 1u : 0u;                          /* k_rays_w traverses rays the shading kernels have clipped (k_clip.h) */
+        D.wideNodeCache = std::min<uint32_t>(bvh.nWNodes, WIDE_NODE_CACHE_MAX);
+        D.preclip = 1u;                          /* k_rays_w traverses rays the shading kernels have clipped (k_clip.h) */
         /* the fused kernel's LDS plan (k_mega.h): the whole tree, every Wald and shading record, the emitter table and the
            materials in LDS, a stack that cannot spill (phip_mega.hip) */
         /* (treeInLds: the whole tree and every Wald record are staged in LDS and the stack cannot spill -- also true of small scenes with glass, copper,
@@ -750,7 +733,7 @@ struct SceneBuild {
             && tab.size() <= EMITTER_LDS_FLOATS && mats.size() <= MATERIAL_LDS_MAX;
     }
 
-    /* the leaf boxes of flatLeafTable in the packed form with record masks (k_traverse.h: traverseFlat2).  A leaf reference is
+    /* the leaf boxes of flatLeafTable in the packed form with record masks (k_traverse.h: flat2Pass1).  A leaf reference is
        ~((first record << 3) | records - 1); a triangle referenced by several leaves (spatial splits) has one record per
        reference -- the copies carry the same 12 words, so only the first copy's bit is set.
        Round 5: 33..64 records keep the packed form with a two-word mask (flatMode 3; the centre / half-extent table of the dealt
@@ -768,7 +751,6 @@ struct SceneBuild {
             unsigned long long bits64 = 0;
             for (uint32_t i = 0; i < count; ++i) bits64 |= 1ull << firstCopy[first + i];
             const uint32_t bits = (uint32_t) bits64, bitsHi = (uint32_t) (bits64 >> 32);
-#if MEGA_FLAT_CH
             /* centre / half extent (k_traverse.h: flat2Pass1).  c -+ h must cover the (padded) box whatever the rounding of c, and the
                distances c' -+ h |rcp| are rounded differently from the plane form the pad of bvh.h was sized for (two roundings of
                magnitude |c rcp| + |o rcp| instead of one): h gets the rounding of c and another 4e-6 of the scene's extent on top */
@@ -786,21 +768,16 @@ struct SceneBuild {
             }
             packed.push_back(make_float4(c[0], c[1], c[2], pm_from_bits(bitsHi)));
             packed.push_back(make_float4(h[0], h[1], h[2], pm_from_bits(bits)));
-#else
-            (void) bitsHi;
-            packed.push_back(make_float4(mn.x, mx.x, mn.y, mx.y));
-            packed.push_back(make_float4(mn.z, mx.z, pm_from_bits(bits), 0.0f));
-#endif
         }
         flat.swap(packed);
     }
 
-    /* for trees of few leaves (the Cornell box: 17), the leaves as a flat table: the fused kernel tests every leaf box in one uniform pass instead
-       of walking the 7-node tree (k_traverse.h: traverseFlat).  Entry = (min.xyz, bits(leaf reference)) (max.xyz, 0), boxes as the BVH4 nodes hold
-       them (padded).  flatMode: 0 no table, 1 these boxes, 2 / 3 the packed form of at most 32 / 64 Wald records */
+    /* for trees of few leaves (the Cornell box: 17), the leaves as a flat table: the LDS-resident kernels test every leaf box in one uniform pass instead
+       of walking the 7-node tree.  Entry = (min.xyz, bits(leaf reference)) (max.xyz, 0), boxes as the BVH4 nodes hold them (padded), then packed.
+       flatMode: 0 no table, 1 these boxes (no kernel reads them: only a build with another PHIP_WIDE_MIN_RECORDS gets there), 2 / 3 the packed form of at most 32 / 64 Wald records */
     void flatLeafTable() {
         int mode = 0;
-        if (treeInLds && !sc->wideOnly && sc->bvh.nLeaves <= FLAT2_LEAVES_MAX && !expEnv("PHIP_NO_FLAT")) {
+        if (treeInLds && !sc->wideOnly && sc->bvh.nLeaves <= FLAT2_LEAVES_MAX) {
             if (sc->bvh.rootRef < 0) {                         /* a single leaf: its box is the scene's */
                 flat.push_back(make_float4(sc->bvh.tightMin[0] - 1.0f, sc->bvh.tightMin[1] - 1.0f, sc->bvh.tightMin[2] - 1.0f, pm_from_bits((uint32_t) sc->bvh.rootRef)));
                 flat.push_back(make_float4(sc->bvh.tightMax[0] + 1.0f, sc->bvh.tightMax[1] + 1.0f, sc->bvh.tightMax[2] + 1.0f, 0.0f));
@@ -814,8 +791,7 @@ struct SceneBuild {
                 }
             }
             const size_t nRec = sc->bvh.tris.size() / 12;
-            const size_t packedMax = (MEGA_FLAT_CH && MEGA_BALANCE && !expEnv("PHIP_NO_FLAT3")) ? 64 : 32;
-            if (flat.size() / 2 <= FLAT2_LEAVES_MAX && nRec <= packedMax && !expEnv("PHIP_NO_FLAT2")) {
+            if (flat.size() / 2 <= FLAT2_LEAVES_MAX && nRec <= 64) {
                 packLeafTable(nRec); mode = nRec <= 32 ? 2 : 3;
             } else if (fitsLdsBase && sc->materialMask == 0 && flat.size() / 2 <= FLAT_LEAVES_MAX)
                 mode = 1;
@@ -828,26 +804,24 @@ struct SceneBuild {
        the stack the LDS plans of those kernels need, the lane deal of the shading kernels */
     void chooseDevicePaths() {
         const int mask = sc->materialMask;
-        /* leaf BSDF models: diffuse only for the trees the fused kernel walks or sweeps leaf by leaf, any (round 5) on the packed leaf table */
-        sc->fitsLds = fitsLdsBase && (mask == 0 || (D.flatMode >= 2 && !expEnv("PHIP_NO_MEGA_MATERIALS")));
+        /* leaf BSDF models: any (round 5) on the packed leaf table */
+        sc->fitsLds = fitsLdsBase && (mask == 0 || D.flatMode >= 2);
         /* round 6: the fused kernel on a tree that does not fit LDS (k_wide_wave.h) -- every scene on the 8-wide tree whose emitter table fits LDS and that needs none of the
            feature sets k_mega is not compiled with (bitmap textures, an environment emitter) */
         sc->fusedWide = (sc->wideOnly && !sc->hasTextures && envEmitter < 0 && stride == TRISHADE_FLOAT4S && tab.size() <= EMITTER_LDS_FLOATS
-                         && sc->bvh.wtris.size() / 12 < WP_TRI_MAX && !expEnv("PHIP_NO_MEGA_WIDE"))
+                         && sc->bvh.wtris.size() / 12 < WP_TRI_MAX)
                       ? (mats.size() <= MATERIAL_LDS_MAX ? 4 : 5) : 0;
-        const bool traceable = D.flatMode >= 2 && tab.size() <= EMITTER_LDS_FLOATS && mats.size() <= MATERIAL_LDS_MAX && !expEnv("PHIP_NO_SHADE_TRACE");
+        const bool traceable = D.flatMode >= 2 && tab.size() <= EMITTER_LDS_FLOATS && mats.size() <= MATERIAL_LDS_MAX;
         sc->flatTrace = !sc->fitsLds && traceable; sc->flatTraceToo = sc->fitsLds && traceable;
-        /* the walk of the BVH4; k_mega deals the Wald tests of the packed table over the wave through LDS buffers that lie over the (then unused) traversal stack
-           (k_traverse.h: traverseFlat2W); k_mega<MM_ALL> keeps its mailbox of copper vertices (QMC build: the exchange buffer of its class deal) in MEGA_DEAL_DWORDS x BLOCK
-           dwords of LDS that lie there too (k_mega.h) */
+        /* k_mega deals the Wald tests of the packed table over the wave through LDS buffers that lie over the (unused) traversal stack
+           (k_traverse.h: traverseFlat2W); k_mega<MM_ALL> keeps its mailbox of copper vertices in MEGA_DEAL_DWORDS x BLOCK dwords of LDS that lie there too (k_mega.h) */
         const uint32_t dealStack = D.flatMode >= 2 ? (uint32_t) (((BLOCK / 64) * BAL_WAVE_BYTES + BLOCK * sizeof(uint32_t) - 1) / (BLOCK * sizeof(uint32_t))) : 0u;
         const uint32_t mailboxStack = (sc->fitsLds && mask != 0) ? (uint32_t) MEGA_DEAL_DWORDS : 0u;
         D.stackDepth = std::max(walkStack, std::max(dealStack, mailboxStack));
         /* the lane deal of k_shade pays where the expensive model is rare: rough conductors (microfacet sampling: atrium, 8 % of the vertices,
            k_shade -7 %); on a diffuse + dielectric mix the extra round trip costs more than the cheap Fresnel branch (glass room: +8 %).
            k_shade_trace deals its lanes by BSDF model where there is more than one (the kernel traces its own rays and leaves the class in the hit word) */
-        const char *sortSwitch = expEnv("PHIP_SHADE_SORT");       /* experiment hook */
-        D.shadeSort = (((sc->wide && (mask & MM_ROUGH)) || (traceable && mask != 0)) && (!sortSwitch || atoi(sortSwitch) != 0)) ? 1u : 0u;
+        D.shadeSort = ((mask & MM_ROUGH) || (traceable && mask != 0)) ? 1u : 0u;
     }
 
     /* every immutable scene buffer of the device (placeholders where a kernel argument must not be NULL), the DevScene's pointers, the per-device counters */
@@ -857,16 +831,14 @@ struct SceneBuild {
         if (ts.empty()) sd.triShade.alloc(TRISHADE_FLOAT4S_UV); else sd.triShade.upload(ts.data(), ts.size());
         if (texTexels.empty()) sd.texTexels.alloc(1); else sd.texTexels.upload(texTexels.data(), texTexels.size());
         if (texDesc.empty()) sd.texDesc.alloc(1); else sd.texDesc.upload(texDesc.data(), texDesc.size());
-        if (sc->wide) {
-            if (WIDE_NODE_STRIDE == 5) sd.wnodes.upload((const uint4 *) bvh.wnodes.data(), bvh.wnodes.size() / 4);
-            else {                                               /* one node per WIDE_NODE_STRIDE * 16 bytes (a 128-byte line) */
-                const size_t n = bvh.wnodes.size() / 20;
-                std::vector<uint4> padded(n * WIDE_NODE_STRIDE, make_uint4(0, 0, 0, 0));
-                for (size_t i = 0; i < n; ++i) memcpy(&padded[i * WIDE_NODE_STRIDE], &bvh.wnodes[i * 20], 80);
-                sd.wnodes.upload(padded.data(), padded.size());
-            }
-            if (bvh.wtris.empty()) sd.wtris.alloc(3); else sd.wtris.upload((const float4 *) bvh.wtris.data(), bvh.wtris.size() / 4);
-        } else { sd.wnodes.alloc(5); sd.wtris.alloc(3); }
+        if (WIDE_NODE_STRIDE == 5) sd.wnodes.upload((const uint4 *) bvh.wnodes.data(), bvh.wnodes.size() / 4);
+        else {                                                   /* one node per WIDE_NODE_STRIDE * 16 bytes (a 128-byte line) */
+            const size_t n = bvh.wnodes.size() / 20;
+            std::vector<uint4> padded(n * WIDE_NODE_STRIDE, make_uint4(0, 0, 0, 0));
+            for (size_t i = 0; i < n; ++i) memcpy(&padded[i * WIDE_NODE_STRIDE], &bvh.wnodes[i * 20], 80);
+            sd.wnodes.upload(padded.data(), padded.size());
+        }
+        if (bvh.wtris.empty()) sd.wtris.alloc(3); else sd.wtris.upload((const float4 *) bvh.wtris.data(), bvh.wtris.size() / 4);
         sd.trisAreWide = sc->wideOnly;                           /* DevScene::tris = wtris: SceneDev::bind */
         if (sc->wideOnly) { sd.nodes.alloc(8); sd.tris.alloc(3); }
         else {
@@ -1025,16 +997,15 @@ static void phipLaunchShadeDirect(int feat, int materialMask, dim3 grid, hipStre
     }
 }
 
-static size_t traversalLdsBytes(const DevScene &D) {               /* kernels launched with blocks of BLOCK threads */
-    if (D.wideNodeCache) return wideLdsBytes(wideRaycastCache(D.wideNodeCache), BLOCK);
-    return traversalLdsBytesOf(D);
+static size_t traversalLdsBytes(const DevScene &D) {               /* k_raycast_w: blocks of BLOCK threads */
+    return wideLdsBytes(wideRaycastCache(D.wideNodeCache), BLOCK);
 }
 
-static void algorithmicBytes(bool mergedRays, phip_stats &st, double filmPixels, bool wide = false) {
-    /* SURVEY 8(d) with this structure's sizes: 128-byte BVH4 node visits, 48-byte triangle records
+static void algorithmicBytes(bool mergedRays, phip_stats &st, double filmPixels) {
+    /* SURVEY 8(d) with this structure's sizes: 80-byte node visits of the 8-wide tree, 48-byte triangle records
        (no separate index array: records are stored in leaf order) */
     const double film = 20.0 * filmPixels;
-    const double nodeBytes = wide ? 80.0 : 128.0;
+    const double nodeBytes = 80.0;
     st.algorithmic_bytes = nodeBytes * (double) (st.closest_node_visits + st.shadow_node_visits) +
            48.0 * (double) (st.closest_triangle_tests + st.shadow_triangle_tests) +
            (64.0 + 40.0 + 108.0) * (double) st.closest_rays + (64.0 + 4.0) * (double) st.shadow_rays +
@@ -1043,7 +1014,7 @@ static void algorithmicBytes(bool mergedRays, phip_stats &st, double filmPixels,
        the SURVEY's read+write convention: ray 64 B, hit 40 B */
     st.trace_kernel_bytes = nodeBytes * (double) st.closest_node_visits + 48.0 * (double) st.closest_triangle_tests +
            (64.0 + 40.0) * (double) st.closest_rays;
-    if (mergedRays)    /* k_rays_p also casts the shadow rays: their node + record fetches, entry read, 4-byte result */
+    if (mergedRays)    /* k_rays_w also casts the shadow rays: their node + record fetches, entry read, 4-byte result */
         st.trace_kernel_bytes += nodeBytes * (double) st.shadow_node_visits + 48.0 * (double) st.shadow_triangle_tests +
                (64.0 + 4.0) * (double) st.shadow_rays;
 }
@@ -1155,14 +1126,10 @@ struct FusedPlan {
 /* The wavefront kernels for one render call (set up only when that path runs): pool, kernel choice, grids */
 struct WavefrontPlan {
     bool shadeTrace = false;                /* k_shade_trace: the vertex kernel traces both rays of the iteration itself */
-    bool merged = false;                    /* closest-hit and any-hit rays share one persistent launch */
     uint32_t capacity = 0, nWaves = 0, nBlocks = 0;
     int feat = 0;                           /* FEAT of the shading kernels: 1 environment emitter, 2 bitmap textures, 8 the QMC samplers */
-    size_t ldsBytes = 0, wideLds = 0, shadeTraceLds = 0;
+    size_t wideLds = 0, shadeTraceLds = 0;
     dim3 grid = dim3(1), pgridRays = dim3(1);
-#if PHIP_EXPERIMENTS
-    dim3 pgrid = dim3(1), pgridTrace = dim3(1); bool forcePersist = false;
-#endif
 };
 
 /* One device's share of one render call: what the stages of renderOnDevice hand to each other */
@@ -1176,7 +1143,7 @@ struct RenderJob {
     FusedPlan F; WavefrontPlan wf;
     PathPool P;                             /* the wavefront pool; a fused pass sets its statistics rows only (k_reduce_stats) */
     RenderConst rc;                         /* of the call, then of the pass that is running */
-    EventList evTrace, evShadow, evShade, evFilm, evFused;
+    EventList evTrace, evShade, evFilm, evFused;
     Counters hc; phip_stats st;
     unsigned long long samplesDone = 0;     /* samples of the passes that are in the film already */
     bool cancelled = false;
@@ -1228,7 +1195,7 @@ static void shardTiles(RenderJob &J, int shardIndex, int shardCount) {
 /* passes: bound the per-sample buffer (16 B per sample id; 24 B with the jitter the sequence samplers keep for the film pass) */
 static void planPasses(RenderJob &J) {
     SceneDev &sd = J.sd; const phip_render_params *p = J.p;
-    J.keepJitter = (p->sampler == PHIP_SAMPLER_SOBOL || p->sampler == PHIP_SAMPLER_HALTON || p->sampler == PHIP_SAMPLER_HAMMERSLEY) && !expEnv("PHIP_NO_JITTER_BUFFER");
+    J.keepJitter = (p->sampler == PHIP_SAMPLER_SOBOL || p->sampler == PHIP_SAMPLER_HALTON || p->sampler == PHIP_SAMPLER_HAMMERSLEY);
     const unsigned long long maxIdsPerPass = (1ull << 32) - 1;                 /* sample ids are 32-bit in the slot state */
     unsigned long long budgetIds = (24ull << 30) / (J.keepJitter ? 24 : 16);  /* 24 GiB of sample buffer */
     if (const char *e = getenv("PHIP_MAX_PASS_SAMPLES")) budgetIds = std::max(1ull, strtoull(e, nullptr, 10));   /* test hook: force several passes */
@@ -1295,11 +1262,10 @@ static void planFused(RenderJob &J) {
     phip_scene *sc = J.sc; SceneDev &sd = J.sd; const phip_render_params *p = J.p; FusedPlan &F = J.F;
     /* (the fused kernel on the 8-wide tree: by default where it is faster than the wavefront kernels -- trees that live in L2, DESIGN.md 3.9 -- with PHIP_FLAG_FUSED_ANY wherever it can run) */
     const bool wideFused = sc->fusedWide && (sc->bvh.nWNodes <= PHIP_FUSED_WIDE_MAX_NODES || (p->flags & PHIP_FLAG_FUSED_ANY));
-    F.on = (sc->fitsLds || wideFused) && sc->traversal == 2 && !(p->flags & (PHIP_FLAG_NO_FUSED | PHIP_FLAG_NO_MEGA));
+    F.on = (sc->fitsLds || wideFused) && !(p->flags & (PHIP_FLAG_NO_FUSED | PHIP_FLAG_NO_MEGA));
     F.flat = sc->fitsLds ? (J.D.nFlatLeaves ? (int) J.D.flatMode : 0) : sc->fusedWide;
     if (J.direct && F.flat < 2) F.on = false;      /* (round 6: `direct` rides the fused kernel too -- k_mega<.., DIRECT>, on the packed leaf tables and on the tree in memory) */
     F.wide = F.flat >= 4;
-    if (const char *e = expEnv("PHIP_MEGA")) F.on = F.on && atoi(e) != 0;            /* experiment hook: PHIP_MEGA=0 forces the wavefront kernels */
     F.strictNormals = !J.direct && p->strict_normals != 0;
     F.blocksPerCU = J.direct ? phipMegaBlocksPerCUDirect : F.wide ? phipMegaBlocksPerCUWide : phipMegaBlocksPerCU;
     F.launch = J.direct ? phipLaunchMegaDirect : F.wide ? phipLaunchMegaWide : phipLaunchMega;
@@ -1307,24 +1273,20 @@ static void planFused(RenderJob &J) {
        creation): when none fits a compute unit the render runs on the wavefront kernels, as it did before the samplers moved to k_mega */
     if (F.on) {
         if (F.wide) {
-            /* the top of the tree every block stages (BFS order); the mailbox build (all leaf BSDF models, counter stream) has the S-box behind the round buffers */
+            /* the top of the tree every block stages (BFS order) */
             F.nodeCache = std::min<uint32_t>(sc->bvh.nWNodes, MEGA_WIDE_NODE_CACHE);
-            if (const char *e = expEnv("PHIP_MEGA_NODE_CACHE")) F.nodeCache = std::min<uint32_t>(sc->bvh.nWNodes, (uint32_t) atoi(e));
-            const bool mailbox = false;     /* (the tree-in-memory builds deal their paths by BSDF model; the mailboxes' LDS would cost the fourth block of a CU: k_mega.h) */
-            F.lds = MEGA_POOL ? megaWidePoolLdsBytesOf(J.D, F.nodeCache, mailbox, F.flat == 4, MB_DW * MB_NS * sizeof(uint32_t))
-                              : megaWideLdsBytesOf(J.D, F.nodeCache, mailbox, F.flat == 4, MB_DW * MB_NS * sizeof(uint32_t));
+            const bool mailbox = false;     /* (the mailboxes' LDS would cost the tree-in-memory builds the fourth block of a CU: k_mega.h) */
+            F.lds = megaWidePoolLdsBytesOf(J.D, F.nodeCache, mailbox, F.flat == 4, MB_DW * MB_NS * sizeof(uint32_t));
         } else {
             F.lds = megaLdsBytesOf(J.D);
         }
         F.perCU = std::min(MEGA_WAVES, F.blocksPerCU(sc->materialMask, F.strictNormals, F.flat, J.qmc, F.lds));
-        if (const char *e = expEnv("PHIP_MEGA_BLOCKS")) F.perCU = std::max(1, std::min(F.perCU, atoi(e)));
         if (F.perCU <= 0) F.on = false;
         if (getenv("PHIP_DEBUG_TIMING")) fprintf(stderr, "[phip] k_mega (traversal form %d): %d blocks per CU with %zu bytes of dynamic LDS\n", F.flat, F.perCU, F.lds);
     }
     sd.fused = F.on;
     /* ... or k_shade_trace: the scene's tree is the packed leaf table, but k_mega does not serve it (glass / copper / textures / environment emitter) */
-    J.wf.shadeTrace = !F.on && (sc->flatTrace || sc->flatTraceToo) && !J.direct && sc->traversal == 2 && !(p->flags & PHIP_FLAG_NO_FUSED);
-    sd.mergedRays = false;                  /* (until the wavefront setup decides) */
+    J.wf.shadeTrace = !F.on && (sc->flatTrace || sc->flatTraceToo) && !J.direct && !(p->flags & PHIP_FLAG_NO_FUSED);
     if (!F.on) return;
 
     /* resident grid and per-wave statistics rows */
@@ -1363,46 +1325,25 @@ static void setupWavefrontGrids(RenderJob &J) {
     const int feat0 = (D.envEmitter >= 0 ? 1 : 0) | (sc->hasTextures ? 2 : 0);
     wf.feat = J.qmc ? (feat0 ? 11 : 8) : feat0;
     wf.shadeTraceLds = shadeTraceLdsBytes(D);
-    wf.ldsBytes = traversalLdsBytes(D);
-    /* persistent kernels: exactly the resident set (TRACE_WAVES waves per SIMD = TRACE_WAVES blocks of 256 per CU)
-       ... but never more blocks per CU than their LDS (stack + node/record cache) allows: a persistent grid larger than
-       the resident set would serialise */
-    /* The grid of a persistent kernel is exactly its resident set.  Residency is asked of the runtime (registers, the block's static
-       + dynamic LDS and the LDS allocation granule all enter) -- an arithmetic estimate that is one block per CU too high makes
-       the surplus blocks wait for a resident one to finish: a second round that doubled the ray kernel's time when the LDS
-       node cache grew to 7.5 KB (round 2). */
-    auto residentBlocks = [&](const void *kernel, int wanted) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, BLOCK, wf.ldsBytes) != hipSuccess || n <= 0) n = 1;
-        return std::min(n, wanted);
-    };
-    [[maybe_unused]] auto persistentGrid = [&](const void *kernel, int blocksPerCU) {
-        return dim3((unsigned) std::max(1, std::min<int>(nCU * residentBlocks(kernel, blocksPerCU), (int) ((capacity + BLOCK - 1) / BLOCK))));
-    };
     wf.grid = dim3((capacity + BLOCK - 1) / BLOCK);
-#if PHIP_EXPERIMENTS
-    wf.pgrid = persistentGrid((const void *) k_shadow_p, TRACE_WAVES);
-    wf.pgridTrace = persistentGrid(sc->bvh.nNodes >= 64 ? (const void *) k_trace_p<false> : (const void *) k_trace_p<true>, TRACE_P_WAVES);
-    wf.pgridRays = persistentGrid((const void *) k_rays_p, RAYS_WAVES);       /* (PHIP_WIDE=0: the BVH4 ray kernels of rounds 1-2 on the big scenes) */
-    wf.forcePersist = expEnv("PHIP_TRACE_PERSIST") != nullptr;
-#endif
-    /* k_rays_w: blocks of WIDE_BLOCK threads with their own LDS plan (one block per CU holds 800 nodes of the tree) */
-    wf.wideLds = sc->wide ? wideLdsBytes(D.wideNodeCache, WIDE_BLOCK) + wideDealBytes(WIDE_BLOCK) : 0;
-    if (sc->wide) {
-        if (wf.wideLds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *) k_rays_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int) wf.wideLds));
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *) k_rays_w, WIDE_BLOCK, wf.wideLds) != hipSuccess || n <= 0) n = 1;
-        n = std::min(n, WIDE_WAVES * 256 / WIDE_BLOCK);
-        if (n <= 0) n = 1;
-        wf.pgridRays = dim3((unsigned) std::max(1, std::min<int>(nCU * n, (int) ((capacity + WIDE_BLOCK - 1) / WIDE_BLOCK))));
-        /* k_rays_w draws its chunks from sharded counters */
-        if (J.sd.drawCounters.n < 2 * RAY_SHARDS * RAY_SHARD_STRIDE) J.sd.drawCounters.alloc(2 * RAY_SHARDS * RAY_SHARD_STRIDE);
-    }
+    /* k_rays_w: blocks of WIDE_BLOCK threads with their own LDS plan.  The grid of a persistent kernel is exactly its resident set.  Residency is asked
+       of the runtime (registers, the block's static + dynamic LDS and the LDS allocation granule all enter) -- an arithmetic estimate that is one block
+       per CU too high makes the surplus blocks wait for a resident one to finish: a second round that doubled the ray kernel's time when the LDS node
+       cache grew to 7.5 KB (round 2). */
+    wf.wideLds = wideLdsBytes(D.wideNodeCache, WIDE_BLOCK) + wideDealBytes(WIDE_BLOCK);
+    if (wf.wideLds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *) k_rays_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int) wf.wideLds));
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *) k_rays_w, WIDE_BLOCK, wf.wideLds) != hipSuccess || n <= 0) n = 1;
+    n = std::min(n, WIDE_WAVES * 256 / WIDE_BLOCK);
+    if (n <= 0) n = 1;
+    wf.pgridRays = dim3((unsigned) std::max(1, std::min<int>(nCU * n, (int) ((capacity + WIDE_BLOCK - 1) / WIDE_BLOCK))));
+    /* k_rays_w draws its chunks from sharded counters */
+    if (J.sd.drawCounters.n < 2 * RAY_SHARDS * RAY_SHARD_STRIDE) J.sd.drawCounters.alloc(2 * RAY_SHARDS * RAY_SHARD_STRIDE);
 }
 
 /* The wavefront path's pool, sized for a first pass of idsFirstPass sample ids and for the memory that is free now; then its kernels and grids */
 static void setupWavefront(RenderJob &J, unsigned long long idsFirstPass) {
-    phip_scene *sc = J.sc; SceneDev &sd = J.sd; WavefrontPlan &wf = J.wf; PathPool &P = J.P;
+    SceneDev &sd = J.sd; WavefrontPlan &wf = J.wf; PathPool &P = J.P;
     /* pool size: large enough that per-launch fixed costs vanish, small enough that the tail (slots
        running dry at the end of a pass) stays a small fraction of the pass (measured: 4M / 8M slots) */
     /* (round 3) Every launch of the persistent ray kernel ends with a drain in which each wave waits for its longest ray while the
@@ -1418,21 +1359,15 @@ static void setupWavefront(RenderJob &J, unsigned long long idsFirstPass) {
                                      : idsFirstPass > (256ull << 20) ? (1ull << 26) : idsFirstPass >= (64ull << 20) ? (1ull << 24)
                                      : idsFirstPass >= (16ull << 20) ? (1ull << 23) : (1ull << 22);
     uint32_t capacity = (uint32_t) std::min<unsigned long long>(std::max<unsigned long long>(idsFirstPass, BLOCK), poolCap);
-    /* traversal-stack overflow: SPILL_DEPTH words per LANE of a ray kernel -- the wide tree is only walked by persistent grids
-       (at most 8 resident blocks of 256 per CU), the BVH4 also by one-lane-per-slot launches */
-    const bool canSpill = sc->wide ? (int) sc->bvh.wMaxDepth + 2 > WIDE_STACK_LDS : 3 * ((int) sc->bvh.maxDepth - 1) + 1 > (int) J.D.stackDepth;
-    const bool persistentOnly = sc->wide || (sc->traversal == 2 && sc->bvh.nNodes >= 64 && !expEnv("PHIP_MERGED"));
-    {   /* ... and with the memory that is there: the pool's state is ~144 B per slot (+ 384 B of spill stack where every slot is a lane that can
-           spill); it may take a quarter of what is free now (a shared or partitioned GPU, n_devices replicas), never less than the 4 M slots
+    {   /* ... and with the memory that is there: the pool's state is ~144 B per slot; it may take a quarter of what is free now (a shared or partitioned GPU, n_devices replicas), never less than the 4 M slots
            every job ran with before the pool grew */
         size_t freeB = 0, totalB = 0;
         if (sd.rayO.n < capacity && hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-            unsigned long long fit = (unsigned long long) (freeB / 4) / (144ull + ((!persistentOnly && canSpill) ? (unsigned long long) SPILL_DEPTH * 4ull : 0ull));
+            unsigned long long fit = (unsigned long long) (freeB / 4) / 144ull;
             while (capacity > (1u << 22) && capacity > fit) capacity >>= 1;
         }
     }
     capacity = (capacity + BLOCK - 1) / BLOCK * BLOCK;
-    if (const char *e = expEnv("PHIP_POOL")) { capacity = (uint32_t) std::max(BLOCK, atoi(e)) / BLOCK * BLOCK; }
     const size_t laneCap = ((size_t) capacity + WIDE_BLOCK - 1) / WIDE_BLOCK * WIDE_BLOCK;      /* k_rays_w runs whole blocks of WIDE_BLOCK lanes */
     const uint32_t nWaves = (uint32_t) (laneCap / 64), nBlocks = capacity / BLOCK;
     if (sd.rayO.n < capacity) {
@@ -1440,12 +1375,10 @@ static void setupWavefront(RenderJob &J, unsigned long long idsFirstPass) {
         sd.mis.alloc(capacity); sd.info.alloc(capacity); sd.state.alloc(capacity); sd.shadow.alloc(3 * (size_t) capacity);
         sd.shadowCount.alloc(nBlocks); sd.blockDead.alloc(nBlocks); sd.blockShard.alloc(nBlocks);
     }
-    {   /* persistent grids (at most 8 resident blocks of 256 per CU): the buffer always covers the whole grid, also when the host's depth bound says
-           that no lane can reach it -- 200 MB of 288 GB against a silent out-of-bounds write should that hand-derived bound ever be off.  One lane
-           per slot (BVH4 trees of < 64 nodes: small scenes with non-diffuse materials, every `direct` render of a small scene): 384 B per SLOT of a
-           pool of up to 64 M slots is 3..25 GB for a stack that is at most ~20 entries deep on such a tree -- there the bound decides, as before
-           round 4; when it says "can spill" the full size is allocated AND priced in the free-memory guard above */
-        const size_t spillLanes = persistentOnly ? std::min<size_t>(laneCap, (size_t) J.nCU * 8 * 256) : (canSpill ? laneCap : (size_t) WIDE_BLOCK);
+    {   /* traversal-stack overflow: SPILL_DEPTH words per LANE of the ray kernel.  The wide tree is only walked by persistent grids (at most 8 resident
+           blocks of 256 per CU): the buffer always covers the whole grid, also when the tree's depth says that no lane can reach it -- 200 MB of 288 GB
+           against a silent out-of-bounds write should that hand-derived bound ever be off */
+        const size_t spillLanes = std::min<size_t>(laneCap, (size_t) J.nCU * 8 * 256);
         if (sd.spill.n < spillLanes * SPILL_DEPTH) sd.spill.alloc(spillLanes * SPILL_DEPTH);
         P.spillLanes = (uint32_t) std::min<size_t>(sd.spill.n / SPILL_DEPTH, 0xFFFFFFFFu);
     }
@@ -1456,12 +1389,6 @@ static void setupWavefront(RenderJob &J, unsigned long long idsFirstPass) {
     P.shadow = sd.shadow.p; P.shadowCount = sd.shadowCount.p; P.blockDead = sd.blockDead.p; P.stat = sd.stat.p; P.spill = sd.spill.p; P.capacity = capacity; P.nWaves = nWaves;
     J.rc.blockShard = sd.blockShard.p;
     wf.capacity = capacity; wf.nWaves = nWaves; wf.nBlocks = nBlocks;
-    /* big trees: closest-hit and any-hit rays share one persistent launch (measured +2..4 % on the 250k-triangle scenes;
-       on small trees the plain per-slot closest-hit launch wins, so the kernels stay separate there) */
-    wf.merged = sc->traversal == 2 && sc->bvh.nNodes >= 64;
-    if (const char *e = expEnv("PHIP_MERGED")) wf.merged = sc->traversal == 2 && atoi(e) != 0;
-    if (sc->wide) wf.merged = true;                             /* the wide tree has the merged kernel only */
-    sd.mergedRays = wf.merged;
     setupWavefrontGrids(J);
 }
 
@@ -1503,10 +1430,8 @@ static void callConstants(RenderJob &J) {
         rc.sobol.matrices = sd.sobolMat.p; rc.sobol.vdc = (const uint64_t *) sd.sobolVdc.p; rc.sobol.vdcInv = (const uint64_t *) sd.sobolVdc.p + PHIP_SOBOL_MATRIX_SIZE;
         rc.sobol.dims = p->sobol_dimensions; rc.sobol.logRes = p->sobol_log_resolution; rc.sobol.scramble = (uint32_t) p->sobol_scramble;
         rc.sobol.resolution = (float) (1u << p->sobol_log_resolution);
-        if (!(PHIP_EXPERIMENTS && expEnv("PHIP_SOBOL_BITWISE"))) {      /* (experiment builds, A/B: the row-by-row loops of sobolseq.h -- the product's device code has the byte tables only) */
-            rc.sobol.matBt = sd.sobolBt.p;
-            rc.sobol.vdcBt = (const uint64_t *) sd.sobolVdcBt.p; rc.sobol.vdcInvBt = (const uint64_t *) sd.sobolVdcBt.p + 4u * 256u;
-        }
+        rc.sobol.matBt = sd.sobolBt.p;              /* (the device code has the byte tables only: dv_math.h) */
+        rc.sobol.vdcBt = (const uint64_t *) sd.sobolVdcBt.p; rc.sobol.vdcInvBt = (const uint64_t *) sd.sobolVdcBt.p + 4u * 256u;
     } else if (p->sampler == PHIP_SAMPLER_STRATIFIED) {
         const unsigned n = J.sampleTotal();
         unsigned r = 1; while (r * r < n) ++r;
@@ -1516,7 +1441,7 @@ static void callConstants(RenderJob &J) {
         RinvTab &T = rc.rinv;
         T.primes = sd.rinvPrimes.p; T.perm = p->qmc_permutations ? sd.rinvPerm.p : nullptr; T.permOffset = sd.rinvOffsets.p; T.dims = p->qmc_dimensions;
         T.invPerm2 = sd.rinvInvPerm2; T.invPerm3 = sd.rinvInvPerm3;
-        if (sd.rinvTabDims && !expEnv("PHIP_RINV_DIGITWISE")) {     /* (A/B: the digit-by-digit loops of qmc.cpp) */
+        if (sd.rinvTabDims) {
             T.dimInfo = sd.rinvDimInfo.p; T.chunk = sd.rinvChunk.p; T.fac = sd.rinvFac.p; T.pw = sd.rinvPw.p; T.tabDims = sd.rinvTabDims;
         }
         const uint32_t res[2] = { (uint32_t) J.D.film.width, (uint32_t) J.D.film.height };
@@ -1596,36 +1521,13 @@ static FusedPass fusedPass(RenderJob &J, uint32_t sppDone) {
     return cancelled ? FusedPass::Cancelled : FusedPass::Done;
 }
 
-/* The ray kernel(s) of one wavefront iteration */
+/* The ray kernel of one wavefront iteration: the closest-hit and the any-hit rays in one persistent launch */
 static void launchRayKernels(RenderJob &J) {
-    phip_scene *sc = J.sc; SceneDev &sd = J.sd; const WavefrontPlan &wf = J.wf; hipStream_t stream = J.stream;
-    [[maybe_unused]] const dim3 block(BLOCK);
-    if (wf.merged) {
-        if (J.timing) J.evTrace.record(stream);
-        if (sc->wide) {
-            HIP_TRY(hipMemsetAsync(sd.drawCounters.p, 0, 2 * RAY_SHARDS * RAY_SHARD_STRIDE * sizeof(unsigned int), stream));
-            hipLaunchKernelGGL(k_rays_w, wf.pgridRays, dim3(WIDE_BLOCK), wf.wideLds, stream, J.D, J.P, sd.L.p, sd.drawCounters.p);
-        }
-#if PHIP_EXPERIMENTS
-        else hipLaunchKernelGGL(k_rays_p, wf.pgridRays, block, wf.ldsBytes, stream, J.D, J.P, sd.L.p);
-#endif
-        if (J.timing) J.evTrace.record(stream);
-    } else {
-#if PHIP_EXPERIMENTS      /* the BVH4 ray kernels of round 1 (PHIP_BVH4_RAYS=1 on a small scene, PHIP_WIDE=0 / PHIP_TRAVERSAL=lane): A/B only */
-        if (J.timing) J.evShadow.record(stream);
-        if (sc->traversal != 2) hipLaunchKernelGGL(k_shadow, wf.grid, block, wf.ldsBytes, stream, J.D, J.P, sd.L.p); else
-        hipLaunchKernelGGL(k_shadow_p, wf.pgrid, block, wf.ldsBytes, stream, J.D, J.P, sd.L.p);
-        if (J.timing) J.evShadow.record(stream);
-        if (J.timing) J.evTrace.record(stream);
-        if (sc->traversal == 2 && sc->bvh.nNodes >= 64) hipLaunchKernelGGL(k_trace_p<false>, wf.pgridTrace, block, wf.ldsBytes, stream, J.D, J.P);
-        else if (sc->traversal == 2 && wf.forcePersist) hipLaunchKernelGGL(k_trace_p<true>, wf.pgridTrace, block, wf.ldsBytes, stream, J.D, J.P);
-        else
-        hipLaunchKernelGGL(k_trace, wf.grid, block, wf.ldsBytes, stream, J.D, J.P);
-        if (J.timing) J.evTrace.record(stream);
-#else
-        throw std::runtime_error("internal error: no ray kernel for this scene (the wide tree is missing)");
-#endif
-    }
+    SceneDev &sd = J.sd; const WavefrontPlan &wf = J.wf; hipStream_t stream = J.stream;
+    if (J.timing) J.evTrace.record(stream);
+    HIP_TRY(hipMemsetAsync(sd.drawCounters.p, 0, 2 * RAY_SHARDS * RAY_SHARD_STRIDE * sizeof(unsigned int), stream));
+    hipLaunchKernelGGL(k_rays_w, wf.pgridRays, dim3(WIDE_BLOCK), wf.wideLds, stream, J.D, J.P, sd.L.p, sd.drawCounters.p);
+    if (J.timing) J.evTrace.record(stream);
 }
 
 /* One pass on the wavefront kernels: the pool's slots draw sample ids until none is left, one vertex of every live path per iteration */
@@ -1638,8 +1540,7 @@ static void wavefrontPass(RenderJob &J) {
     /* static share: the first 3/4 of every slot's samples; the remainder is handed out dynamically */
     {
         const unsigned long long perSlot = rc.totalIds / capacity;
-        unsigned long long staticPerSlot = perSlot - perSlot / 4;
-        if (const char *e = expEnv("PHIP_STATIC_PERCENT")) staticPerSlot = perSlot * (unsigned long long) atoi(e) / 100;
+        const unsigned long long staticPerSlot = perSlot - perSlot / 4;
         rc.staticIds = staticPerSlot * capacity;
         const unsigned long long dyn = rc.totalIds - rc.staticIds;
         rc.shardIds = (dyn + DYN_SHARDS - 1) / DYN_SHARDS;
@@ -1712,23 +1613,14 @@ static void filmPass(RenderJob &J, int acc) {
     if (J.timing) J.evFilm.record(stream);
     const dim3 fg((W + 15) / 16, (H + 15) / 16);
     const int reach = (int) std::floor(D.film.radius + 0.5f);
-    const char *fv = expEnv("PHIP_FILM_V1"); (void) fv;       /* experiment hook: the round-2 tiled kernel */
-    const bool splat = reach <= 2 && tileShift >= 4 && bs == (1 << tileShift) && sd.nLocalTiles > 0 && !expEnv("PHIP_FILM_GATHER");     /* PHIP_FILM_GATHER: the tiled gathers of rounds 2 / 3 (A/B) */
+    const bool splat = reach <= 2 && tileShift >= 4 && bs == (1 << tileShift) && sd.nLocalTiles > 0;
     if (splat) {
         if (reach <= 1) launchFilmSplat<1>(J, fg, acc);
         else launchFilmSplat<2>(J, fg, acc);
     } else if (J.qmc)
         hipLaunchKernelGGL(k_film<true>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut,
                            acc, sd.invalid.p);
-#if PHIP_EXPERIMENTS
-    else if (reach <= 2 && bs >= FILM_TILE + 2 * std::max(reach, 1) && !expEnv("PHIP_FILM_GENERIC") && !(fv && atoi(fv))) {
-        if (reach <= 1)
-            hipLaunchKernelGGL(k_film_tiled2<1>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut, acc, sd.invalid.p);
-        else
-            hipLaunchKernelGGL(k_film_tiled2<2>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut, acc, sd.invalid.p);
-    }
-#endif
-    else if (reach <= FILM_MAX_REACH && !expEnv("PHIP_FILM_GENERIC"))
+    else if (reach <= FILM_MAX_REACH)
         if (reach <= 2)
             hipLaunchKernelGGL(k_film_tiled<2>, fg, block, 0, stream, D, rc, (const float4 *) sd.L.p, (const int32_t *) sd.tileSlot.p, tilesX, dOut,
                                acc, sd.invalid.p, reach);
@@ -1803,12 +1695,12 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
     unsigned long long inv = 0;
     HIP_TRY(hipMemcpy(&inv, sd.invalid.p, sizeof(inv), hipMemcpyDeviceToHost));
     st.invalid_samples = inv;
-    st.trace_kernel_ms = J.evTrace.sumPairs(); st.shadow_kernel_ms = J.evShadow.sumPairs();
+    st.trace_kernel_ms = J.evTrace.sumPairs(); st.shadow_kernel_ms = 0.0;      /* (k_rays_w casts the shadow rays too: trace_kernel_ms) */
     st.shade_kernel_ms = J.evShade.sumPairs(); st.film_kernel_ms = J.evFilm.sumPairs(); st.fused_kernel_ms = J.evFused.sumPairs();
     st.fused = J.F.on ? 1u : 0u; st.n_devices = 1;
     st.vertex_traced = J.wf.shadeTrace ? 1u : 0u;
     st.render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - J.t0).count();
-    algorithmicBytes(J.wf.merged, st, (double) J.W * J.H, sc->wide);
+    algorithmicBytes(J.wf.capacity != 0 /* the wavefront kernels ran */, st, (double) J.W * J.H);
     if (stats) *stats = st;
     return J.cancelled ? PHIP_ERR_CANCELLED : PHIP_OK;
 }
@@ -2237,12 +2129,7 @@ int phip_trace(phip_scene *scene, const phip_ray *rays, size_t n, phip_hit *hits
             HIP_TRY(hipMemset(stat.p, 0, stat.n * sizeof(unsigned long long)));
             P.stat = stat.p; P.spill = spill.p; P.spillLanes = (uint32_t) (spill.n / SPILL_DEPTH);
             ev.record(0);
-            if (scene->wide) hipLaunchKernelGGL(k_raycast_w, dim3((unsigned) ((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), traversalLdsBytes(sd.dev), 0, sd.dev, (const phip_ray *) dr.p, m, dh.p, dz.p, P);
-#if PHIP_EXPERIMENTS
-            else hipLaunchKernelGGL(k_raycast, dim3((unsigned) ((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), traversalLdsBytes(sd.dev), 0, sd.dev, (const phip_ray *) dr.p, m, dh.p, dz.p, P);
-#else
-            else throw std::runtime_error("internal error: no ray kernel for this scene (the wide tree is missing)");
-#endif
+            hipLaunchKernelGGL(k_raycast_w, dim3((unsigned) ((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), traversalLdsBytes(sd.dev), 0, sd.dev, (const phip_ray *) dr.p, m, dh.p, dz.p, P);
             ev.record(0);
             HIP_TRY(hipMemsetAsync(sd.counters.p, 0, sizeof(Counters), 0));
             hipLaunchKernelGGL(k_reduce_stats, dim3(ST_COUNT, REDUCE_SPLIT), dim3(256), 0, 0, P, sd.counters.p, 0);
@@ -2260,7 +2147,7 @@ int phip_trace(phip_scene *scene, const phip_ray *rays, size_t n, phip_hit *hits
             out_stats->closest_rays = hits ? n : 0; out_stats->shadow_rays = occluded ? n : 0;
             out_stats->trace_kernel_ms = ev.sumPairs(); out_stats->iterations = (uint32_t) ((n + CHUNK - 1) / CHUNK);
             out_stats->n_devices = 1;
-            algorithmicBytes(false, *out_stats, 0.0, scene->wide);
+            algorithmicBytes(false, *out_stats, 0.0);
         }
         return PHIP_OK;
     } catch (const std::exception &e) {

@@ -1,6 +1,6 @@
 /*
  * phip_mega.hip -- k_mega<materials, strictNormals, traversal form, QMC> (k_mega.h): the fused single-kernel path.  Compiled twice (phip_common.h):
- *   -DMEGA_PART=0  scenes that fit LDS: BVH4 walk / leaf tables (FLAT 0 .. 3)
+ *   -DMEGA_PART=0  scenes that fit LDS: the packed leaf tables (FLAT 2 / 3)
  *   -DMEGA_PART=1  round 6: scenes whose tree stays in memory -- the compressed 8-wide tree walked from L2 (FLAT 4 / 5: k_wide_wave.h)
  *   -DMEGA_PART=2  round 6: the `direct` integrator in the same kernel (k_mega<.., DIRECT = true>), packed leaf tables and the tree in memory
  */
@@ -19,24 +19,19 @@
 typedef void (*MegaKernel)(DevScene, MegaParams, RenderConst, float4 *);
 
 #if MEGA_PART == 0
-/* Leaf BSDF models: diffuse only (every traversal form), or all three (round 5) on the packed leaf table -- the Cornell box with a glass and a copper block.
+/* Leaf BSDF models: diffuse only, or all three (round 5) -- the Cornell box with a glass and a copper block.
    (Round 2 measured "more than 256 VGPRs" for the microfacet / dielectric code next to the traversal; since then the traversal became the dealt table pass,
    the work counters moved to LDS and the camera samples to a queue: k_mega<MM_ALL, false, 2, false> builds at 128 VGPRs with 16 B of scratch, four waves.)
    A scene with glass but no copper runs the build that also knows copper: one more material set, not three. */
 template <bool QMC> static MegaKernel megaKernelOf(int materialMask, bool strictNormals, int flat) {
     if (materialMask & MM_ALL) {
-        if (flat == 3) return MEGA_BALANCE ? (strictNormals ? k_mega<MM_ALL, true, 3, QMC> : k_mega<MM_ALL, false, 3, QMC>) : nullptr;
+        if (flat == 3) return strictNormals ? k_mega<MM_ALL, true, 3, QMC> : k_mega<MM_ALL, false, 3, QMC>;
         if (flat == 2) return strictNormals ? k_mega<MM_ALL, true, 2, QMC> : k_mega<MM_ALL, false, 2, QMC>;
         return nullptr;
     }
-    if (flat == 3) return MEGA_BALANCE ? (strictNormals ? k_mega<0, true, 3, QMC> : k_mega<0, false, 3, QMC>) : nullptr;
+    if (flat == 3) return strictNormals ? k_mega<0, true, 3, QMC> : k_mega<0, false, 3, QMC>;
     if (flat == 2) return strictNormals ? k_mega<0, true, 2, QMC> : k_mega<0, false, 2, QMC>;
-#if PHIP_EXPERIMENTS      /* the BVH4 walk and the per-lane leaf table in LDS (rounds 2-3): since round 6 every scene past the packed leaf table's 64 records is on the 8-wide tree (FLAT 4 / 5) */
-    if (flat) return strictNormals ? k_mega<0, true, 1, QMC> : k_mega<0, false, 1, QMC>;
-    return strictNormals ? k_mega<0, true, 0, QMC> : k_mega<0, false, 0, QMC>;
-#else
-    return nullptr;
-#endif
+    return nullptr;      /* (every scene past the packed leaf table's 64 records is on the 8-wide tree: FLAT 4 / 5) */
 }
 #define MEGA_ENTRY(name) name
 #elif MEGA_PART == 2

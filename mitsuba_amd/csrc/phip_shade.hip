@@ -47,7 +47,7 @@ void SHADE_CAT(phipLaunchShadeF, SHADE_FEAT)(bool strictNormals, int materialMas
                                              const DevScene &S, const PathPool &P, const RenderConst &rc, float4 *L) {
     int tables = 0;
 #if SHADE_FEAT == 0
-    if (S.emitterTabSize <= EMITTER_LDS_FLOATS && !(PHIP_EXPERIMENTS && getenv("PHIP_SHADE_FLAT_TABLES"))) tables = S.nMaterials <= MATERIAL_LDS_MAX ? 1 : 2;
+    if (S.emitterTabSize <= EMITTER_LDS_FLOATS) tables = S.nMaterials <= MATERIAL_LDS_MAX ? 1 : 2;
 #endif
     const ShadeKernel k = strictNormals ? SHADE_CAT(phipShadeKernelS1F, SHADE_FEAT)(materialMask, tables) : SHADE_CAT(phipShadeKernelS0F, SHADE_FEAT)(materialMask, tables);
     hipLaunchKernelGGL(k, grid, dim3(BLOCK), 0, stream, S, P, rc, L);

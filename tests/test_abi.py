@@ -51,6 +51,28 @@ def test_product_library_reads_no_fault_knob():
     assert b"PHIP_TEST_FAULT_WAVES" in data and b"PHIP_TEST_FAULT_PASS" in data and b"PHIP_TEST_FAULT_SHORT" in data
 
 
+def test_sources_read_the_documented_environment_only():
+    """One algorithm per job: no source under csrc/ carries an experiment build (PHIP_EXPERIMENTS, expEnv) and every name handed to getenv is one that
+    DESIGN.md 9 documents -- debug output, the pass budget, the BVH builder's parameters, and the `fault` test library's knobs."""
+    allowed = {"PHIP_DEBUG_TIMING", "PHIP_MAX_PASS_SAMPLES",
+               "PHIP_BVH_MAXLEAF", "PHIP_BVH_CTRAV", "PHIP_BVH_ALPHA", "PHIP_BVH_SPATIAL", "PHIP_BVH_THREADS", "PHIP_BVH_OPT", "PHIP_BVH_OPT_POPS",
+               "PHIP_TEST_FAULT_WAVES", "PHIP_TEST_FAULT_PASS", "PHIP_TEST_FAULT_SHORT"}
+    csrc = os.path.join(ROOT, "mitsuba_amd", "csrc")
+    names = [n for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".h", ".inl"))]
+    assert names
+    calls = 0
+    for name in names:
+        src = open(os.path.join(csrc, name)).read()
+        src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+        assert "PHIP_EXPERIMENTS" not in src and "expEnv" not in src, name
+        for arg in re.findall(r"\bgetenv\s*\(([^)]*)\)", src):
+            calls += 1
+            lit = re.fullmatch(r'\s*"([^"]*)"\s*', arg)
+            assert lit, "%s: getenv(%s) does not name its variable" % (name, arg)
+            assert lit.group(1) in allowed, "%s reads %s" % (name, lit.group(1))
+    assert calls                                                    # (the pattern still finds the calls)
+
+
 def test_struct_sizes_match_ctypes_mirror(phip):
     structs = [A.phip_material, A.phip_shape, A.phip_emitter, A.phip_camera, A.phip_film, A.phip_scene_desc,
                A.phip_render_params, A.phip_stats, A.phip_ray, A.phip_hit, A.phip_accel_info]

@@ -50,7 +50,7 @@ def test_ray_kernel_of_the_big_scenes_fits_seven_waves_per_simd():
     assert k["vgprs"] <= 512 // waves // 8 * 8, k                  # 72: the allocation granule is 8 registers
     assert blocks_per_cu_by_sgprs(k["sgprs"]) >= waves, k           # the persistent grid is sized for `waves` blocks per CU
     stack = int(re.search(r"#define WIDE_STACK_LDS (\d+)", src).group(1)); cache = int(re.search(r"#define WIDE_NODE_CACHE_MAX (\d+)", src).group(1))
-    deal = 4 * (64 * 8 + 64 * 8 + 256 * 2) if re.search(r"#define WIDE_DEAL 1", src) else 0      # WD_WAVE_BYTES per wave: slots, (u, v), work list
+    deal = 4 * (64 * 8 + 64 * 8 + 256 * 2)                         # WD_WAVE_BYTES per wave: slots, (u, v), work list of the dealt triangle rounds
     assert waves * (stack * 8 * 256 + cache * 80 + deal + k["lds"]) <= 160 * 1024      # ... and their LDS (stack + node cache + triangle rounds + counters) fits the CU
     # the standalone ray cast of phip_trace on the same tree
     rc = next(v for name, v in res.items() if name.startswith("_Z11k_raycast_w"))
@@ -79,7 +79,7 @@ def test_fused_kernel_keeps_four_waves_without_scratch():
             limit = (112 if qmc else 64) if allmat else (((40 if strict else 32) if not packed else (24 if strict else 8)) if qmc else 0)
             assert v["vgprs"] <= 128 and v["scratch"] <= limit, (name, v)
             assert 4 * (v["lds"] + 12 * 1024) <= 160 * 1024, (name, v)      # four blocks per CU with the Cornell box's 11 KB of dynamic LDS (tables, records, flat table)
-    assert n == 16                                                  # {diffuse, all materials} x strictNormals x {packed flat table of <= 32 / <= 64 records} x {counter stream, QMC} (round 6: the BVH4 walk and the per-lane leaf table in LDS are experiment builds -- scenes past 64 records are on the 8-wide tree)
+    assert n == 16                                                  # {diffuse, all materials} x strictNormals x {packed flat table of <= 32 / <= 64 records} x {counter stream, QMC} (the BVH4 walk and the per-lane leaf table in LDS, forms 0 and 1, are gone -- scenes past 64 records are on the 8-wide tree)
 
 
 def test_shading_kernels_of_the_metric_configurations_keep_their_waves():

@@ -2,8 +2,7 @@
 # Builds an alternative libphip (same sources, extra flags) next to the product for A/B runs on the GPU box:
 #   [MAIN_FLAGS=..] [MEGA_FLAGS=..] [MEGAW_FLAGS=..] [SHADE_FLAGS=..] tools/build_variant.sh <tag> [flags for every unit...]
 #   ->  mitsuba_amd/_build/libphip_<tag>.so   (load it with PHIP_LIB=...)
-# Units whose flags equal the product's are not recompiled (the product's objects are linked).  Experiment builds (the measured alternatives of DESIGN.md 9:
-# earlier kernel generations, algorithm-selecting environment variables) add -DPHIP_EXPERIMENTS=1 to every unit:  tools/build_variant.sh exp -DPHIP_EXPERIMENTS=1
+# Units whose flags equal the product's are not recompiled (the product's objects are linked).
 set -e
 tag=$1; shift
 root=$(cd "$(dirname "$0")/.." && pwd); b=$root/mitsuba_amd/_build; c=$root/mitsuba_amd/csrc

@@ -1,7 +1,8 @@
 #!/bin/bash
 # A/B of library variants on the GPU box, one gpurun call: the product first, then every mitsuba_amd/_build/libphip_*.so built by
-# tools/build_variant.sh (same sources, extra -D flags), each on the workloads below.  Extra environment for a row: A/B rows of the form
-# "label VAR=value ..." in the AB_ENV variable, separated by ';' (e.g. AB_ENV="nosort PHIP_SHADE_SORT=0;pool8M PHIP_POOL=8388608").
+# tools/build_variant.sh (same sources, extra -D flags: e.g. `tools/build_variant.sh w6 -DWIDE_WAVES=6`), each on the workloads below.  The library reads no
+# algorithm-selecting environment variable: an alternative is a variant built with its -D flag.  Extra environment for a row (the documented knobs of DESIGN.md 9):
+# rows of the form "label VAR=value ..." in the AB_ENV variable, separated by ';' (e.g. AB_ENV="onepass PHIP_MAX_PASS_SAMPLES=4294967295;timing PHIP_DEBUG_TIMING=1").
 #   WORKLOADS="atrium 64;glass 128;cornell 256" bash tools/gpu_ab.sh
 # (round 3's one-off experiment scripts gpu_r3a..q.sh were folded into this one; their outputs are profiles/r03_gpu_call_logs.txt)
 b=$PWD/mitsuba_amd/_build

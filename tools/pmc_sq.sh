@@ -1,6 +1,6 @@
 #!/bin/bash
 # SQ counter passes (issue / wait / lane utilisation) for one gpu_scenes.py scene.
-# usage (on the GPU box, from the repo root): bash tools/pmc_sq.sh <scene> <outdir> [tag]   [SPP=.. PHIP_MEGA=.. in the env]
+# usage (on the GPU box, from the repo root): bash tools/pmc_sq.sh <scene> <outdir> [tag]   [SPP=.. in the env]
 # Counters only with --kernel-trace (never with sys/hip/hsa tracing, see the gpurun rules).
 sc=$1; out=$2; tag=${3:-$sc}; root=$(pwd); mkdir -p $out; cd /tmp; export TMPDIR=/tmp
 i=0

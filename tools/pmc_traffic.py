@@ -37,17 +37,10 @@ def run(counter, tag, cmd):
 
 
 sys.path.insert(0, ROOT)
-if os.environ.get("PHIP_POOL"):
-    # the pool-size hook is read by experiment builds only (-DPHIP_EXPERIMENTS=1: expEnv is a constant in the product) -- a run against the product would
-    # record an override that never applied
-    _lib = os.environ.get("PHIP_LIB") or os.path.join(ROOT, "mitsuba_amd", "_build", "libphip.so")
-    if not os.path.exists(_lib) or b"PHIP_POOL" not in open(_lib, "rb").read():
-        sys.exit("pmc_traffic.py: PHIP_POOL is set, but %s does not read it (the product ignores algorithm-selecting environment variables): build an experiment "
-                 "library with `tools/build_variant.sh exp -DPHIP_EXPERIMENTS=1` and pass it as PHIP_LIB, or unset PHIP_POOL" % _lib)
 from mitsuba_amd import _ffi as _ffi_id  # noqa: E402  (the id compiled into the library that is being profiled: read from the file, no GPU call)
-res = {"build_id": _ffi_id.built_id(os.environ.get("PHIP_LIB")), "workload": bench_name, "scene_key": workload, "spp_override": spp or None, "pool_slots_override": os.environ.get("PHIP_POOL"),
+res = {"build_id": _ffi_id.built_id(os.environ.get("PHIP_LIB")), "workload": bench_name, "scene_key": workload, "spp_override": spp or None,
        "units": "FETCH_SIZE / WRITE_SIZE are reported in KiB",
-       "note": "per-launch figures: the path pool must have the size of the full job (8 M slots for jobs >= 256 M samples, else 4 M) -- set PHIP_POOL when spp is reduced"}
+       "note": "per-launch figures: the path pool must have the size of the full job (the library sizes it by the job: a reduced spp gets a smaller pool)"}
 cf, _ = run("FETCH_SIZE", "cal_fetch", cal_cmd)
 cw, _ = run("WRITE_SIZE", "cal_write", cal_cmd)
 # gather: every 16-B read misses everything; the HBM transfer unit is a 64-B sector -> n*64 B expected (128 B if whole lines are fetched)
