@@ -24,6 +24,17 @@
  * lane 0 (guided: the chunk shrinks towards the end of the pass so that the waves finish together) and deals them to its
  * lanes in order -- 64 consecutive ids are one 8x8 pixel patch of one sample index (ids are block-major, then sample, then
  * Morton index), so the camera rays of a wave are coherent.
+ *
+ * The sections of the persistent loop, in order (each under a comment of that name):
+ *   withdraw      MAILBOX: the server's free lanes take vertices out of the S-box, a client's free lanes claim continued paths from the R-box (MailboxEntry::load)
+ *   regeneration  draw a chunk of ids | prepare 64 camera samples into the wave's queue | pop into the free lanes
+ *   idle or done  nothing in the wave's lanes: done, or look again -- bounded by the progress signature (the wave gives up)
+ *   closest hit   WIDE: traceWidePool with the deferred shadow ray of the previous pass, which is settled here | packed leaf table: traverseFlat2W
+ *   deposit       MAILBOX: a client hands its copper vertices to the S-box (MailboxEntry::store)
+ *   vertex        shadeVertex / directVertex
+ *   shadow ray    WIDE: deferred to the next pass, a path that ended parks its accumulator | traced now; then the end of the sample: L[id] = accumulator
+ *   hand back     MAILBOX: the block's live ids; the server returns continued paths to the R-box
+ * and after the loop the work counters, the measurement builds' rows and the row of the waves that gave up.
  */
 
 #ifndef MEGA_PROFILE
@@ -52,16 +63,47 @@
 #endif
 /* MB_NS = 64 entries of the S-box (dynamic LDS, behind the work lists; k_pool.h) and MB_NR of the R-box (static: what four blocks per CU leave) */
 #define MB_NR 48u
-/* MB_DW = 24 (k_pool.h): dwords per mailbox entry (S-box: hit 4, direction 3, throughput 4, MIS 2, id, pixel, k, state, accumulator 4 = 21; R-box: origin + mint 4,
-                                        direction + maxt 4 instead of hit and direction = 22) */
+/* A mailbox entry: [MB_DW rows][N entries] of LDS words, entry e at x = box + e (N: MB_NS for the S-box, MB_NR for the R-box).  THE one statement of the two layouts --
+   S-box (a vertex that waits to be shaded): hit 4, direction 3;  R-box (a continued path): origin + mint 4, direction + maxt 4;  then in both: throughput 4, MIS 2, id, pixel,
+   k, state, accumulator 4, and in rows 22 and 23 the sample's sequence index (the QMC builds carry it along; row 21 of an S-box entry is unused).  seq: the lane's word in row 0 of its wave's
+   table ldsSeq[wave][2][64]; the word in row 1 lies SEQ_ROW further */
+template <bool RBOX, uint32_t N> struct MailboxEntry {
+    enum { SEQ_ROW = 64 };
+    enum { HEAD = 0, DIR = 4, THR = RBOX ? 8 : 7, MIS = THR + 4, ID = MIS + 2, PIXEL, K, STATE, ACCUM, LAST = ACCUM + 3, SEQ = 22 };
+    static_assert(LAST < SEQ && SEQ + 2 == MB_DW && MB_DW == 24, "a mailbox entry: the path's state lies below the two rows of the sequence index, which end the MB_DW rows k_pool.h sizes the boxes with");
+    static __device__ __forceinline__ void put(uint32_t *x, int row, float f) { x[row * N] = pm_to_bits(f); }
+    static __device__ __forceinline__ float get(const uint32_t *x, int row) { return pm_from_bits(x[row * N]); }
+    static __device__ __forceinline__ void put4(uint32_t *x, int row, const float4 &f) { put(x, row, f.x); put(x, row + 1, f.y); put(x, row + 2, f.z); put(x, row + 3, f.w); }
+    static __device__ __forceinline__ float4 get4(const uint32_t *x, int row) { return make_float4(get(x, row), get(x, row + 1), get(x, row + 2), get(x, row + 3)); }
+    template <bool QMC> static __device__ __forceinline__ void store(uint32_t *x, const PathVertex &v, const float4 &accum, const uint32_t *seq) {
+        if (RBOX) { put4(x, HEAD, v.rayO); put4(x, DIR, v.rayD); }
+        else { put4(x, HEAD, v.hit); put(x, DIR, v.rayD.x); put(x, DIR + 1, v.rayD.y); put(x, DIR + 2, v.rayD.z); }
+        put4(x, THR, v.thr);
+        put(x, MIS, v.mis.x); put(x, MIS + 1, v.mis.y);
+        x[ID * N] = v.id; x[PIXEL * N] = v.pixel; x[K * N] = v.k; x[STATE * N] = v.state;
+        put4(x, ACCUM, accum);
+        if (QMC) { x[SEQ * N] = seq[0]; x[(SEQ + 1) * N] = seq[SEQ_ROW]; }
+    }
+    template <bool QMC> static __device__ __forceinline__ void load(const uint32_t *x, PathVertex &v, float4 &accum, uint32_t *seq) {
+        if (RBOX) { v.rayO = get4(x, HEAD); v.rayD = get4(x, DIR); }
+        else { v.hit = get4(x, HEAD); v.rayD = make_float4(get(x, DIR), get(x, DIR + 1), get(x, DIR + 2), 0.0f); }
+        v.thr = get4(x, THR);
+        v.mis = make_float2(get(x, MIS), get(x, MIS + 1));
+        v.id = x[ID * N]; v.pixel = x[PIXEL * N]; v.k = x[K * N]; v.state = x[STATE * N];
+        accum = get4(x, ACCUM);
+        if (QMC) { seq[0] = x[SEQ * N]; seq[SEQ_ROW] = x[(SEQ + 1) * N]; }
+    }
+};
+typedef MailboxEntry<false, MB_NS> SBoxEntry;
+typedef MailboxEntry<true, MB_NR> RBoxEntry;
 static_assert((BLOCK / 64u) * BAL_WAVE_BYTES + MB_DW * MB_NS * sizeof(uint32_t) <= MEGA_DEAL_DWORDS * BLOCK * sizeof(uint32_t), "the S-box lies behind the work lists in the region phip.hip sizes with MEGA_DEAL_DWORDS");
 #define MEGA_CHUNK_MAX 4096u
 #define MEGA_CHUNK_MIN 64u
 
 enum { MC_SAMPLES = 0, MC_VERTICES, MC_RAYS, MC_NODE, MC_TRI, MC_SH_RAYS, MC_SH_NODE, MC_SH_TRI, MC_COUNT };
 
-template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (traverseFlat2W), 3: the same with 33..64 records (two-word masks); (0 and 1, the BVH4 walk and the per-lane leaf table: HISTORY.md)
-                                           round 6 -- 4: the compressed 8-wide tree in L2 / HBM (k_wide_wave.h: traceWidePool), emitter table and materials in LDS, 5: the same with the materials in memory */,
+template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (traverseFlat2W), 3: the same with 33..64 records (two-word masks);
+                                           4: the compressed 8-wide tree in L2 / HBM (k_wide_wave.h: traceWidePool), emitter table and materials in LDS, 5: the same with the materials in memory */,
           bool QMC /* the reference's sobol / halton / hammersley / stratified streams (FEAT bit 3 of shadeVertex) */,
           bool DIRECT = false /* round 6: MIDirectIntegrator::Li (k_shade_direct.h: directVertex) instead of the path tracer's vertex -- a lane owns a CAMERA SAMPLE through its
                                  emitter and BSDF sampling rounds; the loop, the traversals and the camera-sample queue are the same */> __global__ __launch_bounds__(BLOCK, MEGA_WAVES) void k_mega(DevScene S, MegaParams M, RenderConst rc, float4 *L) {
@@ -69,7 +111,7 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
     /* (the tree-in-memory builds have no room for the mailboxes' 10 KB at four blocks per CU, and sorting paths by BSDF model costs them more than the divergence it removes once a
        pass is dominated by a traversal whose length differs from wave to wave -- profiles/r06_gpu_call_i_*, _n_*; `direct`: the camera vertex's rounds carry the camera hit along) */
     constexpr bool MAILBOX = MM != 0 && !WIDE && !DIRECT;         /* (round 6: the QMC builds too -- their work counters became per-wave ones (WCNT: 8 KB of static LDS), which is the room the R-box needed; the sample's sequence index travels with the path) */
-    __shared__ uint32_t mbR[MAILBOX ? MB_DW * MB_NR : 1u];        /* the R-box, [MB_DW][MB_NR] (MB_DW = 24: the last two words of an entry carry the sample's sequence index in the QMC builds); the S-box lies in
+    __shared__ uint32_t mbR[MAILBOX ? MB_DW * MB_NR : 1u];        /* the R-box, [MB_DW][MB_NR] (MailboxEntry); the S-box lies in
                                                                      the dynamic LDS behind the traversals' work lists (phip.hip sizes the region) */
     __shared__ uint32_t mbState[MAILBOX ? MB_NS + MB_NR : 1u];   /* entry states, S-box then R-box: 0 empty, 2 full, 3 being read (R-box: three consumers claim by compare-and-swap) */
     __shared__ int mbLive;                                        /* sample ids drawn by the block's waves that have not ended as a sample yet (queued camera samples and paths, wherever they are) */
@@ -129,7 +171,7 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
     bool exhausted = rc.totalIds == 0;
     /* the mailboxes */
     uint32_t *mbS = WIDE ? (uint32_t *) (wideDeal + (BLOCK / 64u) * WAVE_BYTES)
-                         : (uint32_t *) (g_smem + (BLOCK / 64u) * BAL_WAVE_BYTES);      /* the S-box, [MB_DW][64], behind the four waves' work lists */
+                         : (uint32_t *) (g_smem + (BLOCK / 64u) * BAL_WAVE_BYTES);      /* the S-box, [MB_DW][MB_NS], behind the four waves' work lists */
     const bool server = MAILBOX && waveInBlock == 0u;
     bool haveHit = false;                                       /* server: the lane's path came out of the S-box with its hit */
     uint32_t idleSpins = 0, patience = 0, idleSig = 0;
@@ -193,6 +235,7 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
         const unsigned long long pfWant_ = __ballot(!alive);
 #endif
         bool skipRegen = false;
+        /* ---- withdraw: free lanes take what the mailboxes hold for this wave ---- */
         if (MAILBOX) {
             haveHit = false;
             if (__any(!alive)) {
@@ -206,14 +249,7 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
                     skipRegen = waiting;
                     uint32_t e;
                     if (waiting && mbAssign(!alive, stt == 2u, e)) {
-                        const uint32_t *x = mbS + e;
-                        v.hit = make_float4(pm_from_bits(x[0 * MB_NS]), pm_from_bits(x[1 * MB_NS]), pm_from_bits(x[2 * MB_NS]), pm_from_bits(x[3 * MB_NS]));
-                        v.rayD = make_float4(pm_from_bits(x[4 * MB_NS]), pm_from_bits(x[5 * MB_NS]), pm_from_bits(x[6 * MB_NS]), 0.0f);
-                        v.thr = make_float4(pm_from_bits(x[7 * MB_NS]), pm_from_bits(x[8 * MB_NS]), pm_from_bits(x[9 * MB_NS]), pm_from_bits(x[10 * MB_NS]));
-                        v.mis = make_float2(pm_from_bits(x[11 * MB_NS]), pm_from_bits(x[12 * MB_NS]));
-                        v.id = x[13 * MB_NS]; v.pixel = x[14 * MB_NS]; v.k = x[15 * MB_NS]; v.state = x[16 * MB_NS];
-                        accum = make_float4(pm_from_bits(x[17 * MB_NS]), pm_from_bits(x[18 * MB_NS]), pm_from_bits(x[19 * MB_NS]), pm_from_bits(x[20 * MB_NS]));
-                        if (QMC) { ldsSeq[QMC ? waveInBlock : 0][0][lane] = x[22 * MB_NS]; ldsSeq[QMC ? waveInBlock : 0][1][lane] = x[23 * MB_NS]; }
+                        SBoxEntry::load<QMC>(mbS + e, v, accum, &ldsSeq[QMC ? waveInBlock : 0][0][lane]);
                         alive = true; haveHit = true;
 #if MEGA_MB_DIAG
                         ++dgWithdrawn;
@@ -231,14 +267,7 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
                             got = __hip_atomic_compare_exchange_strong(&mbState[MB_NS + e], &expect, 3u, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         }
                         if (got) {
-                            const uint32_t *x = mbR + e;
-                            v.rayO = make_float4(pm_from_bits(x[0 * MB_NR]), pm_from_bits(x[1 * MB_NR]), pm_from_bits(x[2 * MB_NR]), pm_from_bits(x[3 * MB_NR]));
-                            v.rayD = make_float4(pm_from_bits(x[4 * MB_NR]), pm_from_bits(x[5 * MB_NR]), pm_from_bits(x[6 * MB_NR]), pm_from_bits(x[7 * MB_NR]));
-                            v.thr = make_float4(pm_from_bits(x[8 * MB_NR]), pm_from_bits(x[9 * MB_NR]), pm_from_bits(x[10 * MB_NR]), pm_from_bits(x[11 * MB_NR]));
-                            v.mis = make_float2(pm_from_bits(x[12 * MB_NR]), pm_from_bits(x[13 * MB_NR]));
-                            v.id = x[14 * MB_NR]; v.pixel = x[15 * MB_NR]; v.k = x[16 * MB_NR]; v.state = x[17 * MB_NR];
-                            accum = make_float4(pm_from_bits(x[18 * MB_NR]), pm_from_bits(x[19 * MB_NR]), pm_from_bits(x[20 * MB_NR]), pm_from_bits(x[21 * MB_NR]));
-                            if (QMC) { ldsSeq[QMC ? waveInBlock : 0][0][lane] = x[22 * MB_NR]; ldsSeq[QMC ? waveInBlock : 0][1][lane] = x[23 * MB_NR]; }
+                            RBoxEntry::load<QMC>(mbR + e, v, accum, &ldsSeq[QMC ? waveInBlock : 0][0][lane]);
                             alive = true;
 #if MEGA_MB_DIAG
                             ++dgRefill;
@@ -333,6 +362,7 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
             qHead += took; qCount -= took;
         }
         PF_END(0, pfWant_) }
+        /* ---- idle or done ---- */
         if (MAILBOX) {
             if (!__any(alive)) {
                 /* nothing in this wave's lanes: done when no id is left anywhere AND every id the block's waves drew has ended as a sample (a path may sit in a
@@ -358,13 +388,14 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
         /* ---- closest hit ---- */
         uint32_t hitCls = 0;                                    /* shade class of the record hit (the Wald record's 12th word: 0 diffuse, 1 rough conductor, 2 dielectric) */
         { PF_BEGIN
-        if (WIDE) {                                             /* every lane takes part (k_wide_wave.h) */
-            const V3 o(v.rayO.x, v.rayO.y, v.rayO.z), d(v.rayD.x, v.rayD.y, v.rayD.z);
-            float mint, maxt;
-            TravResult r;
-            V3 rcp;
-            const bool trace = alive && !(MAILBOX && haveHit) && !(DIRECT && (v.state & F_NOTRACE));      /* (DIRECT: a round without a BSDF sample has no closest-hit query) */
-            const bool go = trace & clipToSceneSel<false>(S, o, d, v.rayO.w, v.rayD.w, mint, maxt, rcp);
+        /* the query both arms share: every lane takes part in the traversal, a lane without a ray to trace with go = false */
+        const V3 o(v.rayO.x, v.rayO.y, v.rayO.z), d(v.rayD.x, v.rayD.y, v.rayD.z);
+        float mint, maxt;
+        TravResult r;
+        V3 rcp;
+        const bool trace = alive && !(MAILBOX && haveHit) && !(DIRECT && (v.state & F_NOTRACE));      /* (DIRECT: a round without a BSDF sample has no closest-hit query) */
+        const bool go = trace & clipToSceneSel<false>(S, o, d, v.rayO.w, v.rayD.w, mint, maxt, rcp);
+        if (WIDE) {                                             /* the tree in memory (k_wide_wave.h) */
             /* ... and the shadow ray of the vertex this lane shaded in the previous pass (its own path's, or that of the path that ended there) */
             const V3 so(cSh.e0.x, cSh.e0.y, cSh.e0.z), sd(cSh.e1.x, cSh.e1.y, cSh.e1.z);
             float smint = 0.0f, smaxt = 0.0f;
@@ -386,14 +417,8 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
             const uint32_t nS_ = (uint32_t) __popcll(__ballot(cPush)), nE_ = (uint32_t) __popcll(__ballot(cPend));
             if (lane == 0u) { wc[WC_SH_RAYS] += nS_; wc[WC_SAMPLES] += nE_; }
             cPush = false; cPend = false;
-        } else {                                                /* every lane takes part: the tests of the wave's rays are dealt over its lanes */
-            const V3 o(v.rayO.x, v.rayO.y, v.rayO.z), d(v.rayD.x, v.rayD.y, v.rayD.z);
-            float mint, maxt;
-            TravResult r;
+        } else {                                                /* the packed leaf table: the tests of the wave's rays are dealt over its lanes */
             uint32_t nNode = 0, nTri = 0;
-            V3 rcp;
-            const bool trace = alive && !(MAILBOX && haveHit) && !(DIRECT && (v.state & F_NOTRACE));
-            const bool go = trace & clipToSceneSel<false>(S, o, d, v.rayO.w, v.rayD.w, mint, maxt, rcp);
             traverseFlat2W<false, FLAT == 3>(flat, S.nFlatLeaves, stk.tris, wb, lane, go, o, d, rcp, mint, maxt, r, nNode, nTri);
             if (trace) {
                 v.hit = make_float4(r.t, r.u, r.v, pm_from_bits(r.prim));
@@ -404,7 +429,7 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
         }
 
         PF_END(1, __ballot(alive)) }
-        /* ---- the mailboxes: a client hands the paths that hit copper to the server (if its third of the S-box has room: otherwise it shades them itself) ---- */
+        /* ---- deposit: a client hands the paths that hit copper to the server (if its third of the S-box has room: otherwise it shades them itself) ---- */
         if (MAILBOX && !server) {
             const bool special = alive && pm_to_bits(v.hit.w) != PHIP_NO_HIT && hitCls != 0u && ((MEGA_MB_CLASSES >> (hitCls - 1u)) & 1u);
             if (__any(special)) {
@@ -413,14 +438,7 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
                 uint32_t e;
                 const bool got = mbAssign(special, stt == 0u && (lane * 3u) / MB_NS == waveInBlock - 1u, e);
                 if (got) {
-                    uint32_t *x = mbS + e;
-                    x[0 * MB_NS] = pm_to_bits(v.hit.x); x[1 * MB_NS] = pm_to_bits(v.hit.y); x[2 * MB_NS] = pm_to_bits(v.hit.z); x[3 * MB_NS] = pm_to_bits(v.hit.w);
-                    x[4 * MB_NS] = pm_to_bits(v.rayD.x); x[5 * MB_NS] = pm_to_bits(v.rayD.y); x[6 * MB_NS] = pm_to_bits(v.rayD.z);
-                    x[7 * MB_NS] = pm_to_bits(v.thr.x); x[8 * MB_NS] = pm_to_bits(v.thr.y); x[9 * MB_NS] = pm_to_bits(v.thr.z); x[10 * MB_NS] = pm_to_bits(v.thr.w);
-                    x[11 * MB_NS] = pm_to_bits(v.mis.x); x[12 * MB_NS] = pm_to_bits(v.mis.y);
-                    x[13 * MB_NS] = v.id; x[14 * MB_NS] = v.pixel; x[15 * MB_NS] = v.k; x[16 * MB_NS] = v.state;
-                    x[17 * MB_NS] = pm_to_bits(accum.x); x[18 * MB_NS] = pm_to_bits(accum.y); x[19 * MB_NS] = pm_to_bits(accum.z); x[20 * MB_NS] = pm_to_bits(accum.w);
-                    if (QMC) { x[22 * MB_NS] = ldsSeq[QMC ? waveInBlock : 0][0][lane]; x[23 * MB_NS] = ldsSeq[QMC ? waveInBlock : 0][1][lane]; }
+                    SBoxEntry::store<QMC>(mbS + e, v, accum, &ldsSeq[QMC ? waveInBlock : 0][0][lane]);
                     __hip_atomic_store(&mbState[e], 2u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                     alive = false;
 #if MEGA_MB_DIAG
@@ -489,6 +507,7 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
             alive = false;
         }
         if (WCNT && !WIDE) { const uint32_t n_ = (uint32_t) __popcll(__ballot(ended)); if (lane == 0u) wc[WC_SAMPLES] += n_; }
+        /* ---- hand back: the block's live ids, and the server's continued paths ---- */
         if (MAILBOX) {
             const int nEnded = __popcll(__ballot(ended));
             if (nEnded && lane == 0u) atomicSub(&mbLive, nEnded);
@@ -497,14 +516,7 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
                 const uint32_t stt = lane < MB_NR ? __hip_atomic_load(&mbState[MB_NS + lane], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) : ~0u;
                 uint32_t e;
                 if (mbAssign(alive, stt == 0u, e)) {
-                    uint32_t *x = mbR + e;
-                    x[0 * MB_NR] = pm_to_bits(v.rayO.x); x[1 * MB_NR] = pm_to_bits(v.rayO.y); x[2 * MB_NR] = pm_to_bits(v.rayO.z); x[3 * MB_NR] = pm_to_bits(v.rayO.w);
-                    x[4 * MB_NR] = pm_to_bits(v.rayD.x); x[5 * MB_NR] = pm_to_bits(v.rayD.y); x[6 * MB_NR] = pm_to_bits(v.rayD.z); x[7 * MB_NR] = pm_to_bits(v.rayD.w);
-                    x[8 * MB_NR] = pm_to_bits(v.thr.x); x[9 * MB_NR] = pm_to_bits(v.thr.y); x[10 * MB_NR] = pm_to_bits(v.thr.z); x[11 * MB_NR] = pm_to_bits(v.thr.w);
-                    x[12 * MB_NR] = pm_to_bits(v.mis.x); x[13 * MB_NR] = pm_to_bits(v.mis.y);
-                    x[14 * MB_NR] = v.id; x[15 * MB_NR] = v.pixel; x[16 * MB_NR] = v.k; x[17 * MB_NR] = v.state;
-                    x[18 * MB_NR] = pm_to_bits(accum.x); x[19 * MB_NR] = pm_to_bits(accum.y); x[20 * MB_NR] = pm_to_bits(accum.z); x[21 * MB_NR] = pm_to_bits(accum.w);
-                    if (QMC) { x[22 * MB_NR] = ldsSeq[QMC ? waveInBlock : 0][0][lane]; x[23 * MB_NR] = ldsSeq[QMC ? waveInBlock : 0][1][lane]; }
+                    RBoxEntry::store<QMC>(mbR + e, v, accum, &ldsSeq[QMC ? waveInBlock : 0][0][lane]);
                     __hip_atomic_store(&mbState[MB_NS + e], 2u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                     alive = false;
                 }
@@ -528,7 +540,7 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
 
 #if MEGA_MB_DIAG
     ldsCount[MC_NODE][threadIdx.x] = dgDeposit; ldsCount[MC_TRI][threadIdx.x] = dgLocal; ldsCount[MC_SH_NODE][threadIdx.x] = dgWithdrawn; ldsCount[MC_SH_TRI][threadIdx.x] = dgKept;
-    ldsCount[MC_RAYS][threadIdx.x] = dgServerPass; ldsCount[MC_SH_RAYS][threadIdx.x] = dgClientPass; ldsCount[MC_VERTICES][threadIdx.x] = dgRefill + (dgServerRegen << 0) * 0u; ldsCount[MC_SAMPLES][threadIdx.x] = dgServerRegen;
+    ldsCount[MC_RAYS][threadIdx.x] = dgServerPass; ldsCount[MC_SH_RAYS][threadIdx.x] = dgClientPass; ldsCount[MC_VERTICES][threadIdx.x] = dgRefill; ldsCount[MC_SAMPLES][threadIdx.x] = dgServerRegen;
 #endif
     /* per-wave statistics (one owner per entry, no atomics) */
     PathPool P; P.stat = M.stat; P.nWaves = M.nWaves;

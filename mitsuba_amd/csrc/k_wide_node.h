@@ -22,9 +22,6 @@
 #ifndef WIDE_NODE_STRIDE
 #define WIDE_NODE_STRIDE 5               /* uint4 per node in HBM: 5 = packed 80-byte nodes (half of them straddle two 128-byte lines), 8 = one node per 128-byte line */
 #endif
-#ifndef WIDE_PROFILE
-#define WIDE_PROFILE 0
-#endif
 #ifndef WIDE_WAVES
 #define WIDE_WAVES 7                     /* waves per SIMD of k_rays_w = blocks of 256 per CU.  Round 3: 74 VGPRs (flat loop, wave-uniform state in SGPRs, stack
                                             addresses rebuilt from the lane index: see persistentTraverseWide), six waves -- measured C3 / C4 at 128 spp, ray-kernel
