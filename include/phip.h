@@ -403,15 +403,16 @@ void  phip_host_free(void *p);
 /* RGB = sum/weight (0 where weight == 0): rgbaw[n*5] -> rgb[n*3]. Host-side helper. */
 void phip_develop(const float *rgbaw, size_t n_pixels, float *out_rgb);
 
-/* Acceleration-structure facts for DESIGN.md / bench accounting. */
+/* Acceleration-structure facts for DESIGN.md / bench accounting: n_nodes, max_depth, node_bytes (80) and sah_cost are those of the compressed 8-wide tree, which
+   every scene has; n_leaves and n_triangle_refs those of the binary tree it was collapsed from. */
 typedef struct phip_accel_info {
     uint32_t n_nodes, n_leaves, n_triangle_refs, max_depth;
     uint32_t node_bytes, triangle_bytes;
     float    sah_cost;
     float    build_ms;
-    uint32_t fits_lds;       /* 1: tree, records, emitter table and materials fit the fused kernel's LDS plan (k_mega) */
-    uint32_t fused_traversal; /* how k_mega traverses the scene: 0 = it walks the BVH4, 1 = flat table of leaf boxes, 2 / 3 = packed table with masks of
-                                 <= 32 / <= 64 Wald records, tests dealt over the wave (was `reserved`, always 0, before round 5: same layout); round 6, fits_lds = 0:
+    uint32_t fits_lds;       /* 1: leaf table, records, emitter table and materials fit the fused kernel's LDS plan (k_mega) */
+    uint32_t fused_traversal; /* how k_mega traverses the scene: 2 / 3 = packed leaf table with masks of <= 32 / <= 64 Wald records, tests dealt over the wave
+                                 (was `reserved`, always 0, before round 5: same layout; 0 and 1 were a walk of the BVH4 and a table of plain leaf boxes: retired); round 6, fits_lds = 0:
                                  4 / 5 = k_mega can walk the compressed 8-wide tree from memory (materials in LDS / in memory; PHIP_FLAG_FUSED_ANY) */
 } phip_accel_info;
 int  phip_scene_accel_info(const phip_scene *scene, phip_accel_info *out);

@@ -3,24 +3,22 @@
  *
  * The reference answers ray queries with a SAH kd-tree (include/mitsuba/render/gkdtree.h,
  * sahkdtree3.h); a kd-tree's pointer-chasing, duplicated references and 48-entry Havran stack
- * are a poor fit for 64-wide wavefronts.  The MI355X design instead uses a binary BVH built
- * with binned SAH on the host, flattened into 64-byte nodes that hold BOTH children's boxes
- * (one node visit = four coalescable 16-byte loads, two slab tests), with triangles stored in
- * leaf order as 48-byte Wald records (the reference's TriAccel arithmetic,
- * include/mitsuba/render/triaccel.h:61-93, so that (t,u,v) are bit-identical to the CPU path).
- * Closest-hit results do not depend on the structure, only on the triangle test.
+ * are a poor fit for 64-wide wavefronts.  Closest-hit results do not depend on the structure, only
+ * on the triangle test, so the device gets structures of its own.  What buildBVH makes, in order:
+ *   1. a binary BVH by binned SAH (Builder::build); from SPATIAL_MIN_TRIS triangles on with spatial splits
+ *      (Builder::buildSpatial, Stich et al. 2009) and one pass of bounded reinsertion (Reinserter, Bittner et al. 2013).
+ *      It is an intermediate: 16 floats per node, both children's PADDED boxes (pad()) and their references --
+ *      (l.min.xyz l.max.x | l.max.yz r.min.xy | r.min.z r.max.xyz | bits(l ref) bits(r ref) 0 0).  HostBVH::maxDepth is ITS depth;
+ *   2. the triangles in leaf order as 48-byte Wald records (the reference's TriAccel arithmetic,
+ *      include/mitsuba/render/triaccel.h:61-93, so that (t,u,v) are bit-identical to the CPU path);
+ *   3. for a tree of at most LEAF_LIST_MAX leaves and records, the list of its leaves as (reference, padded box): all the
+ *      LDS-resident kernels need of the tree -- phip.hip packs it into their leaf table (k_traverse.h: flat2Pass1);
+ *   4. the compressed 8-wide tree every scene's ray kernels walk: the SAH-optimal collapse of the binary tree (buildWide),
+ *      with the records regrouped per wide node.
+ * The binary tree is released at the end; the 4-wide tree that was collapsed from it until the last kernel that walked one was retired is gone.
  *
- * The binary tree is then collapsed into a 4-wide BVH (a child that is an inner node is replaced by
- * its two children, largest surface area first) so that one 128-byte node -- exactly one cache line,
- * eight coalescable 16-byte loads -- yields four slab tests per dependent memory round trip.
- *
- * BVH4 node layout (8 x float4, children in the four lanes of each vector):
- *   n0 = min.x[4]  n1 = min.y[4]  n2 = min.z[4]  n3 = max.x[4]  n4 = max.y[4]  n5 = max.z[4]
- *   n6 = bits(child ref[4])   n7 = unused
- *   empty child slots have min = +inf, max = -inf (never hit).
- * (intermediate BVH2 node, 4 x float4: l.min.xyz l.max.x | l.max.yz r.min.xy | r.min.z r.max.xyz | refs)
  * child reference: >= 0 inner-node index; < 0 leaf: ~ref = (firstTri << 3) | (count - 1), count in 1..8.
- * Triangle record (3 x float4): (bits(k), n_u, n_v, n_d) (a_u, a_v, b_nu, b_nv) (c_nu, c_nv, bits(globalPrim), 0)
+ * Triangle record (3 x float4): (bits(k), n_u, n_v, n_d) (a_u, a_v, b_nu, b_nv) (c_nu, c_nv, bits(globalPrim), 0 -- phip.hip writes the shade class there)
  */
 #pragma once
 #include <vector>
@@ -38,6 +36,7 @@ namespace pt {
 
 struct BuildTri { float bmin[3], bmax[3], c[3]; uint32_t prim; };
 constexpr uint32_t SPATIAL_MIN_TRIS = 4096;     /* scenes from this size on are built with spatial splits */
+constexpr uint32_t LEAF_LIST_MAX = 64;          /* HostBVH::leaves is collected for trees of at most this many leaves and Wald records */
 
 struct HostBVH {
     /* 8-wide tree with quantised child boxes for the big-scene ray kernels (k_wide.h), after Ylitie, Karras & Laine,
@@ -45,15 +44,17 @@ struct HostBVH {
     std::vector<uint32_t> wnodes; /* 20 dwords per node */
     std::vector<float> wtris;     /* 12 floats per triangle record, grouped per wide node (each node's leaf triangles are consecutive) */
     uint32_t nWNodes = 0, wMaxDepth = 0, nWTris = 0; float wSahCost = 0;
-    std::vector<float> nodes;     /* 32 floats per BVH4 node */
-    std::vector<float> nodes2;    /* 16 floats per intermediate BVH2 node */
+    std::vector<float> nodes2;    /* 16 floats per node of the intermediate binary tree (released when the wide tree is built) */
     uint32_t nNodes2 = 0;
     std::vector<float> tris;      /* 12 floats per triangle record, leaf order */
-    uint32_t nNodes = 0, nLeaves = 0, nTriRefs = 0, maxDepth = 0;
+    uint32_t nLeaves = 0, nTriRefs = 0, maxDepth = 0;      /* maxDepth: the binary tree's, as the builder recorded it */
+    /* the binary tree's leaves, depth first, left child first: what the LDS-resident kernels' packed leaf table is made of (phip.hip).  Only for a tree
+       with an inner node, at most LEAF_LIST_MAX leaves and at most LEAF_LIST_MAX records; empty otherwise */
+    struct LeafBox { int32_t ref; float mn[3], mx[3]; };
+    std::vector<LeafBox> leaves;
     float sceneMin[3], sceneMax[3];       /* enlarged like gkdtree.h:1213-1220 */
     float tightMin[3], tightMax[3];
-    float sahCost = 0, buildMs = 0;
-    int32_t rootRef = 0;
+    float buildMs = 0;
 };
 
 namespace detail {
@@ -172,7 +173,7 @@ struct Builder {
        plane x = 0 (round 2: ties on such planes were decided by the traversal order), hence the term in the scene's extent. */
     float extent[3] = { 0, 0, 0 };
     /* ... and, round 6, a term in the CAMERA's position: the slab distance of a plane is (plane - o) * rcp, whose rounding grows with |o|, and the camera's are the only rays that
-       start outside the scene box -- a telephoto view from thousands of scene extents away used to be safe only on the BVH4 of the small scenes, whose kernels left the product
+       start outside the scene box -- a telephoto view from thousands of scene extents away used to be safe only on the 4-wide tree that was walked on the small scenes, whose kernels left the product
        when every scene got the wide tree (tests/test_gpu_parity.py: far camera; the packed leaf table pads its half extents the same way, phip.hip) */
     float camPad[3] = { 0, 0, 0 };
     void pad(Box &b) const {
@@ -575,7 +576,7 @@ struct Reinserter {
 /*
  * Compressed wide BVH (CWBVH, Ylitie et al. 2017), built by collapsing the binary SAH tree.  The ray kernels of the big scenes
  * are bound by the CU's vector-memory path (every lane of a wave fetches its own node: 64 cache lines per load instruction),
- * so what counts is bytes and dependent round trips per ray: one 80-byte node replaces ~2.3 of the 128-byte BVH4 nodes.
+ * so what counts is bytes and dependent round trips per ray: one 80-byte node replaces ~2.3 of the 128-byte nodes of the 4-wide tree that was walked before.
  *
  * Node = 5 x 16 bytes:
  *   [0] p.x p.y p.z (float: the node box's lower corner)   e.x | e.y << 8 | e.z << 16 | imask << 24
@@ -769,7 +770,6 @@ inline void buildBVH(const float *positions, const uint32_t *indices, uint32_t n
         /* empty scene: a single never-hit leaf */
         float rec[12] = { 0 }; rec[0] = detail::bits2f(3u); rec[10] = detail::bits2f(0xFFFFFFFFu);
         out.tris.assign(rec, rec + 12);
-        out.rootRef = ~(int32_t) 0;
         for (int a = 0; a < 3; ++a) { out.sceneMin[a] = out.tightMin[a] = 0; out.sceneMax[a] = out.tightMax[a] = 0; }
         return;
     }
@@ -855,7 +855,6 @@ inline void buildBVH(const float *positions, const uint32_t *indices, uint32_t n
         }
     }
 
-    /* ---- collapse to BVH4 ---- */
     typedef detail::ChildRef Child;
     auto children2 = [&](int32_t ref, Child out2[2]) {
         const float *nd = &out.nodes2[(size_t) ref * 16];
@@ -864,73 +863,23 @@ inline void buildBVH(const float *positions, const uint32_t *indices, uint32_t n
         uint32_t l, r; memcpy(&l, &nd[12], 4); memcpy(&r, &nd[13], 4);
         out2[0].ref = (int32_t) l; out2[1].ref = (int32_t) r;
     };
-    out.maxDepth = 0;
-    double cost = 0; const double rootA = rootBox.area() > 0 ? rootBox.area() : 1.0;
-    std::function<int32_t(int32_t, uint32_t)> collapse = [&](int32_t ref2, uint32_t depth) -> int32_t {
-        out.maxDepth = std::max(out.maxDepth, depth);
-        if (ref2 < 0) return ref2;                      /* leaf reference stays */
-        Child ch[4]; int n = 2;
-        children2(ref2, ch);
-        while (n < 4) {                                 /* expand the inner child with the largest area */
-            int best = -1; float bestA = -1;
-            for (int i = 0; i < n; ++i) if (ch[i].ref >= 0 && ch[i].box.area() > bestA) { bestA = ch[i].box.area(); best = i; }
-            if (best < 0) break;
-            Child two[2]; children2(ch[best].ref, two);
-            ch[best] = two[0]; ch[n++] = two[1];
-        }
-        const uint32_t idx = out.nNodes++;
-        out.nodes.resize((size_t) out.nNodes * 32);
-        int32_t refs[4];
-        for (int i = 0; i < n; ++i) {
-            refs[i] = collapse(ch[i].ref, depth + 1);
-            cost += ch[i].box.area() / rootA * (ch[i].ref < 0 ? (double) (((~(uint32_t) ch[i].ref) & 7) + 1) : 1.0);
-        }
-        float *nd = &out.nodes[(size_t) idx * 32];
-        for (int i = 0; i < 4; ++i) {
-            const bool used = i < n;
-            for (int a = 0; a < 3; ++a) {
-                nd[4 * a + i] = used ? ch[i].box.mn[a] : INFINITY;
-                nd[4 * (3 + a) + i] = used ? ch[i].box.mx[a] : -INFINITY;
-            }
-            nd[24 + i] = detail::bits2f(used ? (uint32_t) refs[i] : 0xffffffffu);   /* unused: never reached */
-            nd[28 + i] = 0.0f;
-        }
-        return (int32_t) idx;
-    };
-    out.rootRef = collapse(root2, 1);
-    out.sahCost = (float) (cost + 1.0);
 
-    /* The traversal kernels stage nodes [0, K) in LDS: renumber so that the top of the tree comes first
-       (breadth-first for the first TOP_BFS nodes, the rest keeps its depth-first order). */
-    if (out.rootRef >= 0 && out.nNodes > 1) {
-        const uint32_t TOP_BFS = 256;
-        std::vector<uint32_t> order; order.reserve(out.nNodes);
-        std::vector<uint8_t> taken(out.nNodes, 0);
-        order.push_back((uint32_t) out.rootRef); taken[out.rootRef] = 1;
-        for (size_t head = 0; head < order.size() && order.size() < TOP_BFS; ++head) {
-            const float *nd = &out.nodes[(size_t) order[head] * 32];
-            for (int i = 0; i < 4 && order.size() < TOP_BFS; ++i) {
-                uint32_t r; memcpy(&r, &nd[24 + i], 4);
-                if ((int32_t) r >= 0 && r < out.nNodes && !taken[r]) { taken[r] = 1; order.push_back(r); }
-            }
+    /* ---- the leaf list of the small trees (HostBVH::leaves) ---- */
+    /* (root2 >= 0: a tree that is a SINGLE leaf gets no list -- it never had a leaf table: the record cache used to be tied to a non-empty node cache, and
+       such a tree had no 4-wide node; the ray kernels serve it) */
+    if (root2 >= 0 && out.nLeaves <= LEAF_LIST_MAX && out.tris.size() / 12 <= LEAF_LIST_MAX) {
+        Child two[2]; children2(root2, two);
+        std::vector<Child> stack = { two[1], two[0] };
+        while (!stack.empty()) {
+            const Child c = stack.back(); stack.pop_back();
+            if (c.ref >= 0) { children2(c.ref, two); stack.push_back(two[1]); stack.push_back(two[0]); continue; }
+            HostBVH::LeafBox leaf; leaf.ref = c.ref;
+            for (int a = 0; a < 3; ++a) { leaf.mn[a] = c.box.mn[a]; leaf.mx[a] = c.box.mx[a]; }
+            out.leaves.push_back(leaf);
         }
-        for (uint32_t i = 0; i < out.nNodes; ++i) if (!taken[i]) order.push_back(i);
-        std::vector<uint32_t> newIndex(out.nNodes);
-        for (uint32_t i = 0; i < out.nNodes; ++i) newIndex[order[i]] = i;
-        std::vector<float> nn(out.nodes.size());
-        for (uint32_t i = 0; i < out.nNodes; ++i) {
-            const float *src = &out.nodes[(size_t) order[i] * 32]; float *dst = &nn[(size_t) i * 32];
-            memcpy(dst, src, 32 * sizeof(float));
-            for (int c = 0; c < 4; ++c) {
-                uint32_t r; memcpy(&r, &src[24 + c], 4);
-                if ((int32_t) r >= 0 && r < out.nNodes && src[c] != INFINITY) { r = newIndex[r]; memcpy(&dst[24 + c], &r, 4); }
-            }
-        }
-        out.nodes.swap(nn);
-        out.rootRef = (int32_t) newIndex[out.rootRef];
     }
 
-    /* ---- compressed 8-wide tree for the big-scene ray kernels ---- */
+    /* ---- compressed 8-wide tree for the ray kernels ---- */
     buildWide(out, root2, rootBox, children2);
     std::vector<float>().swap(out.nodes2);
     out.buildMs = (float) std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

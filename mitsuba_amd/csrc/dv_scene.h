@@ -2,8 +2,10 @@
  * dv_scene.h -- device-resident scene layout and the per-vertex shading functions of path_hip.
  *
  * HBM layout (all arrays are immutable after phip_scene_create):
- *   nodes      float4[8*nNodes]    128-byte BVH4 nodes, SoA over the four children (bvh.h)
- *   tris       float4[3*nTriRefs]  48-byte Wald triangle records in leaf order
+ *   wnodes     uint4[5*nWNodes]    80-byte nodes of the compressed 8-wide tree every scene's ray kernels walk (bvh.h: buildWide)
+ *   wtris      float4[3*nWTris]    48-byte Wald triangle records, grouped per wide node
+ *   tris       float4[3*nTriRefs]  the same records in the binary tree's leaf order: scenes of at most 64 records, beside ...
+ *   flatLeaves float4[2*nLeaves]   ... the packed leaf table of the LDS-resident kernels (k_traverse.h: flat2Pass1); tris == wtris elsewhere
  *   triShade   float4[6*nTriangles] 96-byte shading record per GLOBAL triangle id (vertices, leaf
  *                                  BSDF ids, emitter id, flat-shading frame or vertex normals)
  *   materials  DevMaterial[]       80 bytes each; staged in LDS by k_shade when there are few
@@ -84,12 +86,12 @@ struct DevEnvMap {
 };
 
 struct DevScene {
-    const float4 *nodes; const float4 *tris; const float4 *triShade;
-    uint32_t flatMode;                                      /* layout of flatLeaves: 1 = (min, ref)(max, 0) per leaf; 2 = packed planes + record masks (traverseFlat2) */
-    const float4 *flatLeaves; uint32_t nFlatLeaves;         /* k_mega: the leaves of a tree of <= FLAT_LEAVES_MAX leaves as a flat table (k_traverse.h: traverseFlat); 0: walk the BVH4 */
+    const float4 *tris; const float4 *triShade;
+    uint32_t flatMode;                                      /* 0: no leaf table; 2 / 3: flatLeaves is the packed table (centre, half extent, record mask) of at most 32 / 64 Wald records */
+    const float4 *flatLeaves; uint32_t nFlatLeaves;         /* k_mega, k_shade_trace: the leaves of a tree of <= FLAT2_LEAVES_MAX leaves as a table (k_traverse.h: flat2Pass1) */
     const uint4 *wnodes; uint32_t wideNodeCache;             /* the compressed 8-wide tree (k_wide_node.h) and -- wtris -- the Wald records in ITS leaf order.  Scenes past the packed leaf
-                                                                table (more than 64 records) hold nothing else: tris == wtris, nodes unused; the LDS-resident scenes keep the BVH4-ordered
-                                                                records (tris) and the leaf table for k_mega / k_shade_trace beside the wide tree the ray kernels walk (round 6) */
+                                                                table (more than 64 records) hold nothing else: tris == wtris; the LDS-resident scenes keep the records in the binary tree's leaf order
+                                                                (tris) and the leaf table for k_mega / k_shade_trace beside the wide tree the ray kernels walk (round 6) */
     const float4 *wtris;
     const DevMaterial *materials; uint32_t nMaterials;
     const float *emitterTab; uint32_t emitterTabSize;       /* EmitterTab layout, floats */
@@ -98,8 +100,9 @@ struct DevScene {
     uint32_t triShadeStride;             /* float4s per shading record: 6, or 9 when a mesh has texture coordinates */
     int32_t envEmitter; float envCenter[3]; float envRadius;   /* environment emitter (or -1) and its m_sceneBSphere */
     DevEnvMap env;
-    int32_t rootRef; uint32_t nTriangles;
-    uint32_t stackDepth, nodeCache, triCache;   /* LDS staging plan of the traversal kernels */
+    uint32_t nTriangles;
+    uint32_t dealDwords, triCache;       /* LDS plan of k_mega on the packed table: dwords per lane of the deal / mailbox region at the front of its dynamic LDS (it was `stackDepth`);
+                                            Wald records staged behind it (all of them, or 0) */
     uint32_t preclip;                    /* the shading kernels clip the rays they make against the scene box (k_clip.h); k_rays_w expects it */
     uint32_t shadeSort;                  /* the Wald records carry shade classes and the scene has more than one: k_shade deals slots to lanes by class */
     float sceneMin[3], sceneMax[3];
@@ -236,7 +239,7 @@ DV bool waldIntersect(const float4 &a, const float4 &b, const float4 &c, const V
 /* Closest-hit bookkeeping.  Several triangles can report EXACTLY the same distance (a ray through a shared edge, coincident
    surfaces), and the Wald test accepts t == maxt (triaccel.h:140: `t > maxt` rejects), so which of them a structure reports is
    whichever it tests last -- in the reference that is a property of its kd-tree's leaf order.  To make the answer independent
-   of the structure (BVH4 / 8-wide tree, traversal order, spatial splits) the HIGHEST triangle index wins a tie: what a sweep
+   of the structure (leaf table / 8-wide tree, traversal order, spatial splits) the HIGHEST triangle index wins a tie: what a sweep
    over all triangles in index order returns (oracle: set_bruteforce; tests/test_gpu_parity.py, C2 at full size). */
 DV bool winsTie(float tt, uint32_t prim, float bestT, uint32_t bestPrim) { return !(tt == bestT && prim < bestPrim); }
 

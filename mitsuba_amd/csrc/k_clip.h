@@ -1,7 +1,7 @@
 /*
  * k_clip.h -- the scene-box clip + adaptive epsilon of Scene::rayIntersect (src/librender/skdtree.cpp:112-142 closest hit, :207-226 shadow
  * rays) and the reciprocal direction of the slab tests.  Included by every translation unit through phip_common.h: the ray kernels clip
- * the rays they fetch (BVH4 path, k_mega, phip_trace); on scenes that use the wide tree the SHADING kernels clip the rays they make
+ * the rays they fetch (k_mega, phip_trace); on scenes that use the wide tree the SHADING kernels clip the rays they make
  * (DevScene::preclip), where every lane of the wave has one, and k_rays_w fetches (o, mint' | d, maxt') ready to traverse.
  */
 #pragma once

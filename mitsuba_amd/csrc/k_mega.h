@@ -131,12 +131,12 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
                                                                    the origin of a pinhole camera's rays is the same for every sample (camO below) */
     __shared__ uint32_t ldsSeq[QMC ? BLOCK / 64 : 1][2][64];    /* QMC: per lane, the sequence index of the path's sample -- shadeVertex draws every number of the path from it; deriving it anew at every
                                                                    request (sobol::look_up: ~30 table rows) was a third of the QMC kernel's sampling cost */
-    /* dynamic LDS: [traversal stack | all nodes | all Wald records] (setupTraversal) [shading records | emitter table | materials],
+    /* dynamic LDS: [work lists of the dealt traversal, S-box | all Wald records] (stageRecords) [shading records | emitter table | materials | leaf table],
        sized for THIS scene (megaLdsBytes) so that as many blocks as the registers allow fit a CU */
     /* WIDE: [the four waves' task stacks | top-of-tree node cache] (setupWidePool) [the four waves' round buffers] [emitter table | materials (FLAT 4)] (k_wide_wave.h: megaWidePoolLdsBytesOf) */
     constexpr uint32_t WAVE_BYTES = WP_WAVE_BYTES;              /* the waves' round buffers (their first 512 bytes: the result slots, which serve mbAssign between traversals) */
     unsigned char *wideDeal = g_smem + widePoolDealOffset(M.nodeCache);
-    float4 *ldsTriShade = (float4 *) (g_smem + traversalLdsBytesOf(S));
+    float4 *ldsTriShade = (float4 *) (g_smem + recordsLdsEndOf(S));
     float *ldsEm = WIDE ? (float *) (wideDeal + (BLOCK / 64u) * WAVE_BYTES + (MAILBOX ? MB_DW * MB_NS * sizeof(uint32_t) : 0u))
                         : (float *) (ldsTriShade + (size_t) S.nTriangles * TRISHADE_FLOAT4S);
     DevMaterial *ldsMat = (DevMaterial *) (ldsEm + ((S.emitterTabSize + 3u) & ~3u));
@@ -152,15 +152,15 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
         S.triShade = ldsTriShade;                               /* (generic pointer into LDS: six loads per vertex, not the inner loop) */
     }
     if (MAILBOX) { if (threadIdx.x < MB_NS + MB_NR) mbState[threadIdx.x] = 0u; if (threadIdx.x == 0u) mbLive = 0; }
-    TravStack stk; stk.tris = nullptr;
+    lds_cf4 *const ldsTris = (lds_cf4 *) (g_smem + (size_t) S.dealDwords * BLOCK * sizeof(uint32_t)); (void) ldsTris;     /* = stageRecords' result (k_traverse.h) */
     WidePool wpool;
     if (WIDE) setupWidePool(S, M.nodeCache, g_smem, M.spill + (size_t) blockIdx.x * BLOCK * SPILL_DEPTH, (uint32_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)), wpool);   /* the waves' task stacks (LDS, HBM spill behind them) + the top of the tree (barrier inside) */
-    else setupTraversal(S, g_smem, nullptr, stk);               /* stack + all nodes + all Wald records in LDS (barrier inside); the host checked that nothing can spill */
+    else stageRecords(S, g_smem);                     /* all Wald records in LDS (barrier inside) */
 
     const uint32_t waveId = blockIdx.x * (BLOCK / 64) + (uint32_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)), lane = __lane_id();
     unsigned long long next = 0, end = 0;                       /* the wave's chunk of sample ids (wave-uniform) */
     const uint32_t waveInBlock = (uint32_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
-    /* FLAT 2 / 3: over the traversal stack, which the flat table does not use (phip.hip sizes it); WIDE: the wave's round buffers (the slots serve mbAssign between traversals) */
+    /* FLAT 2 / 3: the front of the dynamic LDS (DevScene::dealDwords, phip.hip sizes it); WIDE: the wave's round buffers (the slots serve mbAssign between traversals) */
     unsigned char *const waveDeal = wideDeal + waveInBlock * WAVE_BYTES;
     WaveBalance wb = waveBalanceAt(g_smem, waveInBlock);
     if (WIDE) { wb.slot = (lds_u64 *) waveDeal; wb.list = (lds_u16 *) (waveDeal + 2u * 64u * 8u); }
@@ -419,7 +419,7 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
             cPush = false; cPend = false;
         } else {                                                /* the packed leaf table: the tests of the wave's rays are dealt over its lanes */
             uint32_t nNode = 0, nTri = 0;
-            traverseFlat2W<false, FLAT == 3>(flat, S.nFlatLeaves, stk.tris, wb, lane, go, o, d, rcp, mint, maxt, r, nNode, nTri);
+            traverseFlat2W<false, FLAT == 3>(flat, S.nFlatLeaves, ldsTris, wb, lane, go, o, d, rcp, mint, maxt, r, nNode, nTri);
             if (trace) {
                 v.hit = make_float4(r.t, r.u, r.v, pm_from_bits(r.prim));
                 hitCls = r.cls;
@@ -492,7 +492,7 @@ template <int MM, bool STRICT, int FLAT /* 2: packed leaf table + record masks (
             uint32_t nNode = 0, nTri = 0;
             V3 rcp;
             const bool go = pushShadow & clipToSceneSel<true>(S, o, d, PT_EPSILON, sh.e0.w, mint, maxt, rcp);
-            const bool occluded = traverseFlat2W<true, FLAT == 3>(flat, S.nFlatLeaves, stk.tris, wb, lane, go, o, d, rcp, mint, maxt, r, nNode, nTri);
+            const bool occluded = traverseFlat2W<true, FLAT == 3>(flat, S.nFlatLeaves, ldsTris, wb, lane, go, o, d, rcp, mint, maxt, r, nNode, nTri);
             if (pushShadow) {
                 if (!WCNT) { MEGA_COUNT(MC_SH_RAYS, 1); MEGA_COUNT(MC_SH_NODE, nNode); MEGA_COUNT(MC_SH_TRI, nTri); }
                 if (!occluded) { accum.x += sh.e2.x; accum.y += sh.e2.y; accum.z += sh.e2.z; }

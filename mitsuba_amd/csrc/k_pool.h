@@ -7,12 +7,6 @@
  *  device-side state
  * ====================================================================================== */
 #define BLOCK 256
-#ifndef STACK_DEPTH
-#define STACK_DEPTH 24          /* LDS entries per lane (96 B): 6 waves/SIMD fit in 160 KB; deeper entries spill to HBM */
-#endif
-#ifndef NODE_CACHE_MAX
-#define NODE_CACHE_MAX 48            /* BVH4 nodes staged in LDS per block (144 B each): 16 -> 48 measured -2 % traversal time; 64 costs a block of occupancy */
-#endif
 #ifndef TRI_CACHE_MAX
 #define TRI_CACHE_MAX 96        /* triangle records staged in LDS when the whole scene has at most this many */
 #endif
@@ -75,8 +69,8 @@ enum { ST_CLOSEST_RAYS = 0, ST_NODE, ST_TRI, ST_SHADOW_RAYS, ST_SH_NODE, ST_SH_T
 #ifndef MEGA_WIDE_NODE_CACHE
 #define MEGA_WIDE_NODE_CACHE 48u     /* k_mega<.., FLAT >= 4, ..>: top-of-tree nodes (BFS order) a block stages in LDS (80 B each) */
 #endif
-#define FLAT_LEAVES_MAX 32           /* k_mega: trees of at most this many leaves are traversed as a flat table of leaf boxes (one bit per leaf) */
-#define FLAT2_LEAVES_MAX 64          /* ... of the packed table with record masks (flatMode 2 / 3: at most 32 / 64 Wald records, the mask is over records, not leaves) */
+#define FLAT2_LEAVES_MAX 64          /* k_mega, k_shade_trace: trees of at most this many leaves and Wald records are traversed as the packed leaf table with record masks (flatMode 2 / 3:
+                                        at most 32 / 64 records; the mask is over records, not leaves) */
 #define MEGA_TRISHADE_MAX 96         /* k_mega: shading records staged in LDS (9 KB) */
 #define DYN_SHARDS 8                    /* one dynamic-sample counter per XCD-sized group of blocks */
 #define DYN_STRIDE 16                   /* unsigned long longs between counters (128 B) */

@@ -1,5 +1,5 @@
 /*
- * k_traverse.h -- the LDS-resident trees: the block's staged tree and Wald records (setupTraversal), the packed leaf table with the Wald tests dealt
+ * k_traverse.h -- the LDS-resident scenes: the block's staged Wald records (stageRecords), the packed leaf table with the Wald tests dealt
  * over the wave (traverseFlat2W).  Included by phip.hip, phip_mega.hip and phip_shade.hip; see the header of phip.hip.
  */
 
@@ -8,38 +8,23 @@
  * ====================================================================================== */
 struct TravResult { float t, u, v; uint32_t prim; uint32_t cls = 0; /* shade class of the record hit (k_rays_w only: k_pool.h) */ };
 
-/* Per-lane traversal stack: the first `depth` entries live in LDS (interleaved: entry e of lane l at
- * lds[e * BLOCK + l], so lane i always hits bank i), deeper entries spill to a per-lane HBM array.
- * The same dynamic LDS segment also stages the top of the tree: the first S.nodeCache BVH4 nodes (they
- * are stored in breadth-first order, so these are the levels every ray visits) and, for small scenes,
- * all triangle records.  Cached nodes use a 144-byte stride so that lanes reading different nodes hit
- * different banks with ds_read_b128. */
-#define NODE_LDS_STRIDE 9               /* float4 per cached node (8 + 1 pad) */
 /* LDS pointers carry their address space in the type: through a generic pointer the compiler emits flat_load for the cached
-   nodes/records, which goes through the texture addresser (16 clk per 16-byte wave instruction, shared by the CU's four SIMDs)
+   records, which goes through the texture addresser (16 clk per 16-byte wave instruction, shared by the CU's four SIMDs)
    instead of the LDS pipe (ds_read_b128) -- on the Cornell box, where everything is cached, that was the bottleneck. */
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) f4v lds_cf4;
 __device__ __forceinline__ float4 ldsLoad4(lds_cf4 *p) { const f4v v = *p; return make_float4(v.x, v.y, v.z, v.w); }
-struct TravStack {
-    lds_u32 *lds;           /* lds base + threadIdx.x */
-    uint32_t *spill;        /* global: SPILL_DEPTH entries per lane */
-    lds_cf4 *nodes;         /* LDS copy of nodes [0, nodeCache) */
-    lds_cf4 *tris;          /* LDS copy of triangle records [0, triCache) */
-    uint32_t nodeCache, triCache;
-    int depth, sp;
-};
 
-/* k_mega<MM_ALL>: the region [0, 12 KB) of the dynamic LDS, over the traversal stack (phip.hip sizes it) --
+/* k_mega<MM_ALL>: the region [0, 12 KB) of the dynamic LDS (DevScene::dealDwords; phip.hip sizes it) --
    the four waves' work lists (6 KB), then the S-box of the mailboxes */
 #define MEGA_DEAL_DWORDS 12u
-/* bytes of dynamic LDS setupTraversal() uses; k_mega appends its shading tables (megaLdsBytesOf) */
-__host__ __device__ __forceinline__ size_t traversalLdsBytesOf(const DevScene &S) {
-    return (size_t) S.stackDepth * BLOCK * sizeof(uint32_t) + (size_t) S.nodeCache * NODE_LDS_STRIDE * sizeof(float4) + (size_t) S.triCache * 3 * sizeof(float4);
+/* bytes of dynamic LDS up to the end of the records stageRecords() stages; k_mega appends its shading tables (megaLdsBytesOf) */
+__host__ __device__ __forceinline__ size_t recordsLdsEndOf(const DevScene &S) {
+    return (size_t) S.dealDwords * BLOCK * sizeof(uint32_t) + (size_t) S.triCache * 3 * sizeof(float4);
 }
 __host__ __device__ __forceinline__ size_t megaLdsBytesOf(const DevScene &S) {
-    return traversalLdsBytesOf(S) + (size_t) S.nTriangles * TRISHADE_FLOAT4S * sizeof(float4) + (size_t) ((S.emitterTabSize + 3u) & ~3u) * sizeof(float)
+    return recordsLdsEndOf(S) + (size_t) S.nTriangles * TRISHADE_FLOAT4S * sizeof(float4) + (size_t) ((S.emitterTabSize + 3u) & ~3u) * sizeof(float)
          + (size_t) S.nMaterials * sizeof(DevMaterial) + 16 /* alignment of the next array */ + (size_t) S.nFlatLeaves * 2 * sizeof(float4);
 }
 
@@ -50,18 +35,15 @@ __host__ __device__ __forceinline__ size_t shadeTraceLdsBytes(const DevScene &S)
          + (size_t) S.nMaterials * sizeof(DevMaterial);
 }
 
-/* carve the block's dynamic LDS and stage the cached geometry (all threads of the block must call) */
-__device__ __forceinline__ void setupTraversal(const DevScene &S, unsigned char *smem, uint32_t *spill, TravStack &stk) {
-    uint32_t *stack = (uint32_t *) smem;
-    float4 *ln = (float4 *) (smem + (size_t) S.stackDepth * BLOCK * sizeof(uint32_t));
-    float4 *lt = ln + (size_t) S.nodeCache * NODE_LDS_STRIDE;
-    for (uint32_t i = threadIdx.x; i < S.nodeCache * 8u; i += BLOCK)
-        ln[(i >> 3) * NODE_LDS_STRIDE + (i & 7u)] = S.nodes[i];
+/* k_mega on the packed table: stage the scene's Wald records behind the deal / mailbox region at the front of the block's dynamic LDS and return the copy
+   (all threads of the block must call: barrier inside).  k_mega takes the same address BEFORE the call instead of the result: a pointer that is live out of the
+   staging costs k_mega<MM_ALL, strict, .., QMC> two more dwords of scratch (120 B against the 112 of tests/test_kernel_resources.py) */
+__device__ __forceinline__ lds_cf4 *stageRecords(const DevScene &S, unsigned char *smem) {
+    float4 *lt = (float4 *) (smem + (size_t) S.dealDwords * BLOCK * sizeof(uint32_t));
     for (uint32_t i = threadIdx.x; i < S.triCache * 3u; i += BLOCK)
         lt[i] = S.tris[i];
     __syncthreads();
-    stk.lds = (lds_u32 *) (stack + threadIdx.x); stk.spill = spill; stk.nodes = (lds_cf4 *) ln; stk.tris = (lds_cf4 *) lt;
-    stk.nodeCache = S.nodeCache; stk.triCache = S.triCache; stk.depth = (int) S.stackDepth; stk.sp = 0;
+    return (lds_cf4 *) lt;
 }
 
 #define SPILL_DEPTH 96
@@ -148,7 +130,7 @@ __device__ __forceinline__ uint32_t flat2Pass1(lds_cf4 *flat, uint32_t nFlat, co
  *      first hit in index order: the work counter stays what it was);
  *   3. the owner reads its slot and repeats the winning test with its own registers for (t, u, v): same operands, same bits.
  * A work list of BAL_CAP pairs; a wave with more (never seen on the Cornell box: 64 x 3.1) goes round again with the lanes that did not fit.
- * Every lane of the wave must call, converged; `go` = this lane has a ray.  The buffers lie over the traversal stack (unused by the flat table). */
+ * Every lane of the wave must call, converged; `go` = this lane has a ray.  The buffers lie at the front of the dynamic LDS (DevScene::dealDwords). */
 #define BAL_CAP 512u
 #ifndef BAL_ILP
 #define BAL_ILP 1                        /* pairs per lane and step of the test loop (BAL_CAP is a multiple of 64 * BAL_ILP).  Measured: 1 / 2 / 4 = 53.0 / 56.0 / 59.8 ms
@@ -269,5 +251,5 @@ __device__ __forceinline__ bool traverseFlat2W(lds_cf4 *flat, uint32_t nFlat, ld
     }
 }
 
-/* the block's dynamic LDS: traversal stack + node / record cache (setupTraversal) */
+/* the block's dynamic LDS (k_mega.h has the map) */
 extern __shared__ __attribute__((aligned(16))) unsigned char g_smem[];

@@ -47,7 +47,7 @@ typedef const __attribute__((address_space(3))) u4v lds_cu4;
    lane index back out of the loop. */
 template <int NB> struct WideStackT {
     lds_u2 *ldsBlock;       /* LDS: the block's stack region (wave-uniform) */
-    uint2 *spillBlock;      /* global: the block's spill region, SPILL_DEPTH / 2 entries per lane (the BVH4 kernels' region, reinterpreted) */
+    uint2 *spillBlock;      /* global: the block's spill region, SPILL_DEPTH / 2 entries per lane (it was the BVH4 kernels' region) */
     lds_cu4 *nodes;         /* LDS copy of wide nodes [0, nodeCache) */
     uint32_t nodeCache;
     uint32_t waveBase;      /* first thread of this wave in the block (wave-uniform) */

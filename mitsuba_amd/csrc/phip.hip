@@ -45,9 +45,6 @@
 #ifndef PHIP_DEBUG_HOOKS
 #define PHIP_DEBUG_HOOKS 0
 #endif
-#ifndef PHIP_WIDE_MIN_RECORDS
-#define PHIP_WIDE_MIN_RECORDS 64u    /* scenes of more Wald records than the packed leaf table holds are traversed on the 8-wide tree, whatever their size */
-#endif
 #include <dlfcn.h>
 #include <map>
 #include <rccl/rccl.h>          /* types and prototypes only: librccl is bound with dlopen at the first multi-GPU render */
@@ -171,7 +168,7 @@ void spiralBlocks(int sizeX, int sizeY, int bs, std::vector<std::pair<int, int>>
 struct SceneDev {
     int device = 0;
     /* ---- scene (immutable after build / replication) ---- */
-    DevBuf<float4> nodes, tris, wtris, triShade, flatLeaves;      /* tris: BVH4 leaf order (LDS-resident scenes only), wtris: the wide tree's */
+    DevBuf<float4> tris, wtris, triShade, flatLeaves;      /* tris: the binary tree's leaf order (LDS-resident scenes only), wtris: the wide tree's */
     bool trisAreWide = false;                                      /* scenes past the packed leaf table: DevScene::tris = wtris */
     DevBuf<uint4> wnodes;                                                                     /* compressed wide BVH (big scenes) */
     DevBuf<DevMaterial> materials;
@@ -202,13 +199,13 @@ struct SceneDev {
 
     /* THE list of the immutable scene buffers, as pointers to members */
     template <typename F> static void forEachSceneBuffer(F f) {
-        f(&SceneDev::nodes); f(&SceneDev::wnodes); f(&SceneDev::tris); f(&SceneDev::wtris); f(&SceneDev::triShade); f(&SceneDev::flatLeaves);
+        f(&SceneDev::wnodes); f(&SceneDev::tris); f(&SceneDev::wtris); f(&SceneDev::triShade); f(&SceneDev::flatLeaves);
         f(&SceneDev::materials); f(&SceneDev::emitterTab); f(&SceneDev::texTexels); f(&SceneDev::texDesc);
         f(&SceneDev::envTexels); f(&SceneDev::envLevels); f(&SceneDev::envCdfRows); f(&SceneDev::envCdfCols); f(&SceneDev::envRowWeights);
     }
     /* the pointer members of the DevScene (everything else in it is plain data, equal on every device) */
     void bind() {
-        dev.nodes = nodes.p; dev.wnodes = wnodes.p; dev.wtris = wtris.p; dev.tris = trisAreWide ? wtris.p : tris.p; dev.triShade = triShade.p; dev.flatLeaves = flatLeaves.p; dev.materials = materials.p;
+        dev.wnodes = wnodes.p; dev.wtris = wtris.p; dev.tris = trisAreWide ? wtris.p : tris.p; dev.triShade = triShade.p; dev.flatLeaves = flatLeaves.p; dev.materials = materials.p;
         dev.texTexels = texTexels.p; dev.textures = texDesc.p; dev.emitterTab = emitterTab.p;
         dev.env.texels = envTexels.p; dev.env.levels = envLevels.p; dev.env.cdfRows = envCdfRows.p; dev.env.cdfCols = envCdfCols.p;
         dev.env.rowWeights = envRowWeights.p;
@@ -230,7 +227,7 @@ struct phip_scene {
     int materialMask = MM_ALL;       /* leaf BSDF models present: selects the k_shade instantiation */
     bool flatTraceToo = false;       /* a scene of k_mega that k_shade_trace could serve as well (PHIP_FLAG_NO_MEGA) */
     bool flatTrace = false;          /* not a scene of k_mega, but its tree is the packed leaf table (<= 64 Wald records) and emitter table + materials fit LDS: k_shade_trace */
-    bool wideOnly = false;           /* the device holds the compressed 8-wide BVH the ray kernels walk (every scene has it) and nothing else (trees of >= 64 BVH4 nodes or more than 64 Wald records): no BVH4, no leaf table, no LDS-resident kernels */
+    bool wideOnly = false;           /* the device holds the compressed 8-wide BVH the ray kernels walk (every scene has it) and nothing else (more than 64 Wald records): no leaf table, no LDS-resident kernels */
     bool fitsLds = false;            /* tree, Wald records, shading records, emitter table and materials fit the fused kernel's LDS plan */
     int fusedWide = 0;               /* round 6: 4 / 5 = the fused kernel walks the 8-wide tree from memory (k_mega<.., FLAT 4 / 5, ..>: emitter table in LDS; materials in LDS / in memory) */
     std::vector<std::unique_ptr<SceneDev>> devs;
@@ -345,8 +342,8 @@ struct SceneBuild {
     std::vector<float4> ts; uint32_t stride = TRISHADE_FLOAT4S;     /* shading records */
     std::vector<float> tab;                                         /* packed emitter table */
     std::vector<float4> envTexels; DevMipLevels envLevels; std::vector<float> envCdfRows, envCdfCols, envRowWeights;
-    std::vector<float4> flat;                                       /* flat / packed leaf table (flatMode != 0) */
-    uint32_t walkStack = 0; bool treeInLds = false, fitsLdsBase = false;     /* ldsPlan -> flatLeafTable, chooseDevicePaths */
+    std::vector<float4> flat;                                       /* packed leaf table (flatMode != 0) */
+    bool recordsInLds = false, fitsLdsBase = false;                 /* ldsPlan -> flatLeafTable, chooseDevicePaths */
 
     SceneBuild(phip_scene *sc, const phip_scene_desc &d) : sc(sc), sd(*sc->devs[0]), d(d), D(sd.dev) { memset(&D, 0, sizeof(D)); }
 
@@ -562,14 +559,16 @@ struct SceneBuild {
 
     /* what the device holds beside the 8-wide tree the ray kernels walk (wideOnly) and whether that tree's depth fits their stacks */
     void chooseTraversal() {
-        /* the compressed 8-wide tree: every scene the packed leaf table of the LDS-resident kernels does not serve (more than 64 Wald records).  Round 6: it used to start at 64 BVH4
-           nodes; the scenes in between ran the round-1 BVH4 kernels (or, all-diffuse ones, k_mega's BVH4 walk in LDS) -- now they run k_mega on the wide tree / k_rays_w */
+        /* the compressed 8-wide tree: every scene the packed leaf table of the LDS-resident kernels does not serve (more than 64 Wald records) runs k_mega on the wide tree / k_rays_w.
+           (The rule was "64 nodes of the 4-wide tree or more, or more than 64 records".  Its first half could not decide anything: with at most 64 records the binary tree has at
+           most 63 inner nodes, a collapsed node that keeps an inner child absorbed three of them, so that tree never exceeded 42 nodes.) */
         if (sc->bvh.nWNodes == 0) {      /* a scene without triangles: one node without children (all-zero meta bytes hit nothing) -- the ray kernels need a root to reject */
             sc->bvh.wnodes.assign(20, 0u); sc->bvh.nWNodes = 1; sc->bvh.wMaxDepth = 1;
         }
-        sc->wideOnly = sc->bvh.nNodes >= 64 || sc->bvh.tris.size() / 12 > PHIP_WIDE_MIN_RECORDS;
+        static_assert(FLAT2_LEAVES_MAX == 64 && LEAF_LIST_MAX == FLAT2_LEAVES_MAX, "the packed leaf table has one mask bit per record, two words; bvh.h collects the leaf list up to that size");
+        sc->wideOnly = sc->bvh.tris.size() / 12 > FLAT2_LEAVES_MAX;
         /* ... and, round 6, EVERY scene has the wide tree on the device: the ray kernels of the wavefront path (k_rays_w) and phip_trace (k_raycast_w) walk nothing else.
-           The LDS-resident scenes keep their BVH4-ordered records and leaf table for k_mega / k_shade_trace beside it */
+           The LDS-resident scenes keep their records in the binary tree's leaf order and the packed leaf table for k_mega / k_shade_trace beside it */
         /* the stack of the wide tree: one group per level */
         if ((int) sc->bvh.wMaxDepth + 2 > WIDE_STACK_LDS + SPILL_DEPTH / 2) throw std::runtime_error("wide BVH too deep for the traversal stack");
     }
@@ -698,7 +697,7 @@ struct SceneBuild {
         D.emitterTabSize = (uint32_t) tab.size();
         D.nEmitters = d.n_emitters; D.emitterNormalization = emNorm;
         D.envEmitter = envEmitter;
-        D.rootRef = sc->bvh.rootRef; D.nTriangles = d.n_triangles;
+        D.nTriangles = d.n_triangles;
         for (int a = 0; a < 3; ++a) { D.sceneMin[a] = sc->bvh.sceneMin[a]; D.sceneMax[a] = sc->bvh.sceneMax[a]; }
         setupCamera(d.camera, d.film, D.cam);
         D.film.width = d.film.crop_width; D.film.height = d.film.crop_height;
@@ -712,42 +711,37 @@ struct SceneBuild {
         sc->descCopy.shapes = nullptr; sc->descCopy.materials = nullptr; sc->descCopy.emitters = nullptr;
     }
 
-    /* LDS staging plan of the ray kernels: top-of-tree node cache (nodes are in breadth-first order), all triangle records if there are few, the
-       stack a walk of the BVH4 needs (3 pushes per level) -- and what follows from it for the fused kernel */
+    /* LDS staging plan: the top of the wide tree for the ray kernels (its nodes are in breadth-first order); for the LDS-resident kernels every Wald record, if the
+       scene has a leaf list -- and what follows from it for the fused kernel */
     void ldsPlan() {
         const HostBVH &bvh = sc->bvh;
-        walkStack = (uint32_t) std::min<int>(STACK_DEPTH, std::max<int>(4, 3 * ((int) bvh.maxDepth - 1) + 1));
-        D.nodeCache = sc->wideOnly ? 0u : std::min<uint32_t>(bvh.nNodes, NODE_CACHE_MAX);
-        D.triCache = (!sc->wideOnly && D.nodeCache != 0 && bvh.tris.size() / 12 <= TRI_CACHE_MAX) ? (uint32_t) (bvh.tris.size() / 12) : 0u;
+        /* (recordsInLds: the packed leaf table and every Wald record are staged in LDS -- also true of small scenes with glass, copper, textures or an environment
+           emitter, which k_shade_trace serves on the same table: k_shade_trace.h.  A scene that is ONE leaf has no leaf list, bvh.h: the ray kernels serve it) */
+        recordsInLds = !sc->wideOnly && !bvh.leaves.empty() && bvh.tris.size() / 12 <= TRI_CACHE_MAX;
+        D.triCache = recordsInLds ? (uint32_t) (bvh.tris.size() / 12) : 0u;
         D.wideNodeCache = std::min<uint32_t>(bvh.nWNodes, WIDE_NODE_CACHE_MAX);
         D.preclip = 1u;                          /* k_rays_w traverses rays the shading kernels have clipped (k_clip.h) */
-        /* the fused kernel's LDS plan (k_mega.h): the whole tree, every Wald and shading record, the emitter table and the
-           materials in LDS, a stack that cannot spill (phip_mega.hip) */
-        /* (treeInLds: the whole tree and every Wald record are staged in LDS and the stack cannot spill -- also true of small scenes with glass, copper,
-           textures or an environment emitter, which k_shade_trace serves on the same packed leaf table: k_shade_trace.h) */
-        treeInLds = D.nodeCache == bvh.nNodes && D.triCache == bvh.tris.size() / 12 && 3 * ((int) bvh.maxDepth - 1) + 1 <= (int) walkStack;
-        /* (leaf BSDF models: any -- round 5 -- when the tree is the packed leaf table; diffuse only for the trees the fused kernel walks or sweeps leaf by leaf:
-           chooseDevicePaths, once the table is built) */
+        /* the fused kernel's LDS plan (k_mega.h): the leaf table, every Wald and shading record, the emitter table and the materials in LDS (phip_mega.hip); leaf BSDF
+           models: any (round 5) */
         fitsLdsBase = !sc->hasTextures && envEmitter < 0 && stride == TRISHADE_FLOAT4S
-            && treeInLds && d.n_triangles <= MEGA_TRISHADE_MAX
+            && recordsInLds && d.n_triangles <= MEGA_TRISHADE_MAX
             && tab.size() <= EMITTER_LDS_FLOATS && mats.size() <= MATERIAL_LDS_MAX;
     }
 
-    /* the leaf boxes of flatLeafTable in the packed form with record masks (k_traverse.h: flat2Pass1).  A leaf reference is
+    /* the leaf list (bvh.h) in the packed form with record masks (k_traverse.h: flat2Pass1).  A leaf reference is
        ~((first record << 3) | records - 1); a triangle referenced by several leaves (spatial splits) has one record per
        reference -- the copies carry the same 12 words, so only the first copy's bit is set.
        Round 5: 33..64 records keep the packed form with a two-word mask (flatMode 3; the centre / half-extent table of the dealt
        traversal only -- the high word rides in the centre's spare word) */
-    void packLeafTable(size_t nRec) {
+    void packLeafTable() {
+        const size_t nRec = sc->bvh.tris.size() / 12;
         std::vector<uint32_t> firstCopy(nRec);
         for (size_t i = 0; i < nRec; ++i) {
             firstCopy[i] = (uint32_t) i;
             for (size_t j = 0; j < i; ++j) if (!memcmp(&sc->bvh.tris[12 * i], &sc->bvh.tris[12 * j], 48)) { firstCopy[i] = (uint32_t) j; break; }
         }
-        std::vector<float4> packed;
-        for (size_t l = 0; l < flat.size() / 2; ++l) {
-            const float4 mn = flat[2 * l], mx = flat[2 * l + 1];
-            const uint32_t r = ~pm_to_bits(mn.w), first = r >> 3, count = (r & 7u) + 1u;
+        for (const HostBVH::LeafBox &leaf : sc->bvh.leaves) {
+            const uint32_t r = ~(uint32_t) leaf.ref, first = r >> 3, count = (r & 7u) + 1u;
             unsigned long long bits64 = 0;
             for (uint32_t i = 0; i < count; ++i) bits64 |= 1ull << firstCopy[first + i];
             const uint32_t bits = (uint32_t) bits64, bitsHi = (uint32_t) (bits64 >> 32);
@@ -757,7 +751,7 @@ struct SceneBuild {
             const float ext = std::max(sc->bvh.tightMax[0] - sc->bvh.tightMin[0], std::max(sc->bvh.tightMax[1] - sc->bvh.tightMin[1], sc->bvh.tightMax[2] - sc->bvh.tightMin[2]));
             const float camMax = std::max(std::fabs(d.camera.to_world[3]), std::max(std::fabs(d.camera.to_world[7]), std::fabs(d.camera.to_world[11])));
             float c[3], h[3];
-            const float lo[3] = { mn.x, mn.y, mn.z }, hi[3] = { mx.x, mx.y, mx.z };
+            const float *lo = leaf.mn, *hi = leaf.mx;
             for (int a = 0; a < 3; ++a) {
                 c[a] = (float) (0.5 * ((double) lo[a] + (double) hi[a]));
                 const double need = std::max((double) c[a] - (double) lo[a], (double) hi[a] - (double) c[a]);
@@ -766,46 +760,23 @@ struct SceneBuild {
                    leaf boxes; tests/test_gpu_parity.py: far camera) */
                 h[a] = std::nextafter((float) need, INFINITY) + 2.4e-7f * std::fabs(c[a]) + 4e-6f * ext + 4.8e-7f * camMax;      /* (the largest component on every axis: bvh.h, buildBVH) */
             }
-            packed.push_back(make_float4(c[0], c[1], c[2], pm_from_bits(bitsHi)));
-            packed.push_back(make_float4(h[0], h[1], h[2], pm_from_bits(bits)));
+            flat.push_back(make_float4(c[0], c[1], c[2], pm_from_bits(bitsHi)));
+            flat.push_back(make_float4(h[0], h[1], h[2], pm_from_bits(bits)));
         }
-        flat.swap(packed);
     }
 
-    /* for trees of few leaves (the Cornell box: 17), the leaves as a flat table: the LDS-resident kernels test every leaf box in one uniform pass instead
-       of walking the 7-node tree.  Entry = (min.xyz, bits(leaf reference)) (max.xyz, 0), boxes as the BVH4 nodes hold them (padded), then packed.
-       flatMode: 0 no table, 1 these boxes (no kernel reads them: only a build with another PHIP_WIDE_MIN_RECORDS gets there), 2 / 3 the packed form of at most 32 / 64 Wald records */
+    /* for trees of few leaves (the Cornell box: 17), the leaves as a table: the LDS-resident kernels test every leaf box in one uniform pass, no walk.
+       flatMode: 0 no table, 2 / 3 the packed form of at most 32 / 64 Wald records (1 was a table of plain boxes; its kernel is retired) */
     void flatLeafTable() {
-        int mode = 0;
-        if (treeInLds && !sc->wideOnly && sc->bvh.nLeaves <= FLAT2_LEAVES_MAX) {
-            if (sc->bvh.rootRef < 0) {                         /* a single leaf: its box is the scene's */
-                flat.push_back(make_float4(sc->bvh.tightMin[0] - 1.0f, sc->bvh.tightMin[1] - 1.0f, sc->bvh.tightMin[2] - 1.0f, pm_from_bits((uint32_t) sc->bvh.rootRef)));
-                flat.push_back(make_float4(sc->bvh.tightMax[0] + 1.0f, sc->bvh.tightMax[1] + 1.0f, sc->bvh.tightMax[2] + 1.0f, 0.0f));
-            } else for (uint32_t n = 0; n < sc->bvh.nNodes; ++n) {
-                const float *nd = &sc->bvh.nodes[(size_t) n * 32];
-                for (int c = 0; c < 4; ++c) {
-                    uint32_t ref; memcpy(&ref, &nd[24 + c], 4);
-                    if (nd[c] == INFINITY || (int32_t) ref >= 0) continue;           /* empty slot / inner child */
-                    flat.push_back(make_float4(nd[c], nd[4 + c], nd[8 + c], pm_from_bits(ref)));
-                    flat.push_back(make_float4(nd[12 + c], nd[16 + c], nd[20 + c], 0.0f));
-                }
-            }
-            const size_t nRec = sc->bvh.tris.size() / 12;
-            if (flat.size() / 2 <= FLAT2_LEAVES_MAX && nRec <= 64) {
-                packLeafTable(nRec); mode = nRec <= 32 ? 2 : 3;
-            } else if (fitsLdsBase && sc->materialMask == 0 && flat.size() / 2 <= FLAT_LEAVES_MAX)
-                mode = 1;
-        }
-        if (!mode) flat.clear();
-        D.flatMode = mode; D.nFlatLeaves = (uint32_t) (flat.size() / 2);
+        if (recordsInLds) packLeafTable();
+        D.flatMode = flat.empty() ? 0u : (sc->bvh.tris.size() / 12 <= 32 ? 2u : 3u); D.nFlatLeaves = (uint32_t) (flat.size() / 2);
     }
 
     /* which device path serves the scene: fitsLds (k_mega on the LDS-resident tree), fusedWide (k_mega on the 8-wide tree), flatTrace (k_shade_trace);
-       the stack the LDS plans of those kernels need, the lane deal of the shading kernels */
+       the deal region at the front of k_mega's dynamic LDS, the lane deal of the shading kernels */
     void chooseDevicePaths() {
         const int mask = sc->materialMask;
-        /* leaf BSDF models: any (round 5) on the packed leaf table */
-        sc->fitsLds = fitsLdsBase && (mask == 0 || D.flatMode >= 2);
+        sc->fitsLds = fitsLdsBase;                              /* (implies the packed leaf table: recordsInLds) */
         /* round 6: the fused kernel on a tree that does not fit LDS (k_wide_wave.h) -- every scene on the 8-wide tree whose emitter table fits LDS and that needs none of the
            feature sets k_mega is not compiled with (bitmap textures, an environment emitter) */
         sc->fusedWide = (sc->wideOnly && !sc->hasTextures && envEmitter < 0 && stride == TRISHADE_FLOAT4S && tab.size() <= EMITTER_LDS_FLOATS
@@ -813,11 +784,11 @@ struct SceneBuild {
                       ? (mats.size() <= MATERIAL_LDS_MAX ? 4 : 5) : 0;
         const bool traceable = D.flatMode >= 2 && tab.size() <= EMITTER_LDS_FLOATS && mats.size() <= MATERIAL_LDS_MAX;
         sc->flatTrace = !sc->fitsLds && traceable; sc->flatTraceToo = sc->fitsLds && traceable;
-        /* k_mega deals the Wald tests of the packed table over the wave through LDS buffers that lie over the (unused) traversal stack
+        /* k_mega deals the Wald tests of the packed table over the wave through LDS buffers at the front of its dynamic LDS
            (k_traverse.h: traverseFlat2W); k_mega<MM_ALL> keeps its mailbox of copper vertices in MEGA_DEAL_DWORDS x BLOCK dwords of LDS that lie there too (k_mega.h) */
-        const uint32_t dealStack = D.flatMode >= 2 ? (uint32_t) (((BLOCK / 64) * BAL_WAVE_BYTES + BLOCK * sizeof(uint32_t) - 1) / (BLOCK * sizeof(uint32_t))) : 0u;
-        const uint32_t mailboxStack = (sc->fitsLds && mask != 0) ? (uint32_t) MEGA_DEAL_DWORDS : 0u;
-        D.stackDepth = std::max(walkStack, std::max(dealStack, mailboxStack));
+        const uint32_t dealList = D.flatMode >= 2 ? (uint32_t) (((BLOCK / 64) * BAL_WAVE_BYTES + BLOCK * sizeof(uint32_t) - 1) / (BLOCK * sizeof(uint32_t))) : 0u;
+        const uint32_t mailbox = (sc->fitsLds && mask != 0) ? (uint32_t) MEGA_DEAL_DWORDS : 0u;
+        D.dealDwords = std::max(dealList, mailbox);
         /* the lane deal of k_shade pays where the expensive model is rare: rough conductors (microfacet sampling: atrium, 8 % of the vertices,
            k_shade -7 %); on a diffuse + dielectric mix the extra round trip costs more than the cheap Fresnel branch (glass room: +8 %).
            k_shade_trace deals its lanes by BSDF model where there is more than one (the kernel traces its own rays and leaves the class in the hit word) */
@@ -840,12 +811,7 @@ struct SceneBuild {
         }
         if (bvh.wtris.empty()) sd.wtris.alloc(3); else sd.wtris.upload((const float4 *) bvh.wtris.data(), bvh.wtris.size() / 4);
         sd.trisAreWide = sc->wideOnly;                           /* DevScene::tris = wtris: SceneDev::bind */
-        if (sc->wideOnly) { sd.nodes.alloc(8); sd.tris.alloc(3); }
-        else {
-            if (bvh.nodes.empty()) sd.nodes.alloc(8);
-            else sd.nodes.upload((const float4 *) bvh.nodes.data(), bvh.nodes.size() / 4);
-            sd.tris.upload((const float4 *) bvh.tris.data(), bvh.tris.size() / 4);
-        }
+        if (sc->wideOnly) sd.tris.alloc(3); else sd.tris.upload((const float4 *) bvh.tris.data(), bvh.tris.size() / 4);
         sd.materials.upload(mats.data(), mats.size());
         sd.emitterTab.upload(tab.data(), tab.size());
         if (envIsMap) {
@@ -857,7 +823,7 @@ struct SceneBuild {
         if (flat.empty()) sd.flatLeaves.alloc(2); else sd.flatLeaves.upload(flat.data(), flat.size());
         sd.bind();
         sd.allocCounters();
-        std::vector<float>().swap(bvh.nodes); std::vector<float>().swap(bvh.tris);      /* keep the statistics, drop the arrays */
+        std::vector<float>().swap(bvh.tris);                    /* keep the statistics, drop the arrays */
         std::vector<uint32_t>().swap(bvh.wnodes); std::vector<float>().swap(bvh.wtris);
         HIP_TRY(hipHostMalloc((void **) &sc->cancelFlag, sizeof(int), hipHostMallocPortable | hipHostMallocMapped));
         *sc->cancelFlag = 0;
@@ -2168,10 +2134,9 @@ void phip_develop(const float *rgbaw, size_t n_pixels, float *out_rgb) {
 
 int phip_scene_accel_info(const phip_scene *scene, phip_accel_info *out) {
     if (!scene || !out) return setErr(PHIP_ERR_INVALID, "NULL argument");
-    out->n_nodes = scene->bvh.nNodes; out->n_leaves = scene->bvh.nLeaves; out->n_triangle_refs = scene->bvh.nTriRefs;
-    out->max_depth = scene->bvh.maxDepth; out->node_bytes = 128; out->triangle_bytes = 48;
-    out->sah_cost = scene->bvh.sahCost; out->build_ms = scene->bvh.buildMs;
-    if (scene->wideOnly) { out->n_nodes = scene->bvh.nWNodes; out->max_depth = scene->bvh.wMaxDepth; out->node_bytes = 80; out->sah_cost = scene->bvh.wSahCost; }
+    out->n_nodes = scene->bvh.nWNodes; out->n_leaves = scene->bvh.nLeaves; out->n_triangle_refs = scene->bvh.nTriRefs;
+    out->max_depth = scene->bvh.wMaxDepth; out->node_bytes = 80; out->triangle_bytes = 48;
+    out->sah_cost = scene->bvh.wSahCost; out->build_ms = scene->bvh.buildMs;
     out->fits_lds = scene->fitsLds ? 1u : 0u; out->fused_traversal = scene->fitsLds ? scene->devs[0]->dev.flatMode : (uint32_t) scene->fusedWide;
     return PHIP_OK;
 }

@@ -129,8 +129,8 @@ int phip_debug_host_build_bvh(const float *positions, uint32_t n_vertices, const
         for (uint32_t i = 0; i < 3 * n_triangles; ++i) if (indices[i] >= n_vertices) return setErr(PHIP_ERR_INVALID, "index out of range");
         HostBVH bvh; buildBVH(positions, indices, n_triangles, bvh);
         if (info) {
-            info->n_nodes = bvh.nNodes; info->n_leaves = bvh.nLeaves; info->n_triangle_refs = bvh.nTriRefs; info->max_depth = bvh.maxDepth;
-            info->node_bytes = 128; info->triangle_bytes = 48; info->sah_cost = bvh.sahCost; info->build_ms = bvh.buildMs;
+            info->n_nodes = bvh.nWNodes; info->n_leaves = bvh.nLeaves; info->n_triangle_refs = bvh.nTriRefs; info->max_depth = bvh.wMaxDepth;
+            info->node_bytes = 80; info->triangle_bytes = 48; info->sah_cost = bvh.wSahCost; info->build_ms = bvh.buildMs;
         }
         if (scene_box6) for (int a = 0; a < 3; ++a) { scene_box6[a] = bvh.sceneMin[a]; scene_box6[3 + a] = bvh.sceneMax[a]; }
         return PHIP_OK;

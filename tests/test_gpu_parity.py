@@ -780,6 +780,37 @@ def test_cornell_with_33_to_64_records_keeps_the_dealt_traversal(gpu, oracle, ga
         assert same == 1.0
 
 
+def _spine_scene(gauss, w=32, h=32, n=60):
+    """60 triangles of geometrically growing size strung out along a diagonal, each enclosing box containing all the smaller ones, and a two-triangle light: 62 Wald
+    records whose SAH tree is one long spine -- the deepest binary tree the builder makes of so few triangles"""
+    rng = np.random.default_rng(11)
+    size = 1e-2 * 1.3 ** np.arange(n)                            # almost seven orders of magnitude
+    centre = np.stack([size * 3.0, np.zeros(n), size * 3.0], 1)
+    tri = rng.normal(size=(n, 3, 3)) * size[:, None, None] * 0.7 + centre[:, None, :]
+    P = tri.reshape(-1, 3).astype(np.float32)
+    T = np.arange(3 * n, dtype=np.uint32).reshape(n, 3)
+    sb = S.SceneBuilder()
+    sb.mesh(P, T, sb.twosided(sb.diffuse((0.7, 0.6, 0.5))))
+    ext = float(np.abs(P).max())
+    black = sb.diffuse((0, 0, 0))
+    sb.quad((-ext, 2 * ext, -ext), (ext, 2 * ext, -ext), (ext, 2 * ext, ext), (-ext, 2 * ext, ext), black, facing=(0, -1, 0), radiance=(8.0, 8.0, 8.0))
+    sb.perspective((0.3 * ext, 0.5 * ext, -2.0 * ext), (0.3 * ext, 0.0, 0.3 * ext), (0, 1, 0), 50.0, near=1e-4 * ext, far=10 * ext)
+    sb.hdrfilm(w, h, gauss)
+    return sb
+
+
+def test_deep_tree_of_at_most_64_records_keeps_the_packed_leaf_table(gpu, oracle, gauss):
+    """The packed leaf table has no stack, so the depth of the tree its leaves come from decides nothing: a spine of 62 records is served by the fused kernel like
+    every other scene of its size (HISTORY.md, "The 4-wide tree leaves the host": such a scene used to fall to the wavefront kernels).  Bit-identical samples on
+    every device path."""
+    from mitsuba_amd.integrator import Scene
+    desc = _spine_scene(gauss).desc()
+    assert desc.n_triangles == 62
+    gs = Scene(desc); info = gs.accel_info().as_dict(); gs.close()
+    assert info["fits_lds"] == 1 and info["fused_traversal"] == 3, info
+    compare_render(gpu, oracle, desc, 4)
+
+
 def test_fused_kernel_64_record_work_list_overflow_matches_oracle(gpu, oracle, gauss):
     """the overflow scene of the test above with 64 sheets: every record bit of BOTH mask words set for the camera rays, ~3800 pairs per wave"""
     sb = _sheets_scene(gauss, n=31)
