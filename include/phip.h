@@ -310,12 +310,17 @@ typedef struct phip_render_params {
 #define PHIP_FLAG_ENVMAP_BILINEAR_BACKGROUND 4   /* directly visible envmap pixels: unfiltered level-0 lookup instead of the reference's EWA filter (deviation!) */
 #define PHIP_FLAG_ACCUMULATE 8      /* add to the film of the previous call instead of overwriting it (progressive rendering) */
 #define PHIP_FLAG_ALIAS_DEVICES 16  /* devices[] may name one GPU several times (exercises the multi-device path on a 1-GPU box) */
-#define PHIP_FLAG_NO_FUSED 32       /* never use the fused single-kernel path (k_mega) nor the one-kernel iterations (k_shade_trace) -- A/B and parity tests of the wavefront kernels on small scenes */
-#define PHIP_FLAG_NO_MEGA 64        /* not k_mega, but k_shade_trace where the scene admits it (a small scene with glass / copper runs k_mega since round 5: how the tests still reach
-                                       k_shade_trace on it; the kernel's own clients are small scenes with textures or an environment emitter) */
+#define PHIP_FLAG_NO_FUSED 32       /* never use the fused single-kernel path (k_mega) nor the one-kernel iterations (k_shade_trace, k_shade_trace_w) -- A/B and parity tests of the wavefront kernels on small scenes */
+#define PHIP_FLAG_NO_MEGA 64        /* not k_mega, but the one-kernel iterations where the scene admits them: k_shade_trace on a small scene (with glass / copper it runs k_mega since round 5:
+                                       how the tests still reach k_shade_trace on it), k_shade_trace_w on a scene k_mega serves on the 8-wide tree in memory (fused_traversal 4 / 5; where that kernel is on: PHIP_FLAG_FUSED_ANY).  The
+                                       kernels' own clients are scenes with textures or an environment emitter */
 #define PHIP_FLAG_FUSED_ANY 128     /* the fused kernel on EVERY scene it admits (round 6: k_mega walks the 8-wide tree from memory, phip_accel_info.fused_traversal 4 / 5) -- by default
-                                       only trees of at most PHIP_FUSED_WIDE_MAX_NODES wide nodes run it, the wavefront kernels are faster beyond; parity tests and A/B */
+                                       only trees of at most PHIP_FUSED_WIDE_MAX_NODES wide nodes run it, the wavefront kernels are faster beyond; parity tests and A/B.
+                                       Likewise the one-kernel iterations on the 8-wide tree (k_shade_trace_w: every scene past the packed leaf table that k_mega did not take,
+                                       textures / an environment emitter included; `path` and `volpath_simple`): by default on trees of at most
+                                       PHIP_SHADE_TRACE_WIDE_MAX_NODES wide nodes, with this flag on every tree */
 #define PHIP_FUSED_WIDE_MAX_NODES 4096
+#define PHIP_SHADE_TRACE_WIDE_MAX_NODES 0   /* measured: at no tree size is k_shade_trace_w ahead of k_shade + k_rays_w by more than the step spread -- PHIP_FLAG_FUSED_ANY only */
 
 typedef struct phip_stats {
     uint64_t samples;                /* camera samples rendered by this call                  */
@@ -328,8 +333,10 @@ typedef struct phip_stats {
     uint64_t shadow_triangle_tests;
     uint64_t invalid_samples;        /* rejected by the ImageBlock::put validity check        */
     uint32_t iterations;             /* wavefront iterations = launches of each kernel        */
-    uint32_t vertex_traced;          /* 1: the iterations ran k_shade_trace -- vertex, shadow ray and next ray of a slot in ONE kernel per iteration (small scenes
-                                        that are not k_mega's: <= 64 Wald records, any material); trace / shadow ms are then 0.  (`reserved`, always 0, before round 5) */
+    uint32_t vertex_traced;          /* 1: the iterations ran k_shade_trace / k_shade_trace_w -- vertex, shadow ray and next ray of a slot in ONE kernel per iteration (scenes
+                                        that are not k_mega's: <= 64 Wald records with any material; a scene on the 8-wide tree under PHIP_FLAG_FUSED_ANY, or with a tree of at most
+                                        PHIP_SHADE_TRACE_WIDE_MAX_NODES wide nodes); trace / shadow ms are then 0.  0 for a job that gave such a pass up and went on with the wavefront
+                                        kernels.  (`reserved`, always 0, before round 5) */
     double   render_ms;              /* host wall clock of the call                           */
     double   trace_kernel_ms;        /* sum of HIP-event durations of the closest-hit kernel  */
     double   shadow_kernel_ms;       /* ... of the any-hit kernel                             */

@@ -28,6 +28,7 @@ PHIP_FLAG_NO_FUSED = 32
 PHIP_FLAG_NO_MEGA = 64
 PHIP_FLAG_FUSED_ANY = 128
 PHIP_FUSED_WIDE_MAX_NODES = 4096
+PHIP_SHADE_TRACE_WIDE_MAX_NODES = 0         # k_shade_trace_w by default on trees up to this size: none (measured) -- PHIP_FLAG_FUSED_ANY runs it on every tree
 PHIP_NO_HIT = 0xFFFFFFFF
 
 

@@ -44,6 +44,9 @@ MEGA_FLAGS = ["-mllvm", "-disable-machine-licm"]
 SHADE_FEATS, SHADE_PARTS = (11, 3, 2, 1, 8, 0), (0, 1, 3, 2)
 UNITS = [("phip_shade.hip", ["-DSHADE_FEAT=%d" % f, "-DSHADE_PART=%d" % q], "phip_shade%d_%d.o" % (f, q)) for f in SHADE_FEATS for q in SHADE_PARTS] + \
         [("phip_mega.hip", MEGA_FLAGS + ["-DMEGA_PART=0"], "phip_mega.o"), ("phip_mega.hip", MEGA_FLAGS + ["-DMEGA_PART=1"], "phip_megaw.o"), ("phip_mega.hip", MEGA_FLAGS + ["-DMEGA_PART=2"], "phip_megad.o"), ("phip.hip", [], "phip.o")]
+# phip_shade_w.hip (k_shade_trace_w: a persistent loop around the vertex code, so MachineLICM costs it what it costs k_mega -- 164..580 B of scratch per lane with it,
+# 12..308 B without): once per feature set, appended so that the units above keep their place
+UNITS += [("phip_shade_w.hip", MEGA_FLAGS + ["-DSHADE_FEAT=%d" % f], "phip_tracew%d.o" % f) for f in SHADE_FEATS]
 
 
 DEBUG_UNIT = ("phip.hip", ["-DPHIP_DEBUG_HOOKS=1"], "phip_dbg.o")
@@ -113,12 +116,14 @@ def _build_locked(sid, out_lib, verbose):
     # as many compilers at a time as there are cores, longest unit first (measured seconds per feature set and part; the order of UNITS is part of the build id,
     # the order of submission is not)
     feat_cost = {11: 55.0, 3: 41.0, 2: 29.0, 1: 14.0, 8: 9.0, 0: 11.0}
+    import re
     def cost(cmd):
         name = os.path.basename(cmd[-1])
         if name.startswith("phip_shade"):
-            import re
             f, q = re.match(r"phip_shade(\d+)_(\d)", name).groups()
             return feat_cost.get(int(f), 20.0) * (0.42 if q == "2" else 1.0)
+        if name.startswith("phip_tracew"):
+            return 2.0 * feat_cost.get(int(re.match(r"phip_tracew(\d+)", name).group(1)), 20.0)
         return 31.0 if name.startswith("phip_mega") else 14.0
     cmds.sort(key=cost, reverse=True)
     import concurrent.futures
@@ -154,6 +159,8 @@ TEST_VARIANTS = {"fault": "-DMEGA_MB_FAULT=1",       # waves of fused launches r
                                                      # choose others): the frame must come from the re-rendered pass
                  "cap32": "-DWP_CAP=32u",            # 32-entry task stacks: nearly every push of a big scene spills to memory
                  "overflow": "-DWP_CAP=64u -DWP_SPILL_CAP=64u"}      # 128-entry task stacks, half of them spilled: the tree-in-memory scenes outgrow them -- the wave stops, the pass is re-rendered
+# sources whose objects a variant takes from the product build: its flags do not concern them (the task stacks are k_mega's and k_shade_trace_w's)
+VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip", "cap32": "phip_shade.hip", "overflow": "phip_shade.hip"}
 
 
 def build_test_variant(tag):
@@ -161,7 +168,7 @@ def build_test_variant(tag):
     import sys
     out = os.path.join(BUILD, "libphip_%s.so" % tag)
     root = os.path.dirname(HERE)
-    env = dict(os.environ, PHIP_BUILD_OUTPUT=out, PHIP_EXTRA_HIPCC_FLAGS=TEST_VARIANTS[tag], PHIP_BUILD_REUSE="phip_shade.hip")
+    env = dict(os.environ, PHIP_BUILD_OUTPUT=out, PHIP_EXTRA_HIPCC_FLAGS=TEST_VARIANTS[tag], PHIP_BUILD_REUSE=VARIANT_REUSE[tag])
     env.pop("PHIP_LIB", None)
     r = subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, %r); from mitsuba_amd import _ffi; print(_ffi.build())" % root], env=env, capture_output=True, text=True)
     if r.returncode != 0 or not os.path.exists(out):

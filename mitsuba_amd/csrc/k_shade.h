@@ -29,7 +29,8 @@ __device__ __forceinline__ void shadeEpilogue(const DevScene &S, const PathPool 
                                               const uint32_t slot, const bool inRange, uint4 info, const bool alive, bool needNew,
                                               const bool pushShadow, const float4 sh0, const float4 sh1, const float4 sh2,
                                               const unsigned long long vertices, const unsigned long long done,
-                                              float4 *outRo = nullptr, float4 *outRd = nullptr, bool *outAlive = nullptr /* k_shade_trace: the camera ray a regenerated slot starts with, and whether the slot has a ray to trace */) {
+                                              float4 *outRo = nullptr, float4 *outRd = nullptr, bool *outAlive = nullptr /* k_shade_trace: the camera ray a regenerated slot starts with, and whether the slot has a ray to trace */,
+                                              const uint32_t blk = blockIdx.x /* the block of BLOCK slots this thread block works on (k_shade_trace_w: a persistent grid walks them) */) {
     /* ---- shadow queue: compact this block's entries to the front of its own region (no global atomics) ---- */
     uint32_t shadowTotal = 0;
     {
@@ -41,12 +42,12 @@ __device__ __forceinline__ void shadeEpilogue(const DevScene &S, const PathPool 
 #pragma unroll
         for (uint32_t w = 0; w < BLOCK / 64; ++w) { const uint32_t c = waveCnt[w]; if (w < wave) base += c; total += c; }
         if (pushShadow) {
-            const size_t sidx = (size_t) blockIdx.x * BLOCK + base + (uint32_t) __popcll(m & ((1ull << lane) - 1ull));
+            const size_t sidx = (size_t) blk * BLOCK + base + (uint32_t) __popcll(m & ((1ull << lane) - 1ull));
             float4 e0 = sh0, e1 = sh1;
             if (S.preclip) preclipShadow(S, e0, e1);
             P.shadow[3 * sidx] = e0; P.shadow[3 * sidx + 1] = e1; P.shadow[3 * sidx + 2] = sh2;
         }
-        if (threadIdx.x == 0) P.shadowCount[blockIdx.x] = total;
+        if (threadIdx.x == 0) P.shadowCount[blk] = total;
         shadowTotal = total;
     }
 
@@ -82,7 +83,7 @@ __device__ __forceinline__ void shadeEpilogue(const DevScene &S, const PathPool 
             __shared__ unsigned long long dynBase;
             __shared__ uint32_t dynShard;
             if (threadIdx.x == 0) {
-                uint32_t sh = (blockIdx.x + rc.blockShard[blockIdx.x]) % DYN_SHARDS;    /* blockShard = shards this block has seen run dry */
+                uint32_t sh = (blk + rc.blockShard[blk]) % DYN_SHARDS;    /* blockShard = shards this block has seen run dry */
                 uint32_t dry = 0;
                 unsigned long long base = ~0ull;
                 for (int tries = 0; tries < DYN_SHARDS; ++tries) {
@@ -90,7 +91,7 @@ __device__ __forceinline__ void shadeEpilogue(const DevScene &S, const PathPool 
                     if (old < rc.shardIds) { base = old; break; }
                     sh = (sh + 1) % DYN_SHARDS; ++dry;     /* this shard is used up: move on for good */
                 }
-                if (dry) rc.blockShard[blockIdx.x] += dry;
+                if (dry) rc.blockShard[blk] += dry;
                 dynBase = base; dynShard = sh;
             }
             __syncthreads();
@@ -132,13 +133,13 @@ __device__ __forceinline__ void shadeEpilogue(const DevScene &S, const PathPool 
         nowAlive = true;
     }
     if (outAlive) *outAlive = nowAlive;
-    const uint32_t waveId = (blockIdx.x * BLOCK + threadIdx.x) >> 6;      /* the wave's position in the grid (NOT slot >> 6: k_shade may have permuted the block's slots) */
+    const uint32_t waveId = (blk * BLOCK + threadIdx.x) >> 6;      /* the wave's position in the grid (NOT slot >> 6: k_shade may have permuted the block's slots) */
     /* a slot still waiting for a dynamic sample id counts as live for the termination test */
     const bool live = nowAlive || (inRange && info.w == F_DYNAMIC);
     /* the block retires once none of its slots will ever work again and its last shadow entries have been consumed
        (this launch queued nothing, so shadowCount is 0): later launches of the pass return at the first line */
     const bool retire = !__syncthreads_or(live ? 1 : 0) && shadowTotal == 0;
-    if (retire && threadIdx.x == 0) P.blockDead[blockIdx.x] = 1u;
+    if (retire && threadIdx.x == 0) P.blockDead[blk] = 1u;
     if (inRange || (slot & ~63u) < P.capacity) {
         waveStat(P, ST_VERTICES, waveId, vertices);
         waveStat(P, ST_SAMPLES, waveId, done);

@@ -12,9 +12,10 @@
  *       BSDF models when the tree is the packed leaf table of <= 64 Wald records): k_mega keeps a path in registers from the camera sample to its end;
  *       HBM sees one 16-byte store per sample (k_mega.h)
  *   vertex-traced (small scenes k_mega does not serve: bitmap textures, an environment emitter): k_shade_trace -- the wavefront's pool, but ONE kernel per
- *       iteration that shades a slot's vertex and traces its shadow ray and its next ray on the packed leaf table in LDS (k_shade_trace.h)
+ *       iteration that shades a slot's vertex and traces its shadow ray and its next ray on the packed leaf table in LDS (k_shade_trace.h); scenes of that
+ *       kind whose tree lives in L2: k_shade_trace_w, the same iteration on the 8-wide tree in memory (k_shade_trace_w.h)
  *
- * libphip.so is 26 objects of three sources (phip_common.h).  Kernels and where they live:
+ * libphip.so is 34 objects of four sources (phip_common.h).  Kernels and where they live:
  *   k_pool.h      PathPool (HBM layout of the slots), slot flags, RenderConst, per-wave statistics, the sample streams' entry points
  *   k_traverse.h  the packed leaf tables of the LDS-resident trees with the Wald tests dealt over the wave (traverseFlat2W), the LDS-staged tree
  *                 and Wald records                                                                        [this unit, phip_mega.hip, phip_shade.hip]
@@ -26,6 +27,7 @@
  *                 order.  volpath_simple is a uniform branch of shadeVertex.                                      [phip_shade.hip]
  *   k_shade_direct.h  MIDirectIntegrator::Li on the same pool                                                     [phip_shade.hip]
  *   k_shade_trace.h   the one-kernel iterations of the small scenes                                               [phip_shade.hip]
+ *   k_shade_trace_w.h the one-kernel iterations on the 8-wide tree in memory                                      [phip_shade_w.hip]
  *   k_mega.h      the fused kernel                                                                                [phip_mega.hip]
  *   k_film.h      k_film_splat + k_film_merge (filters of reach <= 2 pixels: register accumulators, no float atomics, deterministic), k_film_tiled /
  *                 k_film (wider filters, small blocks): ImageBlock::put, include/mitsuba/render/imageblock.h:124-204;
@@ -229,6 +231,7 @@ struct phip_scene {
     bool flatTrace = false;          /* not a scene of k_mega, but its tree is the packed leaf table (<= 64 Wald records) and emitter table + materials fit LDS: k_shade_trace */
     bool wideOnly = false;           /* the device holds the compressed 8-wide BVH the ray kernels walk (every scene has it) and nothing else (more than 64 Wald records): no leaf table, no LDS-resident kernels */
     bool fitsLds = false;            /* tree, Wald records, shading records, emitter table and materials fit the fused kernel's LDS plan */
+    bool wideTrace = false;          /* k_shade_trace_w can run the scene's iterations: it is on the 8-wide tree only, with any feature set k_shade serves (textures, UVs, `constant`, `envmap`) */
     int fusedWide = 0;               /* round 6: 4 / 5 = the fused kernel walks the 8-wide tree from memory (k_mega<.., FLAT 4 / 5, ..>: emitter table in LDS; materials in LDS / in memory) */
     std::vector<std::unique_ptr<SceneDev>> devs;
     int *cancelFlag = nullptr;       /* host-pinned (portable, mapped): phip_cancel writes it, host loops and k_mega poll it */
@@ -772,7 +775,7 @@ struct SceneBuild {
         D.flatMode = flat.empty() ? 0u : (sc->bvh.tris.size() / 12 <= 32 ? 2u : 3u); D.nFlatLeaves = (uint32_t) (flat.size() / 2);
     }
 
-    /* which device path serves the scene: fitsLds (k_mega on the LDS-resident tree), fusedWide (k_mega on the 8-wide tree), flatTrace (k_shade_trace);
+    /* which device path serves the scene: fitsLds (k_mega on the LDS-resident tree), fusedWide (k_mega on the 8-wide tree), flatTrace (k_shade_trace), wideTrace (k_shade_trace_w);
        the deal region at the front of k_mega's dynamic LDS, the lane deal of the shading kernels */
     void chooseDevicePaths() {
         const int mask = sc->materialMask;
@@ -782,6 +785,7 @@ struct SceneBuild {
         sc->fusedWide = (sc->wideOnly && !sc->hasTextures && envEmitter < 0 && stride == TRISHADE_FLOAT4S && tab.size() <= EMITTER_LDS_FLOATS
                          && sc->bvh.wtris.size() / 12 < WP_TRI_MAX)
                       ? (mats.size() <= MATERIAL_LDS_MAX ? 4 : 5) : 0;
+        sc->wideTrace = sc->wideOnly && sc->bvh.wtris.size() / 12 < WP_TRI_MAX;
         const bool traceable = D.flatMode >= 2 && tab.size() <= EMITTER_LDS_FLOATS && mats.size() <= MATERIAL_LDS_MAX;
         sc->flatTrace = !sc->fitsLds && traceable; sc->flatTraceToo = sc->fitsLds && traceable;
         /* k_mega deals the Wald tests of the packed table over the wave through LDS buffers at the front of its dynamic LDS
@@ -951,6 +955,27 @@ static void phipLaunchShadeTrace(int feat, bool strictNormals, int materialMask,
         default: phipLaunchShadeTraceF3(strictNormals, materialMask, grid, lds, stream, S, P, rc, L); break;
     }
 }
+static int phipShadeTraceWidePlan(int feat, bool strictNormals, int materialMask, uint32_t nodeCache, size_t *lds) {
+    switch (feat & 11) {
+        case 0: return phipShadeTraceWidePlanF0(strictNormals, materialMask, nodeCache, lds);
+        case 1: return phipShadeTraceWidePlanF1(strictNormals, materialMask, nodeCache, lds);
+        case 2: return phipShadeTraceWidePlanF2(strictNormals, materialMask, nodeCache, lds);
+        case 8: return phipShadeTraceWidePlanF8(strictNormals, materialMask, nodeCache, lds);
+        case 11: return phipShadeTraceWidePlanF11(strictNormals, materialMask, nodeCache, lds);
+        default: return phipShadeTraceWidePlanF3(strictNormals, materialMask, nodeCache, lds);
+    }
+}
+static void phipLaunchShadeTraceWide(int feat, bool strictNormals, int materialMask, dim3 grid, size_t lds, hipStream_t stream,
+                                     const DevScene &S, const PathPool &P, const RenderConst &rc, float4 *L, uint32_t nodeCache) {
+    switch (feat & 11) {
+        case 0: phipLaunchShadeTraceWideF0(strictNormals, materialMask, grid, lds, stream, S, P, rc, L, nodeCache); break;
+        case 1: phipLaunchShadeTraceWideF1(strictNormals, materialMask, grid, lds, stream, S, P, rc, L, nodeCache); break;
+        case 2: phipLaunchShadeTraceWideF2(strictNormals, materialMask, grid, lds, stream, S, P, rc, L, nodeCache); break;
+        case 8: phipLaunchShadeTraceWideF8(strictNormals, materialMask, grid, lds, stream, S, P, rc, L, nodeCache); break;
+        case 11: phipLaunchShadeTraceWideF11(strictNormals, materialMask, grid, lds, stream, S, P, rc, L, nodeCache); break;
+        default: phipLaunchShadeTraceWideF3(strictNormals, materialMask, grid, lds, stream, S, P, rc, L, nodeCache); break;
+    }
+}
 static void phipLaunchShadeDirect(int feat, int materialMask, dim3 grid, hipStream_t stream,
                                   const DevScene &S, const PathPool &P, const RenderConst &rc, float4 *L) {
     switch (feat & 11) {
@@ -1091,7 +1116,9 @@ struct FusedPlan {
 
 /* The wavefront kernels for one render call (set up only when that path runs): pool, kernel choice, grids */
 struct WavefrontPlan {
-    bool shadeTrace = false;                /* k_shade_trace: the vertex kernel traces both rays of the iteration itself */
+    bool shadeTrace = false;                /* k_shade_trace / k_shade_trace_w: the vertex kernel traces both rays of the iteration itself */
+    bool wideTrace = false;                 /* ... on the 8-wide tree in memory (k_shade_trace_w: a persistent grid; a wave whose task stack overflows gives the pass up) */
+    uint32_t traceNodeCache = 0; size_t wideTraceLds = 0; dim3 gridTrace = dim3(1);
     uint32_t capacity = 0, nWaves = 0, nBlocks = 0;
     int feat = 0;                           /* FEAT of the shading kernels: 1 environment emitter, 2 bitmap textures, 8 the QMC samplers */
     size_t wideLds = 0, shadeTraceLds = 0;
@@ -1253,6 +1280,11 @@ static void planFused(RenderJob &J) {
     sd.fused = F.on;
     /* ... or k_shade_trace: the scene's tree is the packed leaf table, but k_mega does not serve it (glass / copper / textures / environment emitter) */
     J.wf.shadeTrace = !F.on && (sc->flatTrace || sc->flatTraceToo) && !J.direct && !(p->flags & PHIP_FLAG_NO_FUSED);
+    /* ... or k_shade_trace_w: the same iterations on the 8-wide tree in memory, by default where they are faster than k_shade + k_rays_w -- measured: nowhere by more than the
+       step spread, PHIP_SHADE_TRACE_WIDE_MAX_NODES is 0 -- with PHIP_FLAG_FUSED_ANY wherever they can run.  (PHIP_FLAG_NO_MEGA keeps k_mega off a scene of its
+       tree-in-memory builds: with both flags such a scene ends here.) */
+    J.wf.wideTrace = !F.on && sc->wideTrace && (sc->bvh.nWNodes <= PHIP_SHADE_TRACE_WIDE_MAX_NODES || (p->flags & PHIP_FLAG_FUSED_ANY)) && !J.direct && !(p->flags & PHIP_FLAG_NO_FUSED);
+    J.wf.shadeTrace = J.wf.shadeTrace || J.wf.wideTrace;
     if (!F.on) return;
 
     /* resident grid and per-wave statistics rows */
@@ -1305,6 +1337,17 @@ static void setupWavefrontGrids(RenderJob &J) {
     wf.pgridRays = dim3((unsigned) std::max(1, std::min<int>(nCU * n, (int) ((capacity + WIDE_BLOCK - 1) / WIDE_BLOCK))));
     /* k_rays_w draws its chunks from sharded counters */
     if (J.sd.drawCounters.n < 2 * RAY_SHARDS * RAY_SHARD_STRIDE) J.sd.drawCounters.alloc(2 * RAY_SHARDS * RAY_SHARD_STRIDE);
+    /* k_shade_trace_w: persistent too -- its resident set as the runtime counts it, walking the pool's blocks of slots.  Its waves' task stacks spill into the buffer that
+       covers k_rays_w's grid (setupWavefront: up to 8 blocks of 256 lanes per CU, SPILL_DEPTH words per lane), so the grid is held to the lanes that buffer has: no
+       allocation of its own, nothing new for the pool's memory fit to price.  No resident block (an LDS plan the device refuses): the wavefront kernels run */
+    if (wf.wideTrace) {
+        wf.traceNodeCache = std::min<uint32_t>(sc->bvh.nWNodes, MEGA_WIDE_NODE_CACHE);
+        const int perCU = phipShadeTraceWidePlan(wf.feat, J.p->strict_normals != 0, sc->materialMask, wf.traceNodeCache, &wf.wideTraceLds);
+        const size_t blocks = std::min<size_t>({ (size_t) nCU * (size_t) std::max(perCU, 0), (size_t) capacity / BLOCK, (size_t) J.P.spillLanes / BLOCK });
+        if (getenv("PHIP_DEBUG_TIMING")) fprintf(stderr, "[phip] k_shade_trace_w: %d blocks per CU with %zu bytes of dynamic LDS, grid %zu\n", perCU, wf.wideTraceLds, blocks);
+        if (blocks == 0) wf.wideTrace = wf.shadeTrace = false;
+        else wf.gridTrace = dim3((unsigned) blocks);
+    }
 }
 
 /* The wavefront path's pool, sized for a first pass of idsFirstPass sample ids and for the memory that is free now; then its kernels and grids */
@@ -1496,8 +1539,9 @@ static void launchRayKernels(RenderJob &J) {
     if (J.timing) J.evTrace.record(stream);
 }
 
-/* One pass on the wavefront kernels: the pool's slots draw sample ids until none is left, one vertex of every live path per iteration */
-static void wavefrontPass(RenderJob &J) {
+/* One pass on the wavefront kernels: the pool's slots draw sample ids until none is left, one vertex of every live path per iteration.
+   false: a wave of k_shade_trace_w gave the pass up (a task stack outgrew LDS + spill buffer, k_wide_wave.h) -- L is incomplete, the caller renders the pass again */
+static bool wavefrontPass(RenderJob &J) {
     using clk = std::chrono::steady_clock;
     phip_scene *sc = J.sc; SceneDev &sd = J.sd; const WavefrontPlan &wf = J.wf; hipStream_t stream = J.stream;
     RenderConst &rc = J.rc; Counters &hc = J.hc;
@@ -1524,12 +1568,16 @@ static void wavefrontPass(RenderJob &J) {
     uint32_t iter = 0;
     bool done = rc.totalIds == 0;
     bool drainingSeen = false;                          /* a termination test has counted fewer live slots than the pool holds: blocks may have retired */
+    static_assert(ST_GAVE_UP == ST_ALIVE + 1, "the termination test of k_shade_trace_w's passes sums the live-slot row and the gave-up row in one launch");
+    const unsigned pollRows = wf.wideTrace ? 2u : 1u;   /* k_shade_trace_w: ... and the row in which a wave says that it gave up */
+    hc.total[ST_GAVE_UP] = 0;
     while (!done) {
         const bool check = ((iter + 1) & 7) == 0 || rc.totalIds <= (unsigned long long) capacity * 4;
         rc.countAlive = check ? 1 : 0;
         rc.draining = drainingSeen ? 1u : 0u;
         if (J.timing) J.evShade.record(stream);
         if (J.direct) phipLaunchShadeDirect(wf.feat, sc->materialMask, wf.grid, stream, J.D, J.P, rc, sd.L.p);
+        else if (wf.wideTrace) phipLaunchShadeTraceWide(wf.feat, rc.strictNormals != 0, sc->materialMask, wf.gridTrace, wf.wideTraceLds, stream, J.D, J.P, rc, sd.L.p, wf.traceNodeCache);
         else if (wf.shadeTrace) phipLaunchShadeTrace(wf.feat, rc.strictNormals != 0, sc->materialMask, wf.grid, wf.shadeTraceLds, stream, J.D, J.P, rc, sd.L.p);
         else phipLaunchShade(wf.feat, rc.strictNormals != 0, sc->materialMask, wf.grid, stream, J.D, J.P, rc, sd.L.p);
         if (J.timing) J.evShade.record(stream);
@@ -1537,16 +1585,16 @@ static void wavefrontPass(RenderJob &J) {
         ++iter;
         if (check) {
             /* termination test: only the live-slot row (and, for a progress callback, the finished-sample row) is summed inside the loop */
-            HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_ALIVE], 0, sizeof(unsigned long long), stream));
-            hipLaunchKernelGGL(k_reduce_stats, dim3(1, REDUCE_SPLIT), dim3(256), 0, stream, J.P, sd.counters.p, (int) ST_ALIVE);
-            HIP_TRY(hipMemcpyAsync(&hc.total[ST_ALIVE], &sd.counters.p->total[ST_ALIVE], sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_ALIVE], 0, pollRows * sizeof(unsigned long long), stream));
+            hipLaunchKernelGGL(k_reduce_stats, dim3(pollRows, REDUCE_SPLIT), dim3(256), 0, stream, J.P, sd.counters.p, (int) ST_ALIVE);
+            HIP_TRY(hipMemcpyAsync(&hc.total[ST_ALIVE], &sd.counters.p->total[ST_ALIVE], pollRows * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
             if (J.p->progress) {
                 HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_SAMPLES], 0, sizeof(unsigned long long), stream));
                 hipLaunchKernelGGL(k_reduce_stats, dim3(1, REDUCE_SPLIT), dim3(256), 0, stream, J.P, sd.counters.p, (int) ST_SAMPLES);
                 HIP_TRY(hipMemcpyAsync(&hc.total[ST_SAMPLES], &sd.counters.p->total[ST_SAMPLES], sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
             }
             HIP_TRY(hipStreamSynchronize(stream));
-            if (hc.total[ST_ALIVE] == 0) done = true;
+            if (hc.total[ST_ALIVE] == 0 || hc.total[ST_GAVE_UP] != 0) done = true;
             if (hc.total[ST_ALIVE] < capacity) drainingSeen = true;
             J.progress(J.samplesDone + hc.total[ST_SAMPLES]);
             if (cancelRequested(sc)) { J.cancelled = true; done = true; }
@@ -1554,8 +1602,16 @@ static void wavefrontPass(RenderJob &J) {
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
+    if (wf.wideTrace && iter && !J.cancelled && hc.total[ST_GAVE_UP] == 0) {      /* (the last termination test may lie before the launch in which a wave gave up) */
+        HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_GAVE_UP], 0, sizeof(unsigned long long), stream));
+        hipLaunchKernelGGL(k_reduce_stats, dim3(1, REDUCE_SPLIT), dim3(256), 0, stream, J.P, sd.counters.p, (int) ST_GAVE_UP);
+        HIP_TRY(hipMemcpyAsync(&hc.total[ST_GAVE_UP], &sd.counters.p->total[ST_GAVE_UP], sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (hc.total[ST_GAVE_UP] != 0 && !J.cancelled) return false;      /* (its launches are not iterations of the job) */
     if (getenv("PHIP_DEBUG_TIMING")) fprintf(stderr, "[phip] setup %.2f ms, loop %.2f ms (%u iterations)\n", std::chrono::duration<double, std::milli>(tLoop0 - J.t0).count(), std::chrono::duration<double, std::milli>(clk::now() - tLoop0).count(), iter);
     J.st.iterations += iter;
+    return true;
 }
 
 /* round 4: one pass over L with the footprint sums in registers, then an ordered merge of the 16 x 16 patch images (k_film.h) */
@@ -1650,7 +1706,13 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
                 setupWavefront(J, J.rc.totalIds);
             }
         }
-        if (!J.F.on) wavefrontPass(J);
+        if (!J.F.on && !wavefrontPass(J)) {
+            /* k_shade_trace_w gave the pass up: this pass again, and the rest of the job, on k_shade + the ray kernel -- the same pool, the same passes (k_mega's contract) */
+            fprintf(stderr, "[phip] warning: the fused kernel gave up on this pass (a task stack outgrew LDS + spill buffer); samples %u.. of the job are rendered by the wavefront kernels\n",
+                    (unsigned) J.rc.sppFirst);
+            J.wf.wideTrace = J.wf.shadeTrace = false;
+            wavefrontPass(J);
+        }
         if (J.cancelled) break;                                 /* L is incomplete: no film pass */
         filmPass(J, (sppDone > 0 || accumulate) ? 1 : 0);
         passResults(J);

@@ -2,11 +2,12 @@
  * phip_common.h -- what every translation unit of libphip.so starts with: HIP, the C ABI, the device scene layout and
  * shading functions (dv_scene.h), the path-pool layout (k_pool.h), the error macro.
  *
- * libphip.so is built from three sources (26 objects) so that they compile in parallel:
+ * libphip.so is built from four sources (34 objects) so that they compile in parallel:
  *   phip.hip        host side (scene build, render loop, multi-device orchestration, C ABI) + traversal and film kernels
  *   phip_shade.hip  k_shade / k_shade_direct / k_shade_trace instantiations behind phipLaunchShade*F<n> -- compiled per feature set (-DSHADE_FEAT=0..3, 8 and 11:
  *                   environment emitter, bitmap textures, the QMC samplers) and per part (-DSHADE_PART=0..3), 24 objects: see its header
- *   phip_mega.hip   k_mega instantiations behind phipLaunchMega (-DMEGA_PART=0: scenes in LDS) / phipLaunchMegaWide (-DMEGA_PART=1: the 8-wide tree in memory)
+ *   phip_shade_w.hip  k_shade_trace_w instantiations behind phipShadeTraceWidePlanF<n> / phipLaunchShadeTraceWideF<n>, per feature set: 6 objects
+   phip_mega.hip   k_mega instantiations behind phipLaunchMega (-DMEGA_PART=0: scenes in LDS) / phipLaunchMegaWide (-DMEGA_PART=1: the 8-wide tree in memory)
  * No device function is called across units (everything on the device side is inline in headers), so no -fgpu-rdc.
  */
 #pragma once
@@ -50,6 +51,14 @@ using namespace pt;
                                   const DevScene &S, const PathPool &P, const RenderConst &rc, float4 *L);
 PHIP_DECLARE_SHADE(0) PHIP_DECLARE_SHADE(1) PHIP_DECLARE_SHADE(2) PHIP_DECLARE_SHADE(3) PHIP_DECLARE_SHADE(8) PHIP_DECLARE_SHADE(11)
 #undef PHIP_DECLARE_SHADE
+/* k_shade_trace_w<materials, strictNormals, FEAT> (phip_shade_w.hip compiled with -DSHADE_FEAT=n): its dynamic LDS with `nodeCache` staged nodes and the blocks of it
+   resident on a compute unit (0: none); the launch of its persistent grid */
+#define PHIP_DECLARE_SHADE_TRACE_WIDE(n)                                                                                           \
+    int phipShadeTraceWidePlanF##n(bool strictNormals, int materialMask, uint32_t nodeCache, size_t *ldsBytes);                    \
+    void phipLaunchShadeTraceWideF##n(bool strictNormals, int materialMask, dim3 grid, size_t ldsBytes, hipStream_t stream,        \
+                                      const DevScene &S, const PathPool &P, const RenderConst &rc, float4 *L, uint32_t nodeCache);
+PHIP_DECLARE_SHADE_TRACE_WIDE(0) PHIP_DECLARE_SHADE_TRACE_WIDE(1) PHIP_DECLARE_SHADE_TRACE_WIDE(2) PHIP_DECLARE_SHADE_TRACE_WIDE(3) PHIP_DECLARE_SHADE_TRACE_WIDE(8) PHIP_DECLARE_SHADE_TRACE_WIDE(11)
+#undef PHIP_DECLARE_SHADE_TRACE_WIDE
 /* k_mega<materials, strictNormals, traversal form> (phip_mega.hip): blocks of BLOCK threads that fit one CU with ldsBytes of dynamic LDS.
    flat 2 / 3 (DevScene::flatMode: scenes that fit LDS) live in the object compiled with -DMEGA_PART=0, flat 4 / 5 (the 8-wide tree in memory) in -DMEGA_PART=1 */
 int  phipMegaBlocksPerCU(int materialMask, bool strictNormals, int flat, bool qmc, size_t ldsBytes);
