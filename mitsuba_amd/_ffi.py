@@ -256,6 +256,7 @@ def debug_lib():
     L.phip_debug_host_build_bvh.argtypes = [fp, u32, C.POINTER(C.c_uint32), u32, C.POINTER(A.phip_accel_info), fp]
     L.phip_debug_host_trace_wide.argtypes = [fp, u32, C.POINTER(C.c_uint32), u32, C.POINTER(A.phip_ray), C.c_size_t, C.POINTER(A.phip_hit), C.c_int, C.POINTER(A.phip_accel_info), u8p, u32]
     L.phip_debug_fmath.argtypes = [C.c_int, C.c_int, C.c_size_t, fp, fp, fp]
+    L.phip_debug_selected_kernel.argtypes = [C.c_int] * 7; L.phip_debug_selected_kernel.restype = C.c_char_p
     _debug = L
     return L
 

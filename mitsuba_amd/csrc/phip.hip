@@ -15,7 +15,10 @@
  *       iteration that shades a slot's vertex and traces its shadow ray and its next ray on the packed leaf table in LDS (k_shade_trace.h); scenes of that
  *       kind whose tree lives in L2: k_shade_trace_w, the same iteration on the 8-wide tree in memory (k_shade_trace_w.h)
  *
- * libphip.so is 34 objects of four sources (phip_common.h).  Kernels and where they live:
+ * libphip.so is 34 objects of four sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
+ * at plan time (shadeUnit: the one table over the feature sets; megaKernelOf -> FusedPlan::kernel in planFused, shadeKernelOf / shadeTraceWideKernelOf ->
+ * WavefrontPlan::vertex / vertexWide in selectVertexKernel), asks the runtime for the residency of the persistent ones (residentBlocksPerCU) and launches them.
+ * Kernels and where they live:
  *   k_pool.h      PathPool (HBM layout of the slots), slot flags, RenderConst, per-wave statistics, the sample streams' entry points
  *   k_traverse.h  the packed leaf tables of the LDS-resident trees with the Wald tests dealt over the wave (traverseFlat2W), the LDS-staged tree
  *                 and Wald records                                                                        [this unit, phip_mega.hip, phip_shade.hip]
@@ -34,7 +37,7 @@
  *                 k_reduce_stats, k_export_samples                                                                [this unit]
  *
  * This file: error handling, scene construction as stages over one SceneBuild (validation, host arrays, BVH build via bvh.h, the
- * choice of the device paths, one upload; camera set-up), replication of the scene to further GPUs through SceneDev's one list of buffers, the render loop, the multi-device orchestration (one host thread + stream per GPU, ncclReduce of the
+ * choice of the device paths, one upload; camera set-up), the choice of each render's kernels, replication of the scene to further GPUs through SceneDev's one list of buffers, the render loop, the multi-device orchestration (one host thread + stream per GPU, ncclReduce of the
  * films over RCCL/xGMI) and the extern "C" entry points.  Not MFMA work: irregular traversal and gathers.
  * The product never includes, links or calls anything under oracle/.
  */
@@ -44,6 +47,9 @@
 #include "k_wide.h"
 #include "k_wide_wave.h"
 #include "k_film.h"
+#include "k_shade.h"
+#include "k_shade_trace.h"
+#include "k_shade_trace_w.h"     /* (for shadeTraceWideLdsBytes: the kernels of these three headers are templates that this unit does not instantiate) */
 #ifndef PHIP_DEBUG_HOOKS
 #define PHIP_DEBUG_HOOKS 0
 #endif
@@ -933,59 +939,58 @@ static SceneDev *replicateScene(phip_scene *sc, int device) {
     return sc->devs.back().get();
 }
 
-static void phipLaunchShade(int feat, bool strictNormals, int materialMask, dim3 grid, hipStream_t stream,
-                            const DevScene &S, const PathPool &P, const RenderConst &rc, float4 *L) {
+/* ---- which kernel a render runs (the look-ups of the other units: phip_common.h) ---- */
+/* The look-ups of one feature set of the shading kernels (FEAT: 1 environment emitter, 2 bitmap textures, 8 the QMC samplers -- without / with both other features) */
+struct ShadeUnit {
+    ShadeKernel (*shade[2])(int materialMask, int tables);      /* k_shade without / with strictNormals */
+    ShadeKernel (*direct)(int materialMask);
+    ShadeKernel (*trace)(bool strictNormals, int materialMask);
+    ShadeTraceWideKernel (*traceWide)(bool strictNormals, int materialMask);
+};
+/* The one place that maps a feature set to its objects */
+static const ShadeUnit &shadeUnit(int feat) {
+#define SHADE_UNIT(n) { { phipShadeKernelS0F##n, phipShadeKernelS1F##n }, phipShadeDirectKernelF##n, phipShadeTraceKernelF##n, phipShadeTraceWideKernelF##n }
+    static const ShadeUnit units[6] = { SHADE_UNIT(0), SHADE_UNIT(1), SHADE_UNIT(2), SHADE_UNIT(3), SHADE_UNIT(8), SHADE_UNIT(11) };
+#undef SHADE_UNIT
     switch (feat & 11) {
-        case 0: phipLaunchShadeF0(strictNormals, materialMask, grid, stream, S, P, rc, L); break;
-        case 1: phipLaunchShadeF1(strictNormals, materialMask, grid, stream, S, P, rc, L); break;
-        case 2: phipLaunchShadeF2(strictNormals, materialMask, grid, stream, S, P, rc, L); break;
-        case 8: phipLaunchShadeF8(strictNormals, materialMask, grid, stream, S, P, rc, L); break;
-        case 11: phipLaunchShadeF11(strictNormals, materialMask, grid, stream, S, P, rc, L); break;
-        default: phipLaunchShadeF3(strictNormals, materialMask, grid, stream, S, P, rc, L); break;
+        case 0: return units[0];
+        case 1: return units[1];
+        case 2: return units[2];
+        case 8: return units[4];
+        case 11: return units[5];
+        default: return units[3];
     }
 }
-static void phipLaunchShadeTrace(int feat, bool strictNormals, int materialMask, dim3 grid, size_t lds, hipStream_t stream,
-                                 const DevScene &S, const PathPool &P, const RenderConst &rc, float4 *L) {
-    switch (feat & 11) {
-        case 0: phipLaunchShadeTraceF0(strictNormals, materialMask, grid, lds, stream, S, P, rc, L); break;
-        case 1: phipLaunchShadeTraceF1(strictNormals, materialMask, grid, lds, stream, S, P, rc, L); break;
-        case 2: phipLaunchShadeTraceF2(strictNormals, materialMask, grid, lds, stream, S, P, rc, L); break;
-        case 8: phipLaunchShadeTraceF8(strictNormals, materialMask, grid, lds, stream, S, P, rc, L); break;
-        case 11: phipLaunchShadeTraceF11(strictNormals, materialMask, grid, lds, stream, S, P, rc, L); break;
-        default: phipLaunchShadeTraceF3(strictNormals, materialMask, grid, lds, stream, S, P, rc, L); break;
-    }
+/* k_shade's table set: FEAT 0 (no environment emitter, no textures, the counter stream) has builds that address the emitter table and the materials (1), or the emitter
+   table only (2), as LDS; every other feature set reads them through generic pointers (0) */
+static int shadeTableSet(int feat, const DevScene &S) {
+    if ((feat & 11) != 0 || S.emitterTabSize > EMITTER_LDS_FLOATS) return 0;
+    return S.nMaterials <= MATERIAL_LDS_MAX ? 1 : 2;
 }
-static int phipShadeTraceWidePlan(int feat, bool strictNormals, int materialMask, uint32_t nodeCache, size_t *lds) {
-    switch (feat & 11) {
-        case 0: return phipShadeTraceWidePlanF0(strictNormals, materialMask, nodeCache, lds);
-        case 1: return phipShadeTraceWidePlanF1(strictNormals, materialMask, nodeCache, lds);
-        case 2: return phipShadeTraceWidePlanF2(strictNormals, materialMask, nodeCache, lds);
-        case 8: return phipShadeTraceWidePlanF8(strictNormals, materialMask, nodeCache, lds);
-        case 11: return phipShadeTraceWidePlanF11(strictNormals, materialMask, nodeCache, lds);
-        default: return phipShadeTraceWidePlanF3(strictNormals, materialMask, nodeCache, lds);
-    }
+/* The vertex kernel of the wavefront iterations that take the pool alone: k_shade_direct (`direct`), k_shade_trace (the packed leaf table in LDS) or k_shade */
+static ShadeKernel shadeKernelOf(int feat, bool direct, bool shadeTrace, bool strictNormals, int materialMask, int tables) {
+    const ShadeUnit &u = shadeUnit(feat);
+    return direct ? u.direct(materialMask) : shadeTrace ? u.trace(strictNormals, materialMask) : u.shade[strictNormals ? 1 : 0](materialMask, tables);
 }
-static void phipLaunchShadeTraceWide(int feat, bool strictNormals, int materialMask, dim3 grid, size_t lds, hipStream_t stream,
-                                     const DevScene &S, const PathPool &P, const RenderConst &rc, float4 *L, uint32_t nodeCache) {
-    switch (feat & 11) {
-        case 0: phipLaunchShadeTraceWideF0(strictNormals, materialMask, grid, lds, stream, S, P, rc, L, nodeCache); break;
-        case 1: phipLaunchShadeTraceWideF1(strictNormals, materialMask, grid, lds, stream, S, P, rc, L, nodeCache); break;
-        case 2: phipLaunchShadeTraceWideF2(strictNormals, materialMask, grid, lds, stream, S, P, rc, L, nodeCache); break;
-        case 8: phipLaunchShadeTraceWideF8(strictNormals, materialMask, grid, lds, stream, S, P, rc, L, nodeCache); break;
-        case 11: phipLaunchShadeTraceWideF11(strictNormals, materialMask, grid, lds, stream, S, P, rc, L, nodeCache); break;
-        default: phipLaunchShadeTraceWideF3(strictNormals, materialMask, grid, lds, stream, S, P, rc, L, nodeCache); break;
-    }
+/* ... and k_shade_trace_w, which also takes the number of staged nodes */
+static ShadeTraceWideKernel shadeTraceWideKernelOf(int feat, bool strictNormals, int materialMask) {
+    return shadeUnit(feat).traceWide(strictNormals, materialMask);
 }
-static void phipLaunchShadeDirect(int feat, int materialMask, dim3 grid, hipStream_t stream,
-                                  const DevScene &S, const PathPool &P, const RenderConst &rc, float4 *L) {
-    switch (feat & 11) {
-        case 8: phipLaunchShadeDirectF8(materialMask, grid, stream, S, P, rc, L); break;
-        case 11: phipLaunchShadeDirectF11(materialMask, grid, stream, S, P, rc, L); break;
-        case 0: phipLaunchShadeDirectF0(materialMask, grid, stream, S, P, rc, L); break;
-        case 1: phipLaunchShadeDirectF1(materialMask, grid, stream, S, P, rc, L); break;
-        case 2: phipLaunchShadeDirectF2(materialMask, grid, stream, S, P, rc, L); break;
-        default: phipLaunchShadeDirectF3(materialMask, grid, stream, S, P, rc, L); break;
-    }
+/* k_mega by integrator and traversal form (k_mega.h; >= 4: the 8-wide tree in memory); nullptr: no build of it serves the form */
+static MegaKernel megaKernelOf(bool direct, int flat, int materialMask, bool strictNormals, bool qmc) {
+    return direct ? phipMegaKernelDirect(materialMask, strictNormals, flat, qmc)
+         : flat >= 4 ? phipMegaKernelWide(materialMask, strictNormals, flat, qmc) : phipMegaKernel(materialMask, strictNormals, flat, qmc);
+}
+
+/* Blocks of `block` threads and `lds` bytes of dynamic LDS of a kernel that the runtime finds resident on a compute unit (registers, static + dynamic LDS and the LDS
+   allocation granule all enter); past 48 KB the kernel's dynamic-LDS limit is raised first.  `limit` is what that call answered -- when it refused, nothing is asked and
+   blocks is 0 --, blocks is 0 too when the occupancy query fails: every caller has its own policy for the two */
+struct Residency { hipError_t limit; int blocks; };
+static Residency residentBlocksPerCU(const void *kernel, int block, size_t lds) {
+    Residency r = { hipSuccess, 0 };
+    if (lds > 48 * 1024) r.limit = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+    if (r.limit == hipSuccess && hipOccupancyMaxActiveBlocksPerMultiprocessor(&r.blocks, kernel, block, lds) != hipSuccess) r.blocks = 0;
+    return r;
 }
 
 static size_t traversalLdsBytes(const DevScene &D) {               /* k_raycast_w: blocks of BLOCK threads */
@@ -1097,16 +1102,12 @@ static void addWork(phip_stats &t, const phip_stats &a) {
     t.shadow_node_visits += a.shadow_node_visits; t.shadow_triangle_tests += a.shadow_triangle_tests;
 }
 
-/* k_mega's entry points for one traversal form (phip_common.h) */
-using MegaBlocksPerCU = int (*)(int, bool, int, bool, size_t);
-using MegaLaunch = void (*)(int, bool, int, bool, dim3, size_t, hipStream_t, const DevScene &, const MegaParams &, const RenderConst &, float4 *);
-
 /* The fused kernel for one render call: whether it runs, in which traversal form, and its resident grid */
 struct FusedPlan {
     bool on = false;                        /* the passes run on k_mega -- until one of them gives up */
     int flat = 0; bool wide = false;        /* k_mega's traversal form (k_mega.h); >= 4: the 8-wide tree in memory */
     bool strictNormals = false;
-    MegaBlocksPerCU blocksPerCU = nullptr; MegaLaunch launch = nullptr;
+    MegaKernel kernel = nullptr;            /* the build of k_mega for the render's materials, traversal form, sampler and integrator (megaKernelOf) */
     int perCU = 0; uint32_t nodeCache = 0; size_t lds = 0;
     dim3 grid = dim3(1); MegaParams M;
 #if MEGA_MB_FAULT
@@ -1118,11 +1119,14 @@ struct FusedPlan {
 struct WavefrontPlan {
     bool shadeTrace = false;                /* k_shade_trace / k_shade_trace_w: the vertex kernel traces both rays of the iteration itself */
     bool wideTrace = false;                 /* ... on the 8-wide tree in memory (k_shade_trace_w: a persistent grid; a wave whose task stack overflows gives the pass up) */
-    uint32_t traceNodeCache = 0; size_t wideTraceLds = 0; dim3 gridTrace = dim3(1);
+    /* the vertex kernel of the iterations, its grid and dynamic LDS (selectVertexKernel): k_shade, k_shade_direct or k_shade_trace with a thread per slot, or -- with
+       wideTrace -- k_shade_trace_w, a persistent grid that stages traceNodeCache nodes */
+    ShadeKernel vertex = nullptr; ShadeTraceWideKernel vertexWide = nullptr;
+    dim3 vertexGrid = dim3(1); size_t vertexLds = 0; uint32_t traceNodeCache = 0;
     uint32_t capacity = 0, nWaves = 0, nBlocks = 0;
     int feat = 0;                           /* FEAT of the shading kernels: 1 environment emitter, 2 bitmap textures, 8 the QMC samplers */
-    size_t wideLds = 0, shadeTraceLds = 0;
-    dim3 grid = dim3(1), pgridRays = dim3(1);
+    size_t wideLds = 0;
+    dim3 pgridRays = dim3(1);
 };
 
 /* One device's share of one render call: what the stages of renderOnDevice hand to each other */
@@ -1260,8 +1264,7 @@ static void planFused(RenderJob &J) {
     if (J.direct && F.flat < 2) F.on = false;      /* (round 6: `direct` rides the fused kernel too -- k_mega<.., DIRECT>, on the packed leaf tables and on the tree in memory) */
     F.wide = F.flat >= 4;
     F.strictNormals = !J.direct && p->strict_normals != 0;
-    F.blocksPerCU = J.direct ? phipMegaBlocksPerCUDirect : F.wide ? phipMegaBlocksPerCUWide : phipMegaBlocksPerCU;
-    F.launch = J.direct ? phipLaunchMegaDirect : F.wide ? phipLaunchMegaWide : phipLaunchMega;
+    F.kernel = megaKernelOf(J.direct, F.flat, sc->materialMask, F.strictNormals, J.qmc);
     /* resident blocks of the fused kernel for THIS render (the QMC build has ~15 KB more static LDS than the plan of fitsLds priced at scene
        creation): when none fits a compute unit the render runs on the wavefront kernels, as it did before the samplers moved to k_mega */
     if (F.on) {
@@ -1273,7 +1276,9 @@ static void planFused(RenderJob &J) {
         } else {
             F.lds = megaLdsBytesOf(J.D);
         }
-        F.perCU = std::min(MEGA_WAVES, F.blocksPerCU(sc->materialMask, F.strictNormals, F.flat, J.qmc, F.lds));
+        /* (no build for the form, a refused LDS limit, a failed query, no resident block: all the same to this path) */
+        const Residency r = F.kernel ? residentBlocksPerCU((const void *) F.kernel, BLOCK, F.lds) : Residency{ hipSuccess, 0 };
+        F.perCU = std::min(MEGA_WAVES, r.blocks);
         if (F.perCU <= 0) F.on = false;
         if (getenv("PHIP_DEBUG_TIMING")) fprintf(stderr, "[phip] k_mega (traversal form %d): %d blocks per CU with %zu bytes of dynamic LDS\n", F.flat, F.perCU, F.lds);
     }
@@ -1315,6 +1320,33 @@ static void planFused(RenderJob &J) {
     J.P.stat = sd.stat.p; J.P.nWaves = M.nWaves;               /* k_reduce_stats reads these two */
 }
 
+/* The vertex kernel of the wavefront iterations, resolved once: k_shade_trace_w where the render wishes it (wideTrace) and a block of it is resident, else
+   k_shade_trace where it wishes that (shadeTrace), else k_shade -- or k_shade_direct.  Sets the two flags to what was resolved; a pass that k_shade_trace_w gave up
+   comes here again for k_shade (renderOnDevice) */
+static void selectVertexKernel(RenderJob &J, bool shadeTrace, bool wideTrace) {
+    phip_scene *sc = J.sc; WavefrontPlan &wf = J.wf;
+    const bool strictNormals = J.p->strict_normals != 0;
+    wf.vertex = nullptr; wf.vertexWide = nullptr;
+    /* k_shade_trace_w: persistent -- its resident set as the runtime counts it, walking the pool's blocks of slots.  Its waves' task stacks spill into the buffer that
+       covers k_rays_w's grid (setupWavefront: up to 8 blocks of 256 lanes per CU, SPILL_DEPTH words per lane), so the grid is held to the lanes that buffer has: no
+       allocation of its own, nothing new for the pool's memory fit to price.  No resident block (an LDS plan the device refuses, a failed query): the wavefront kernels run */
+    if (wideTrace) {
+        wf.traceNodeCache = std::min<uint32_t>(sc->bvh.nWNodes, MEGA_WIDE_NODE_CACHE);
+        wf.vertexLds = shadeTraceWideLdsBytes(wf.traceNodeCache, (sc->materialMask & MM_ALL) != 0);
+        wf.vertexWide = shadeTraceWideKernelOf(wf.feat, strictNormals, sc->materialMask);
+        const int perCU = residentBlocksPerCU((const void *) wf.vertexWide, BLOCK, wf.vertexLds).blocks;
+        const size_t blocks = std::min<size_t>({ (size_t) J.nCU * (size_t) std::max(perCU, 0), (size_t) wf.capacity / BLOCK, (size_t) J.P.spillLanes / BLOCK });
+        if (getenv("PHIP_DEBUG_TIMING")) fprintf(stderr, "[phip] k_shade_trace_w: %d blocks per CU with %zu bytes of dynamic LDS, grid %zu\n", perCU, wf.vertexLds, blocks);
+        if (blocks == 0) { wf.vertexWide = nullptr; wideTrace = shadeTrace = false; }
+        else wf.vertexGrid = dim3((unsigned) blocks);
+    }
+    wf.wideTrace = wideTrace; wf.shadeTrace = shadeTrace || wideTrace;
+    if (wf.vertexWide) return;
+    wf.vertex = shadeKernelOf(wf.feat, J.direct, wf.shadeTrace, strictNormals, sc->materialMask, shadeTableSet(wf.feat, J.D));
+    wf.vertexGrid = dim3((wf.capacity + BLOCK - 1) / BLOCK);
+    wf.vertexLds = wf.shadeTrace ? shadeTraceLdsBytes(J.D) : 0;        /* (k_shade_trace: the packed leaf table, the records and the tables it stages) */
+}
+
 /* The wavefront path's kernels and grids, for the pool of setupWavefront */
 static void setupWavefrontGrids(RenderJob &J) {
     phip_scene *sc = J.sc; WavefrontPlan &wf = J.wf;
@@ -1322,32 +1354,20 @@ static void setupWavefrontGrids(RenderJob &J) {
     /* environment emitter, bitmap textures; 8: the QMC samplers (two builds: the plain one, and one with both other features) */
     const int feat0 = (D.envEmitter >= 0 ? 1 : 0) | (sc->hasTextures ? 2 : 0);
     wf.feat = J.qmc ? (feat0 ? 11 : 8) : feat0;
-    wf.shadeTraceLds = shadeTraceLdsBytes(D);
-    wf.grid = dim3((capacity + BLOCK - 1) / BLOCK);
     /* k_rays_w: blocks of WIDE_BLOCK threads with their own LDS plan.  The grid of a persistent kernel is exactly its resident set.  Residency is asked
        of the runtime (registers, the block's static + dynamic LDS and the LDS allocation granule all enter) -- an arithmetic estimate that is one block
        per CU too high makes the surplus blocks wait for a resident one to finish: a second round that doubled the ray kernel's time when the LDS node
        cache grew to 7.5 KB (round 2). */
     wf.wideLds = wideLdsBytes(D.wideNodeCache, WIDE_BLOCK) + wideDealBytes(WIDE_BLOCK);
-    if (wf.wideLds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *) k_rays_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int) wf.wideLds));
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *) k_rays_w, WIDE_BLOCK, wf.wideLds) != hipSuccess || n <= 0) n = 1;
+    const Residency rays = residentBlocksPerCU((const void *) k_rays_w, WIDE_BLOCK, wf.wideLds);
+    if (rays.limit != hipSuccess) throw std::runtime_error(std::string("k_rays_w: hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize): ") + hipGetErrorString(rays.limit));
+    int n = rays.blocks > 0 ? rays.blocks : 1;
     n = std::min(n, WIDE_WAVES * 256 / WIDE_BLOCK);
     if (n <= 0) n = 1;
     wf.pgridRays = dim3((unsigned) std::max(1, std::min<int>(nCU * n, (int) ((capacity + WIDE_BLOCK - 1) / WIDE_BLOCK))));
     /* k_rays_w draws its chunks from sharded counters */
     if (J.sd.drawCounters.n < 2 * RAY_SHARDS * RAY_SHARD_STRIDE) J.sd.drawCounters.alloc(2 * RAY_SHARDS * RAY_SHARD_STRIDE);
-    /* k_shade_trace_w: persistent too -- its resident set as the runtime counts it, walking the pool's blocks of slots.  Its waves' task stacks spill into the buffer that
-       covers k_rays_w's grid (setupWavefront: up to 8 blocks of 256 lanes per CU, SPILL_DEPTH words per lane), so the grid is held to the lanes that buffer has: no
-       allocation of its own, nothing new for the pool's memory fit to price.  No resident block (an LDS plan the device refuses): the wavefront kernels run */
-    if (wf.wideTrace) {
-        wf.traceNodeCache = std::min<uint32_t>(sc->bvh.nWNodes, MEGA_WIDE_NODE_CACHE);
-        const int perCU = phipShadeTraceWidePlan(wf.feat, J.p->strict_normals != 0, sc->materialMask, wf.traceNodeCache, &wf.wideTraceLds);
-        const size_t blocks = std::min<size_t>({ (size_t) nCU * (size_t) std::max(perCU, 0), (size_t) capacity / BLOCK, (size_t) J.P.spillLanes / BLOCK });
-        if (getenv("PHIP_DEBUG_TIMING")) fprintf(stderr, "[phip] k_shade_trace_w: %d blocks per CU with %zu bytes of dynamic LDS, grid %zu\n", perCU, wf.wideTraceLds, blocks);
-        if (blocks == 0) wf.wideTrace = wf.shadeTrace = false;
-        else wf.gridTrace = dim3((unsigned) blocks);
-    }
+    selectVertexKernel(J, wf.shadeTrace, wf.wideTrace);     /* (as planFused wished) */
 }
 
 /* The wavefront path's pool, sized for a first pass of idsFirstPass sample ids and for the memory that is free now; then its kernels and grids */
@@ -1483,6 +1503,15 @@ static void passConstants(RenderJob &J, uint32_t sppDone) {
     rc.staticIds = 0; rc.shardIds = 0; rc.countAlive = 0; rc.draining = 0;
 }
 
+/* Rows [first, first + n) of the statistics: the waves' counts summed on the device (k_reduce_stats) and their copy into J.hc queued on the job's stream.  The caller
+   synchronises -- once, however many reads its test needs */
+static void readStatRows(RenderJob &J, int first, int n) {
+    Counters *dc = J.sd.counters.p;
+    HIP_TRY(hipMemsetAsync(&dc->total[first], 0, n * sizeof(unsigned long long), J.stream));
+    hipLaunchKernelGGL(k_reduce_stats, dim3((unsigned) n, REDUCE_SPLIT), dim3(256), 0, J.stream, J.P, dc, first);
+    HIP_TRY(hipMemcpyAsync(&J.hc.total[first], &dc->total[first], n * sizeof(unsigned long long), hipMemcpyDeviceToHost, J.stream));
+}
+
 enum class FusedPass { Done, GaveUp, Cancelled };
 
 /* One launch: every path of the pass from camera sample to its last vertex (k_mega.h) */
@@ -1500,7 +1529,7 @@ static FusedPass fusedPass(RenderJob &J, uint32_t sppDone) {
 #endif
     if (rc.totalIds) {
         if (J.timing) J.evFused.record(stream);
-        F.launch(sc->materialMask, F.strictNormals, F.flat, J.qmc, F.grid, F.lds, stream, J.D, F.M, rc, sd.L.p);
+        hipLaunchKernelGGL(F.kernel, F.grid, dim3(BLOCK), F.lds, stream, J.D, F.M, rc, sd.L.p);
         if (J.timing) J.evFused.record(stream);
     }
     HIP_TRY(hipGetLastError());
@@ -1508,10 +1537,8 @@ static FusedPass fusedPass(RenderJob &J, uint32_t sppDone) {
        is incomplete: it is not added to the film -- this pass and the rest of the job run on the kernels that have no such protocol (round 6: degrade, do not fail).
        A pass that was not cancelled must also have counted exactly one sample per crop pixel of this device's blocks and sample of the pass (the ids of edge
        blocks outside the crop window are drawn and skipped: rc.totalIds counts them, the samples do not) */
-    HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_SAMPLES], 0, (ST_GAVE_UP - ST_SAMPLES + 1) * sizeof(unsigned long long), stream));
     static_assert(ST_GAVE_UP == ST_SAMPLES + 2, "the rows the host reads after a fused pass: samples .. gave up");
-    hipLaunchKernelGGL(k_reduce_stats, dim3(ST_GAVE_UP - ST_SAMPLES + 1, REDUCE_SPLIT), dim3(256), 0, stream, J.P, sd.counters.p, (int) ST_SAMPLES);
-    HIP_TRY(hipMemcpyAsync(&hc.total[ST_SAMPLES], &sd.counters.p->total[ST_SAMPLES], (ST_GAVE_UP - ST_SAMPLES + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    readStatRows(J, ST_SAMPLES, ST_GAVE_UP - ST_SAMPLES + 1);
     HIP_TRY(hipStreamSynchronize(stream));
     const bool cancelled = cancelRequested(sc);
     const bool gaveUp = hc.total[ST_GAVE_UP] != 0;
@@ -1569,30 +1596,22 @@ static bool wavefrontPass(RenderJob &J) {
     bool done = rc.totalIds == 0;
     bool drainingSeen = false;                          /* a termination test has counted fewer live slots than the pool holds: blocks may have retired */
     static_assert(ST_GAVE_UP == ST_ALIVE + 1, "the termination test of k_shade_trace_w's passes sums the live-slot row and the gave-up row in one launch");
-    const unsigned pollRows = wf.wideTrace ? 2u : 1u;   /* k_shade_trace_w: ... and the row in which a wave says that it gave up */
+    const int pollRows = wf.wideTrace ? 2 : 1;          /* k_shade_trace_w: ... and the row in which a wave says that it gave up */
     hc.total[ST_GAVE_UP] = 0;
     while (!done) {
         const bool check = ((iter + 1) & 7) == 0 || rc.totalIds <= (unsigned long long) capacity * 4;
         rc.countAlive = check ? 1 : 0;
         rc.draining = drainingSeen ? 1u : 0u;
         if (J.timing) J.evShade.record(stream);
-        if (J.direct) phipLaunchShadeDirect(wf.feat, sc->materialMask, wf.grid, stream, J.D, J.P, rc, sd.L.p);
-        else if (wf.wideTrace) phipLaunchShadeTraceWide(wf.feat, rc.strictNormals != 0, sc->materialMask, wf.gridTrace, wf.wideTraceLds, stream, J.D, J.P, rc, sd.L.p, wf.traceNodeCache);
-        else if (wf.shadeTrace) phipLaunchShadeTrace(wf.feat, rc.strictNormals != 0, sc->materialMask, wf.grid, wf.shadeTraceLds, stream, J.D, J.P, rc, sd.L.p);
-        else phipLaunchShade(wf.feat, rc.strictNormals != 0, sc->materialMask, wf.grid, stream, J.D, J.P, rc, sd.L.p);
+        if (wf.vertexWide) hipLaunchKernelGGL(wf.vertexWide, wf.vertexGrid, dim3(BLOCK), wf.vertexLds, stream, J.D, J.P, rc, sd.L.p, wf.traceNodeCache);
+        else hipLaunchKernelGGL(wf.vertex, wf.vertexGrid, dim3(BLOCK), wf.vertexLds, stream, J.D, J.P, rc, sd.L.p);
         if (J.timing) J.evShade.record(stream);
         if (!wf.shadeTrace) launchRayKernels(J);        /* (k_shade_trace traced both rays of the iteration itself: k_shade_trace.h) */
         ++iter;
         if (check) {
             /* termination test: only the live-slot row (and, for a progress callback, the finished-sample row) is summed inside the loop */
-            HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_ALIVE], 0, pollRows * sizeof(unsigned long long), stream));
-            hipLaunchKernelGGL(k_reduce_stats, dim3(pollRows, REDUCE_SPLIT), dim3(256), 0, stream, J.P, sd.counters.p, (int) ST_ALIVE);
-            HIP_TRY(hipMemcpyAsync(&hc.total[ST_ALIVE], &sd.counters.p->total[ST_ALIVE], pollRows * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-            if (J.p->progress) {
-                HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_SAMPLES], 0, sizeof(unsigned long long), stream));
-                hipLaunchKernelGGL(k_reduce_stats, dim3(1, REDUCE_SPLIT), dim3(256), 0, stream, J.P, sd.counters.p, (int) ST_SAMPLES);
-                HIP_TRY(hipMemcpyAsync(&hc.total[ST_SAMPLES], &sd.counters.p->total[ST_SAMPLES], sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-            }
+            readStatRows(J, ST_ALIVE, pollRows);
+            if (J.p->progress) readStatRows(J, ST_SAMPLES, 1);
             HIP_TRY(hipStreamSynchronize(stream));
             if (hc.total[ST_ALIVE] == 0 || hc.total[ST_GAVE_UP] != 0) done = true;
             if (hc.total[ST_ALIVE] < capacity) drainingSeen = true;
@@ -1603,9 +1622,7 @@ static bool wavefrontPass(RenderJob &J) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     if (wf.wideTrace && iter && !J.cancelled && hc.total[ST_GAVE_UP] == 0) {      /* (the last termination test may lie before the launch in which a wave gave up) */
-        HIP_TRY(hipMemsetAsync(&sd.counters.p->total[ST_GAVE_UP], 0, sizeof(unsigned long long), stream));
-        hipLaunchKernelGGL(k_reduce_stats, dim3(1, REDUCE_SPLIT), dim3(256), 0, stream, J.P, sd.counters.p, (int) ST_GAVE_UP);
-        HIP_TRY(hipMemcpyAsync(&hc.total[ST_GAVE_UP], &sd.counters.p->total[ST_GAVE_UP], sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        readStatRows(J, ST_GAVE_UP, 1);
         HIP_TRY(hipStreamSynchronize(stream));
     }
     if (hc.total[ST_GAVE_UP] != 0 && !J.cancelled) return false;      /* (its launches are not iterations of the job) */
@@ -1663,9 +1680,7 @@ static void passResults(RenderJob &J) {
         hipLaunchKernelGGL(k_export_samples, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream, J.D, rc, (const float4 *) sd.L.p,
                            (const int32_t *) sd.tileSlot.p, J.tilesX, sd.sampleOut.p, (uint32_t) J.p->spp, (uint32_t) J.p->sample_offset);
     }
-    HIP_TRY(hipMemsetAsync(sd.counters.p, 0, sizeof(Counters), stream));
-    hipLaunchKernelGGL(k_reduce_stats, dim3(ST_COUNT, REDUCE_SPLIT), dim3(256), 0, stream, J.P, sd.counters.p, 0);
-    HIP_TRY(hipMemcpyAsync(&hc, sd.counters.p, sizeof(Counters), hipMemcpyDeviceToHost, stream));
+    readStatRows(J, 0, ST_COUNT);
     HIP_TRY(hipStreamSynchronize(stream));
     HIP_TRY(hipGetLastError());
     phip_stats pass; memset(&pass, 0, sizeof(pass));
@@ -1710,7 +1725,7 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
             /* k_shade_trace_w gave the pass up: this pass again, and the rest of the job, on k_shade + the ray kernel -- the same pool, the same passes (k_mega's contract) */
             fprintf(stderr, "[phip] warning: the fused kernel gave up on this pass (a task stack outgrew LDS + spill buffer); samples %u.. of the job are rendered by the wavefront kernels\n",
                     (unsigned) J.rc.sppFirst);
-            J.wf.wideTrace = J.wf.shadeTrace = false;
+            selectVertexKernel(J, false, false);
             wavefrontPass(J);
         }
         if (J.cancelled) break;                                 /* L is incomplete: no film pass */

@@ -122,6 +122,19 @@ int phip_debug_host_rinv2(const uint32_t *primes, const uint16_t *perm, uint32_t
     return PHIP_OK;
 }
 
+/* The kernel the product's selection resolves for a key -- the functions planFused and selectVertexKernel call (phip.hip: shadeKernelOf, shadeTraceWideKernelOf,
+   megaKernelOf), not a copy of them -- by the name the dynamic symbol table has for its host pointer: the mangled name with the template arguments.  No HIP call, no GPU.
+   family 0: k_shade / k_shade_direct (form = k_shade's table set), 1: k_shade_trace, 2: k_shade_trace_w, 3: k_mega (form = its traversal form).  NULL: nothing
+   resolves for the key (a traversal form no build of k_mega holds), or the pointer has no dynamic symbol */
+const char *phip_debug_selected_kernel(int family, int feat, int material_mask, int strict_normals, int form, int qmc, int direct) {
+    const bool strict = strict_normals != 0;
+    const void *k = family == 3 ? (const void *) megaKernelOf(direct != 0, form, material_mask, strict, qmc != 0)
+                  : family == 2 ? (const void *) shadeTraceWideKernelOf(feat, strict, material_mask)
+                                : (const void *) shadeKernelOf(feat, direct != 0, family == 1, strict, material_mask, form);
+    Dl_info info;
+    return k && dladdr(k, &info) && info.dli_saddr == k ? info.dli_sname : nullptr;
+}
+
 /* Wald records + BVH statistics of a triangle soup, built exactly like phip_scene_create does (no GPU needed) */
 int phip_debug_host_build_bvh(const float *positions, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles,
                               phip_accel_info *info, float *scene_box6) {

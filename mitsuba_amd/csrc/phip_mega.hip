@@ -1,5 +1,6 @@
 /*
- * phip_mega.hip -- k_mega<materials, strictNormals, traversal form, QMC> (k_mega.h): the fused single-kernel path.  Compiled three times (phip_common.h; _ffi.UNITS):
+ * phip_mega.hip -- k_mega<materials, strictNormals, traversal form, QMC> (k_mega.h): the fused single-kernel path.  Compiled three times (phip_common.h; _ffi.UNITS),
+ * each part behind one look-up that returns its kernels (phipMegaKernel / phipMegaKernelWide / phipMegaKernelDirect); phip.hip asks for their residency and launches them:
  *   -DMEGA_PART=0  scenes that fit LDS: the packed leaf tables (FLAT 2 / 3)
  *   -DMEGA_PART=1  round 6: scenes whose tree stays in memory -- the compressed 8-wide tree walked from L2 (FLAT 4 / 5: k_wide_wave.h)
  *   -DMEGA_PART=2  round 6: the `direct` integrator in the same kernel (k_mega<.., DIRECT = true>), packed leaf tables and the tree in memory
@@ -15,8 +16,6 @@
 #ifndef MEGA_PART
 #define MEGA_PART 0
 #endif
-
-typedef void (*MegaKernel)(DevScene, MegaParams, RenderConst, float4 *);
 
 #if MEGA_PART == 0
 /* Leaf BSDF models: diffuse only, or all three (round 5) -- the Cornell box with a glass and a copper block.
@@ -64,19 +63,6 @@ template <bool QMC> static MegaKernel megaKernelOf(int materialMask, bool strict
 #undef MEGA_ENTRY
 #define MEGA_ENTRY(name) name##Direct
 #endif
-static MegaKernel megaKernel(int materialMask, bool strictNormals, int flat, bool qmc) {
+MegaKernel MEGA_ENTRY(phipMegaKernel)(int materialMask, bool strictNormals, int flat, bool qmc) {
     return qmc ? megaKernelOf<true>(materialMask, strictNormals, flat) : megaKernelOf<false>(materialMask, strictNormals, flat);
-}
-
-int MEGA_ENTRY(phipMegaBlocksPerCU)(int materialMask, bool strictNormals, int flat, bool qmc, size_t ldsBytes) {
-    int n = 0;
-    if (!megaKernel(materialMask, strictNormals, flat, qmc)) return 0;
-    if (ldsBytes > 48 * 1024 && hipFuncSetAttribute((const void *) megaKernel(materialMask, strictNormals, flat, qmc), hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *) megaKernel(materialMask, strictNormals, flat, qmc), BLOCK, ldsBytes) != hipSuccess) return 0;
-    return n;
-}
-
-void MEGA_ENTRY(phipLaunchMega)(int materialMask, bool strictNormals, int flat, bool qmc, dim3 grid, size_t ldsBytes, hipStream_t stream,
-                                const DevScene &S, const MegaParams &M, const RenderConst &rc, float4 *L) {
-    hipLaunchKernelGGL(megaKernel(materialMask, strictNormals, flat, qmc), grid, dim3(BLOCK), ldsBytes, stream, S, M, rc, L);
 }

@@ -2,9 +2,9 @@
  * phip_shade.hip -- the shading kernels of the wavefront path: k_shade<materials, strictNormals, features> (k_shade.h), k_shade_direct<materials, features>
  * (k_shade_direct.h) and k_shade_trace<materials, strictNormals, features> (k_shade_trace.h).  Compiled once per feature set (-DSHADE_FEAT=0..3: bit 0 =
  * environment emitter, bit 1 = bitmap textures; 8 and 11: bit 3 = the QMC samplers, without / with both other features) AND per part (-DSHADE_PART: 0 / 1 =
- * k_shade without / with strictNormals, 2 = k_shade_direct + the launchers phip.hip calls, 3 = k_shade_trace), 24 objects that build in parallel: the
+ * k_shade without / with strictNormals, 2 = k_shade_direct, 3 = k_shade_trace), 24 objects that build in parallel: the
  * texture code (MIP / EWA look-ups) is inlined into every kernel that can meet a textured leaf, and a unit with all of them took 3.5 minutes on its own.
- * phip.hip dispatches on the scene's feature set (phipLaunchShade / phipLaunchShadeDirect / phipLaunchShadeTrace).  See phip_common.h.
+ * Every part exports one look-up that returns its kernels (declared in phip_common.h); phip.hip selects the render's kernel through them and launches it.
  */
 #include "phip_common.h"
 #include "k_traverse.h"
@@ -17,13 +17,6 @@
 #endif
 #define SHADE_CAT2(a, b) a##b
 #define SHADE_CAT(a, b) SHADE_CAT2(a, b)
-
-typedef void (*ShadeKernel)(DevScene, PathPool, RenderConst, float4 *);
-/* the kernels of the other parts of this feature set: (leaf BSDF models present, which table set: 0 = generic pointers, 1 = emitter table and materials
-   addressed as LDS, 2 = the emitter table only -- FEAT 0 only) -> kernel */
-ShadeKernel SHADE_CAT(phipShadeKernelS0F, SHADE_FEAT)(int materialMask, int tables);
-ShadeKernel SHADE_CAT(phipShadeKernelS1F, SHADE_FEAT)(int materialMask, int tables);
-ShadeKernel SHADE_CAT(phipShadeTraceKernelF, SHADE_FEAT)(bool strictNormals, int materialMask);
 
 #if SHADE_PART == 0 || SHADE_PART == 1
 #define SHADE_STRICT (SHADE_PART == 1)
@@ -43,30 +36,14 @@ ShadeKernel SHADE_CAT(SHADE_CAT(SHADE_CAT(phipShadeKernelS, SHADE_PART), F), SHA
 }
 
 #elif SHADE_PART == 2
-void SHADE_CAT(phipLaunchShadeF, SHADE_FEAT)(bool strictNormals, int materialMask, dim3 grid, hipStream_t stream,
-                                             const DevScene &S, const PathPool &P, const RenderConst &rc, float4 *L) {
-    int tables = 0;
-#if SHADE_FEAT == 0
-    if (S.emitterTabSize <= EMITTER_LDS_FLOATS) tables = S.nMaterials <= MATERIAL_LDS_MAX ? 1 : 2;
-#endif
-    const ShadeKernel k = strictNormals ? SHADE_CAT(phipShadeKernelS1F, SHADE_FEAT)(materialMask, tables) : SHADE_CAT(phipShadeKernelS0F, SHADE_FEAT)(materialMask, tables);
-    hipLaunchKernelGGL(k, grid, dim3(BLOCK), 0, stream, S, P, rc, L);
-}
-
-void SHADE_CAT(phipLaunchShadeDirectF, SHADE_FEAT)(int materialMask, dim3 grid, hipStream_t stream,
-                                                   const DevScene &S, const PathPool &P, const RenderConst &rc, float4 *L) {
+ShadeKernel SHADE_CAT(phipShadeDirectKernelF, SHADE_FEAT)(int materialMask) {
     /* `direct`: leaf BSDF models = diffuse only / all, strictNormals at run time */
     static const ShadeKernel table[2] = { k_shade_direct<0, SHADE_FEAT>, k_shade_direct<MM_ALL, SHADE_FEAT> };
-    hipLaunchKernelGGL(table[(materialMask & MM_ALL) ? 1 : 0], grid, dim3(BLOCK), 0, stream, S, P, rc, L);
-}
-
-/* k_shade_trace (k_shade_trace.h): scenes on the packed leaf table (<= 64 Wald records) that k_mega does not serve; `path` only */
-void SHADE_CAT(phipLaunchShadeTraceF, SHADE_FEAT)(bool strictNormals, int materialMask, dim3 grid, size_t ldsBytes, hipStream_t stream,
-                                                  const DevScene &S, const PathPool &P, const RenderConst &rc, float4 *L) {
-    hipLaunchKernelGGL(SHADE_CAT(phipShadeTraceKernelF, SHADE_FEAT)(strictNormals, materialMask), grid, dim3(BLOCK), ldsBytes, stream, S, P, rc, L);
+    return table[(materialMask & MM_ALL) ? 1 : 0];
 }
 
 #elif SHADE_PART == 3
+/* k_shade_trace (k_shade_trace.h): scenes on the packed leaf table (<= 64 Wald records) that k_mega does not serve; `path` only */
 ShadeKernel SHADE_CAT(phipShadeTraceKernelF, SHADE_FEAT)(bool strictNormals, int materialMask) {
     /* leaf BSDF models = diffuse only / all (a scene with glass but no copper runs the kernel that also knows copper: two builds per feature set, not four);
        FEAT 0: phip.hip takes this path only when emitter table and materials fit LDS -- the kernel stages them itself, whatever FEAT says */
