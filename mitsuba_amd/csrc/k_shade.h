@@ -22,15 +22,32 @@ __device__ __forceinline__ float miWeight(float pdfA, float pdfB) {
 #ifndef SHADE_WAVES_LEAN
 #define SHADE_WAVES_LEAN 4          /* diffuse-only instantiation */
 #endif
+/* a kernel that traces the slot's next ray itself (k_shade_trace, k_shade_trace_w): in, the ray the vertex left; out, the camera ray of a slot that started a
+   sample, and whether the slot has a ray to trace */
+struct NextRay { float4 ro, rd; bool alive; };
+
+/* A camera sample is prepared (integrator.cpp:157-183): its pixel, and its ray through the pixel position the sample's stream jitters, which is returned; the
+   sequence samplers' jitter is kept for the film pass.  (k_mega's regeneration still spells these lines out: its code objects change with a call here, HISTORY.md.) */
+template <bool QMC>
+__device__ __forceinline__ V2 cameraSample(const DevScene &S, const RenderConst &rc, unsigned long long id, uint32_t px, uint32_t py, uint32_t k,
+                                           uint32_t &pixel, V3 &o, V3 &d, float &mint, float &maxt) {
+    pixel = py * (uint32_t) S.film.width + px;
+    const V2 jit = streamJitter<QMC>(rc, pixel, k, (uint32_t) S.film.width);
+    if (QMC && rc.jitter) rc.jitter[id] = make_float2(jit.x, jit.y);
+    const float sx = (float) px + jit.x, sy = (float) py + jit.y;
+    cameraRay(S.cam, sx, sy, o, d, mint, maxt);
+    return jit;
+}
+
 /* The common tail of the shading kernels: the block's shadow-queue entries are compacted, slots whose sample ended start
  * the next camera sample in the same lane, blocks without work retire, per-wave statistics are recorded. */
-template <bool QMC = false>
+template <bool QMC>
 __device__ __forceinline__ void shadeEpilogue(const DevScene &S, const PathPool &P, const RenderConst &rc, uint32_t *waveCnt,
                                               const uint32_t slot, const bool inRange, uint4 info, const bool alive, bool needNew,
                                               const bool pushShadow, const float4 sh0, const float4 sh1, const float4 sh2,
                                               const unsigned long long vertices, const unsigned long long done,
-                                              float4 *outRo = nullptr, float4 *outRd = nullptr, bool *outAlive = nullptr /* k_shade_trace: the camera ray a regenerated slot starts with, and whether the slot has a ray to trace */,
-                                              const uint32_t blk = blockIdx.x /* the block of BLOCK slots this thread block works on (k_shade_trace_w: a persistent grid walks them) */) {
+                                              const uint32_t blk /* the block of BLOCK slots this thread block works on: blockIdx.x, but for k_shade_trace_w, whose persistent grid walks them */,
+                                              NextRay *next = nullptr) {
     /* ---- shadow queue: compact this block's entries to the front of its own region (no global atomics) ---- */
     uint32_t shadowTotal = 0;
     {
@@ -112,19 +129,15 @@ __device__ __forceinline__ void shadeEpilogue(const DevScene &S, const PathPool 
         }
     }
     if (newId != ~0ull) {
-        uint32_t px, py, k;
+        uint32_t px, py, k, pixel;
         decodeId(rc, S.film, newId, px, py, k);
-        const uint32_t pixel = py * (uint32_t) S.film.width + px;
-        const V2 jit = streamJitter<QMC>(rc, pixel, k, (uint32_t) S.film.width);
-        if (QMC && rc.jitter) rc.jitter[newId] = make_float2(jit.x, jit.y);      /* for the film pass */
-        const float sx = (float) px + jit.x, sy = (float) py + jit.y;
         V3 o, d; float mint, maxt;
-        cameraRay(S.cam, sx, sy, o, d, mint, maxt);
+        cameraSample<QMC>(S, rc, newId, px, py, k, pixel, o, d, mint, maxt);
         float4 ro = make_float4(o.x, o.y, o.z, mint), rd = make_float4(d.x, d.y, d.z, maxt);
         if (S.preclip) preclipRay(S, ro, rd);
         P.rayO[slot] = ro;
         P.rayD[slot] = rd;
-        if (outRo) { *outRo = ro; *outRd = rd; }
+        if (next) { next->ro = ro; next->rd = rd; }
         P.thr[slot] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
         P.mis[slot] = make_float2(0.0f, 0.0f);
         info = make_uint4((uint32_t) newId, pixel, k, 1u | F_ALIVE | F_EMITTED | F_FIRST | (dynamicId ? F_DYNAMIC : 0u));
@@ -132,7 +145,7 @@ __device__ __forceinline__ void shadeEpilogue(const DevScene &S, const PathPool 
         P.state[slot] = info.w;
         nowAlive = true;
     }
-    if (outAlive) *outAlive = nowAlive;
+    if (next) next->alive = nowAlive;
     const uint32_t waveId = (blk * BLOCK + threadIdx.x) >> 6;      /* the wave's position in the grid (NOT slot >> 6: k_shade may have permuted the block's slots) */
     /* a slot still waiting for a dynamic sample id counts as live for the termination test */
     const bool live = nowAlive || (inRange && info.w == F_DYNAMIC);
@@ -611,5 +624,5 @@ template <int MM, bool STRICT, int FEAT> __global__ __launch_bounds__(BLOCK, MM 
         }
     }
 
-    shadeEpilogue<(FEAT & 8) != 0>(S, P, rc, waveCnt, slot, inRange, info, alive, needNew, pushShadow, sh.e0, sh.e1, sh.e2, vertices, done);
+    shadeEpilogue<(FEAT & 8) != 0>(S, P, rc, waveCnt, slot, inRange, info, alive, needNew, pushShadow, sh.e0, sh.e1, sh.e2, vertices, done, blockIdx.x);
 }

@@ -236,5 +236,5 @@ template <int MM, int FEAT> __global__ __launch_bounds__(BLOCK, SHADE_WAVES) voi
             P.rayO[slot] = ro; P.rayD[slot] = rdn; P.thr[slot] = v.thr;
         }
     }
-    shadeEpilogue<QMC>(S, P, rc, waveCnt, slot, inRange, info, alive, needNew, pushShadow, sh.e0, sh.e1, sh.e2, vertices, done);
+    shadeEpilogue<QMC>(S, P, rc, waveCnt, slot, inRange, info, alive, needNew, pushShadow, sh.e0, sh.e1, sh.e2, vertices, done, blockIdx.x);
 }

@@ -26,6 +26,31 @@ struct LPending {
     __device__ __forceinline__ uint64_t seqIdx(const RenderConst &rc, const PathVertex &v, uint32_t width) const { return seqIndex(rc, v.k, v.pixel % width, v.pixel / width); }
 };
 
+/* ---- shared by the kernels that trace the vertex's rays themselves (k_shade_trace here, k_shade_trace_w on the 8-wide tree) ---- */
+/* the shadow ray's verdict (path.cpp:187-199): an emitter sample that is not occluded joins the sample's radiance behind the vertex's own terms */
+__device__ __forceinline__ void joinShadow(const float4 *L, const ShadowEntry &sh, bool visible, float4 &pend, bool &have) {
+    if (visible) {
+        if (!have) pend = L[pm_to_bits(sh.e2.w)];
+        pend.x += sh.e2.x; pend.y += sh.e2.y; pend.z += sh.e2.z;
+        have = true;
+    }
+}
+/* the hit record the next launch loads: the shade class of the record hit rides in the prim word (k_pool.h), for that launch's lane deal */
+__device__ __forceinline__ float4 packHitWord(const TravResult &r) {
+    return make_float4(r.t, r.u, r.v, pm_from_bits(r.prim == PHIP_NO_HIT ? r.prim : (r.prim | (r.cls << HIT_CLASS_SHIFT))));
+}
+
+/* the rows the ray kernels fill on the wavefront: rays, node visits and triangle tests of the closest-hit and of the shadow rays */
+__device__ __forceinline__ void tracedStats(const PathPool &P, uint32_t waveId, unsigned long long closestRays, unsigned long long shadowRays,
+                                            unsigned long long node, unsigned long long tri, unsigned long long shNode, unsigned long long shTri) {
+    waveStat(P, ST_CLOSEST_RAYS, waveId, closestRays);
+    waveStat(P, ST_NODE, waveId, node);
+    waveStat(P, ST_TRI, waveId, tri);
+    waveStat(P, ST_SHADOW_RAYS, waveId, shadowRays);
+    waveStat(P, ST_SH_NODE, waveId, shNode);
+    waveStat(P, ST_SH_TRI, waveId, shTri);
+}
+
 template <int MM, bool STRICT, int FEAT> __global__ __launch_bounds__(BLOCK, SHADE_TRACE_WAVES) void k_shade_trace(DevScene S, PathPool P, RenderConst rc, float4 *L) {
     __shared__ uint32_t waveCnt[BLOCK / 64];
     /* one buffer, two uses: the class deal's slot exchange at the head of the block (scenes with more than one BSDF model), then -- behind a barrier -- the
@@ -88,31 +113,20 @@ template <int MM, bool STRICT, int FEAT> __global__ __launch_bounds__(BLOCK, SHA
         float mint, maxt; V3 rcp; TravResult r;
         const bool go = pushShadow & clipToSceneSel<true>(S, o, d, PT_EPSILON, sh.e0.w, mint, maxt, rcp);
         const bool occluded = traverseFlat2W<true, true>(flat, S.nFlatLeaves, tris, wb, lane, go, o, d, rcp, mint, maxt, r, shNode, shTri);
-        if (pushShadow && !occluded) {
-            if (!havePend) pend = L[pm_to_bits(sh.e2.w)];
-            pend.x += sh.e2.x; pend.y += sh.e2.y; pend.z += sh.e2.z;
-            havePend = true;
-        }
+        joinShadow(L, sh, pushShadow && !occluded, pend, havePend);
     }
     if (havePend) L[v.id] = pend;
 
     /* ---- regeneration (shadeEpilogue: static schedule + dynamic tail), then the next ray of every live slot ---- */
-    float4 ro = v.rayO, rd = v.rayD;
-    bool nowAlive = false;
-    shadeEpilogue<(FEAT & 8) != 0>(S, P, rc, waveCnt, slot, inRange, info, alive, needNew, false, sh.e0, sh.e1, sh.e2, vertices, done, &ro, &rd, &nowAlive);
+    NextRay next{ v.rayO, v.rayD, false };
+    shadeEpilogue<(FEAT & 8) != 0>(S, P, rc, waveCnt, slot, inRange, info, alive, needNew, false, sh.e0, sh.e1, sh.e2, vertices, done, blockIdx.x, &next);
     uint32_t nNode = 0, nTri = 0;
     {
-        const V3 o(ro.x, ro.y, ro.z), d(rd.x, rd.y, rd.z);
+        const V3 o(next.ro.x, next.ro.y, next.ro.z), d(next.rd.x, next.rd.y, next.rd.z);
         float mint, maxt; V3 rcp; TravResult r;
-        const bool go = nowAlive & clipToSceneSel<false>(S, o, d, ro.w, rd.w, mint, maxt, rcp);
+        const bool go = next.alive & clipToSceneSel<false>(S, o, d, next.ro.w, next.rd.w, mint, maxt, rcp);
         traverseFlat2W<false, true>(flat, S.nFlatLeaves, tris, wb, lane, go, o, d, rcp, mint, maxt, r, nNode, nTri);
-        if (nowAlive) P.hit[slot] = make_float4(r.t, r.u, r.v, pm_from_bits(r.prim == PHIP_NO_HIT ? r.prim : (r.prim | (r.cls << HIT_CLASS_SHIFT))));
+        if (next.alive) P.hit[slot] = packHitWord(r);
     }
-    const uint32_t waveId = (blockIdx.x * BLOCK + threadIdx.x) >> 6;
-    waveStat(P, ST_CLOSEST_RAYS, waveId, nowAlive ? 1ull : 0ull);
-    waveStat(P, ST_NODE, waveId, nNode);
-    waveStat(P, ST_TRI, waveId, nTri);
-    waveStat(P, ST_SHADOW_RAYS, waveId, pushShadow ? 1ull : 0ull);
-    waveStat(P, ST_SH_NODE, waveId, shNode);
-    waveStat(P, ST_SH_TRI, waveId, shTri);
+    tracedStats(P, (blockIdx.x * BLOCK + threadIdx.x) >> 6, next.alive ? 1ull : 0ull, pushShadow ? 1ull : 0ull, nNode, nTri, shNode, shTri);
 }

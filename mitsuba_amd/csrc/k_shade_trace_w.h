@@ -95,41 +95,31 @@ template <int MM, bool STRICT, int FEAT> __global__ __launch_bounds__(BLOCK, SHA
         }
 
         /* ---- regeneration (shadeEpilogue: static schedule + dynamic tail; its barriers separate the deal's exchange from the traversal's buffers) ---- */
-        float4 ro = v.rayO, rd = v.rayD;
-        bool nowAlive = false;
-        shadeEpilogue<(FEAT & 8) != 0>(S, P, rc, waveCnt, slot, inRange, info, alive, needNew, false, sh.e0, sh.e1, sh.e2, vertices, done, &ro, &rd, &nowAlive, blk);
+        NextRay next{ v.rayO, v.rayD, false };
+        shadeEpilogue<(FEAT & 8) != 0>(S, P, rc, waveCnt, slot, inRange, info, alive, needNew, false, sh.e0, sh.e1, sh.e2, vertices, done, blk, &next);
 
         /* ---- the vertex's shadow ray (path.cpp:187-199) and the next ray of every live slot: one traversal of the wave ---- */
         {
             const V3 so(sh.e0.x, sh.e0.y, sh.e0.z), sd(sh.e1.x, sh.e1.y, sh.e1.z);
             float smint, smaxt; V3 srcp;
             const bool goS = pushShadow & clipToSceneSel<true>(S, so, sd, PT_EPSILON, sh.e0.w, smint, smaxt, srcp);
-            const V3 o(ro.x, ro.y, ro.z), d(rd.x, rd.y, rd.z);
+            const V3 o(next.ro.x, next.ro.y, next.ro.z), d(next.rd.x, next.rd.y, next.rd.z);
             float mint, maxt; V3 rcp;
-            const bool goC = nowAlive & clipToSceneSel<false>(S, o, d, ro.w, rd.w, mint, maxt, rcp);
+            const bool goC = next.alive & clipToSceneSel<false>(S, o, d, next.ro.w, next.rd.w, mint, maxt, rcp);
             bool occluded = false; TravResult r;
             traceWidePool<true, true>(S, wp, lane, goS, so, sd, smint, smaxt, goC, o, d, mint, maxt, occluded, r, wc, wc + 1, overflow);
-            if (pushShadow && !occluded) {
-                if (!havePend) pend = L[pm_to_bits(sh.e2.w)];
-                pend.x += sh.e2.x; pend.y += sh.e2.y; pend.z += sh.e2.z;
-                havePend = true;
-            }
+            joinShadow(L, sh, pushShadow && !occluded, pend, havePend);
             if (havePend) L[oldId] = pend;
-            if (nowAlive) P.hit[slot] = make_float4(r.t, r.u, r.v, pm_from_bits(r.prim == PHIP_NO_HIT ? r.prim : (r.prim | (r.cls << HIT_CLASS_SHIFT))));
+            if (next.alive) P.hit[slot] = packHitWord(r);
         }
-        nClosest += nowAlive ? 1ull : 0ull;
+        nClosest += next.alive ? 1ull : 0ull;
         nShadow += pushShadow ? 1ull : 0ull;
     }
 
     /* the work counters of this wave's blocks of slots, in the rows of the wave's place in the GRID (fewer waves than the pool has: the rows are sums) */
     const uint32_t waveId = blockIdx.x * (BLOCK / 64) + wave;
     const unsigned long long stS = lane == 0u ? wc[0] : 0ull, stC = lane == 0u ? wc[1] : 0ull;
-    waveStat(P, ST_CLOSEST_RAYS, waveId, nClosest);
-    waveStat(P, ST_NODE, waveId, stC & 0xFFFFFFFFull);
-    waveStat(P, ST_TRI, waveId, stC >> 32);
-    waveStat(P, ST_SHADOW_RAYS, waveId, nShadow);
-    waveStat(P, ST_SH_NODE, waveId, stS & 0xFFFFFFFFull);
-    waveStat(P, ST_SH_TRI, waveId, stS >> 32);
+    tracedStats(P, waveId, nClosest, nShadow, stC & 0xFFFFFFFFull, stC >> 32, stS & 0xFFFFFFFFull, stS >> 32);
     /* a wave whose task stack overflowed says so in a row of its own (one owner per entry, zeroed by the host before the pass): the host discards the pass */
     if (__any(overflow) && lane == 0u) P.stat[(size_t) ST_GAVE_UP * P.nWaves + waveId] = 1ull;
 }
