@@ -3,13 +3,14 @@
  * shading functions (dv_scene.h), the path-pool layout (k_pool.h), the error macro.
  *
  * libphip.so is built from four sources (34 objects) so that they compile in parallel:
- *   phip.hip          host side (scene build, kernel selection, render loop, multi-device orchestration, C ABI) + traversal and film kernels: 1 object
+ *   phip.hip          the C ABI + traversal and film kernels, with the host side it includes by concern: host_scene.h (scene build, replicas), host_render.h (kernel
+ *                     selection, one device's render loop), host_multi.h (multi-device orchestration, RCCL): 1 object
  *   phip_shade.hip    k_shade / k_shade_direct / k_shade_trace instantiations behind the look-ups phipShade*KernelF<n> -- compiled per feature set (-DSHADE_FEAT=0..3, 8
  *                     and 11: environment emitter, bitmap textures, the QMC samplers) and per part (-DSHADE_PART=0..3), 24 objects: see its header
  *   phip_shade_w.hip  k_shade_trace_w instantiations behind phipShadeTraceWideKernelF<n>, per feature set: 6 objects
  *   phip_mega.hip     k_mega instantiations behind phipMegaKernel (-DMEGA_PART=0: scenes in LDS) / phipMegaKernelWide (-DMEGA_PART=1: the 8-wide tree in memory) /
  *                     phipMegaKernelDirect (-DMEGA_PART=2: `direct`): 3 objects
- * The other units hold kernels and the look-ups that return them, nothing else: every launch and every query of the runtime is in phip.hip.
+ * The other units hold kernels and the look-ups that return them, nothing else: every launch and every query of the runtime is in phip.hip and its host headers.
  * No device function is called across units (everything on the device side is inline in headers), so no -fgpu-rdc.
  */
 #pragma once

@@ -151,6 +151,7 @@ class PinnedFilm(HDRFilm):
 
 class PathHIP:
     """`path_hip` integrator: MIPathTracer semantics, MI355X execution."""
+    INTEGRATOR = A.PHIP_INTEGRATOR_PATH
 
     def __init__(self, props=None, **kw):
         props = Properties("path_hip", **(dict(props or {}) | kw))
@@ -168,53 +169,43 @@ class PathHIP:
 
     def params(self, scene, spp, seed=0, shard_index=0, shard_count=1, flags=0, stream=None, **extra):
         """extra: devices=[...] (multi-GPU inside the call), sample_offset / sample_total (progressive passes), progress=callable"""
-        return A.default_render_params(spp=spp, max_depth=self.m_maxDepth, rr_depth=self.m_rrDepth,
-                                       strict_normals=int(self.m_strictNormals), hide_emitters=int(self.m_hideEmitters),
-                                       block_size=scene.block_size, seed=seed, shard_index=shard_index,
-                                       shard_count=shard_count, device=scene.device, flags=flags, stream=stream, **extra)
+        p = A.default_render_params(spp=spp, max_depth=self.m_maxDepth, rr_depth=self.m_rrDepth,
+                                    strict_normals=int(self.m_strictNormals), hide_emitters=int(self.m_hideEmitters),
+                                    block_size=scene.block_size, seed=seed, shard_index=shard_index,
+                                    shard_count=shard_count, device=scene.device, flags=flags, stream=stream, **extra)
+        p.integrator = self.INTEGRATOR
+        return p
+
+    def _call(self, entry, scene, p, out):
+        """One render entry point: keeps the call's statistics; False if cancelled, PhipError (Log(EError, ...) throws in the reference) on any other failure."""
+        self._scene = scene
+        st = A.phip_stats()
+        rc = getattr(_ffi.lib(), entry)(scene._h, C.byref(p), out, C.byref(st))
+        self.stats = st
+        if rc == A.PHIP_ERR_CANCELLED:
+            return False
+        if rc != 0:
+            raise _ffi.PhipError(rc, entry)
+        return True
 
     def render(self, scene, film, spp, seed=0, shard_index=0, shard_count=1, flags=0, **extra):
         """Renders into `film` (film.put of one full-frame block).  Returns True on success,
         False if cancelled (SamplingIntegrator::render returns proc->getReturnStatus() == ESuccess)."""
-        self._scene = scene
-        p = self.params(scene, spp, seed, shard_index, shard_count, flags, **extra)
         block = np.zeros((scene.height, scene.width, 5), np.float32)
-        st = A.phip_stats()
-        rc = _ffi.lib().phip_render(scene._h, C.byref(p), _ffi.fptr(block), C.byref(st))
-        self.stats = st
-        if rc == A.PHIP_ERR_CANCELLED:
-            return False
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_render")     # Log(EError, ...) throws in the reference
-        film.put(block)
-        return True
+        ok = self._call("phip_render", scene, self.params(scene, spp, seed, shard_index, shard_count, flags, **extra), _ffi.fptr(block))
+        if ok:
+            film.put(block)
+        return ok
 
     def render_into(self, scene, host_ptr, spp, seed=0, shard_index=0, shard_count=1, flags=0, **extra):
         """phip_render into the caller's host memory (height x width x 5 float32 at address `host_ptr`): what the Mitsuba shim does with
         the film's bitmap.  Pinned memory (PinnedFilm below, torch pin_memory) gets the film in one asynchronous copy."""
-        self._scene = scene
-        p = self.params(scene, spp, seed, shard_index, shard_count, flags, **extra)
-        st = A.phip_stats()
-        rc = _ffi.lib().phip_render(scene._h, C.byref(p), C.cast(C.c_void_p(host_ptr), C.POINTER(C.c_float)), C.byref(st))
-        self.stats = st
-        if rc == A.PHIP_ERR_CANCELLED:
-            return False
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_render")
-        return True
+        return self._call("phip_render", scene, self.params(scene, spp, seed, shard_index, shard_count, flags, **extra),
+                          C.cast(C.c_void_p(host_ptr), C.POINTER(C.c_float)))
 
     def render_device(self, scene, d_out_ptr, spp, seed=0, shard_index=0, shard_count=1, flags=0, stream=None, **extra):
         """Renders this shard's blocks into device memory (e.g. a torch tensor) for an RCCL reduce."""
-        self._scene = scene
-        p = self.params(scene, spp, seed, shard_index, shard_count, flags, stream, **extra)
-        st = A.phip_stats()
-        rc = _ffi.lib().phip_render_device(scene._h, C.byref(p), C.c_void_p(d_out_ptr), C.byref(st))
-        self.stats = st
-        if rc == A.PHIP_ERR_CANCELLED:
-            return False
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_render_device")
-        return True
+        return self._call("phip_render_device", scene, self.params(scene, spp, seed, shard_index, shard_count, flags, stream, **extra), C.c_void_p(d_out_ptr))
 
     def samples(self, scene, spp):
         """Per-sample (R,G,B,alpha) of the last render made with PHIP_FLAG_SAMPLE_BUFFER: [y][x][sample]."""
@@ -231,6 +222,7 @@ class PathHIP:
 
 class DirectHIP(PathHIP):
     """`direct_hip` integrator: MIDirectIntegrator semantics (direct.cpp:149-312) on the same kernels."""
+    INTEGRATOR = A.PHIP_INTEGRATOR_DIRECT
 
     def __init__(self, props=None, **kw):
         props = Properties("direct_hip", **(dict(props or {}) | kw))
@@ -248,7 +240,6 @@ class DirectHIP(PathHIP):
 
     def params(self, scene, spp, seed=0, shard_index=0, shard_count=1, flags=0, stream=None, **extra):
         p = super().params(scene, spp, seed, shard_index, shard_count, flags, stream, **extra)
-        p.integrator = A.PHIP_INTEGRATOR_DIRECT
         p.emitter_samples = self.m_emitterSamples
         p.bsdf_samples = self.m_bsdfSamples
         return p
@@ -258,8 +249,4 @@ class VolPathSimpleHIP(PathHIP):
     """`volpath_simple_hip` integrator: SimpleVolumetricPathTracer (src/integrators/path/volpath_simple.cpp:88-318) on a scene without participating media --
     the `path` loop without multiple importance sampling, same parameters (MonteCarloIntegrator: maxDepth, rrDepth, strictNormals, hideEmitters).  The scene
     description has no media; the Mitsuba plugin shim (mitsuba_amd/plugin/volpath_simple_hip.cpp) refuses a scene that has any."""
-
-    def params(self, scene, spp, seed=0, shard_index=0, shard_count=1, flags=0, stream=None, **extra):
-        p = super().params(scene, spp, seed, shard_index, shard_count, flags, stream, **extra)
-        p.integrator = A.PHIP_INTEGRATOR_VOLPATH_SIMPLE
-        return p
+    INTEGRATOR = A.PHIP_INTEGRATOR_VOLPATH_SIMPLE

@@ -18,8 +18,7 @@ public:
         m_strictNormals = props.getBoolean("strictNormals", false);
         m_hideEmitters = props.getBoolean("hideEmitters", false);
         Assert(m_emitterSamples + m_bsdfSamples > 0);
-        m_holder.setDevice(props.getInteger("device", 0));
-        m_holder.setDeviceCount(props.getInteger("devices", 1));       /* GPUs of the node to spread the job over (0 = all) */
+        m_holder.configure(props);
         Properties p("direct");
         p.setSize("emitterSamples", m_emitterSamples); p.setSize("bsdfSamples", m_bsdfSamples);
         p.setBoolean("strictNormals", m_strictNormals); p.setBoolean("hideEmitters", m_hideEmitters);
@@ -29,8 +28,7 @@ public:
     DirectHIP(Stream *stream, InstanceManager *manager) : SamplingIntegrator(stream, manager) {
         m_emitterSamples = stream->readSize(); m_bsdfSamples = stream->readSize();
         m_strictNormals = stream->readBool(); m_hideEmitters = stream->readBool();
-        m_holder.setDevice(stream->readInt());
-        m_holder.setDeviceCount(stream->readInt());
+        m_holder.unserialize(stream);
         m_cpuDirect = static_cast<SamplingIntegrator *>(manager->getInstance(stream));
     }
 
@@ -38,8 +36,7 @@ public:
         SamplingIntegrator::serialize(stream, manager);
         stream->writeSize(m_emitterSamples); stream->writeSize(m_bsdfSamples);
         stream->writeBool(m_strictNormals); stream->writeBool(m_hideEmitters);
-        stream->writeInt(m_holder.getDevice());
-        stream->writeInt(m_holder.getDeviceCount());
+        m_holder.serialize(stream);
         manager->serialize(stream, m_cpuDirect.get());
     }
 
@@ -50,8 +47,8 @@ public:
     }
 
     Spectrum Li(const RayDifferential &ray, RadianceQueryRecord &rRec) const {
-        static bool told = false;      /* (only a wrapping integrator -- `adaptive`, `irrcache` -- gets here) */
-        if (!told) { told = true; SLog(EWarn, "direct_hip: Li() was called by a wrapping integrator -- these samples run on the CPU (nested `direct`), not on the GPU"); }
+        static bool told = false;
+        PhipSceneHolder::warnLi(told, "direct_hip", "direct");
         return m_cpuDirect->Li(ray, rRec);
     }
 
@@ -71,7 +68,7 @@ public:
         return m_holder.render(scene, queue, job, rp, "direct_hip");
     }
 
-    void cancel() { if (m_holder.get()) phip_cancel(m_holder.get()); }
+    void cancel() { m_holder.cancel(); }
 
     MTS_DECLARE_CLASS()
 private:

@@ -9,7 +9,7 @@
  * (oracle/Makefile.ref, target `shims`; tests/test_gpu_dropin.py); the standalone harness (mitsuba_amd/*.py, tests/)
  * drives the same C ABI through ctypes.  See INTEGRATION.md.
  *
- * What it does, and nothing else:
+ * What it does, and nothing else (PhipMonteCarloShim in phip_flatten.h, shared with volpath_simple_hip.cpp; this file states what is path_hip's own):
  *   - derives from MonteCarloIntegrator so that maxDepth / rrDepth / strictNormals / hideEmitters
  *     parse, validate and serialise exactly like `path` (src/librender/integrator.cpp:190-225);
  *   - preprocess(): flattens Scene::getShapes() into a phip_scene_desc (every Shape through
@@ -24,58 +24,17 @@
 
 MTS_NAMESPACE_BEGIN
 
-class PathHIP : public MonteCarloIntegrator {
+class PathHIP : public PhipMonteCarloShim<PathHIP> {
 public:
-    PathHIP(const Properties &props) : MonteCarloIntegrator(props) {
-        m_holder.setDevice(props.getInteger("device", 0));
-        m_holder.setDeviceCount(props.getInteger("devices", 1));       /* GPUs of the node to spread the job over (0 = all) */
-        Properties p("path");
-        p.setInteger("maxDepth", m_maxDepth); p.setInteger("rrDepth", m_rrDepth);
-        p.setBoolean("strictNormals", m_strictNormals); p.setBoolean("hideEmitters", m_hideEmitters);
-        m_cpuPath = static_cast<SamplingIntegrator *>(PluginManager::getInstance()->createObject(MTS_CLASS(Integrator), p));
-    }
+    static const char *name() { return "path_hip"; }
+    static const char *nested() { return "path"; }
+    static uint32_t integrator() { return PHIP_INTEGRATOR_PATH; }
+    void checkScene(const Scene *) { }
 
-    PathHIP(Stream *stream, InstanceManager *manager) : MonteCarloIntegrator(stream, manager) {
-        m_holder.setDevice(stream->readInt());
-        m_holder.setDeviceCount(stream->readInt());
-        m_cpuPath = static_cast<SamplingIntegrator *>(manager->getInstance(stream));
-    }
-
-    void serialize(Stream *stream, InstanceManager *manager) const {
-        MonteCarloIntegrator::serialize(stream, manager);
-        stream->writeInt(m_holder.getDevice());
-        stream->writeInt(m_holder.getDeviceCount());
-        manager->serialize(stream, m_cpuPath.get());
-    }
-
-    Spectrum Li(const RayDifferential &ray, RadianceQueryRecord &rRec) const {
-        /* reached only through an integrator that wraps this one (`adaptive`, `irrcache`): those call Li() per sample on the host */
-        static bool told = false;
-        if (!told) { told = true; SLog(EWarn, "path_hip: Li() was called by a wrapping integrator -- these samples run on the CPU (nested `path`), not on the GPU"); }
-        return m_cpuPath->Li(ray, rRec);
-    }
-
-    bool preprocess(const Scene *scene, RenderQueue *queue, const RenderJob *job, int sceneResID, int sensorResID, int samplerResID) {
-        if (!MonteCarloIntegrator::preprocess(scene, queue, job, sceneResID, sensorResID, samplerResID))
-            return false;
-        m_holder.flatten(scene);
-        return true;
-    }
-
-    bool render(Scene *scene, RenderQueue *queue, const RenderJob *job, int sceneResID, int sensorResID, int samplerResID) {
-        phip_render_params rp; memset(&rp, 0, sizeof(rp));
-        rp.integrator = PHIP_INTEGRATOR_PATH;
-        rp.max_depth = m_maxDepth; rp.rr_depth = m_rrDepth;
-        rp.strict_normals = m_strictNormals; rp.hide_emitters = m_hideEmitters;
-        return m_holder.render(scene, queue, job, rp, "path_hip");
-    }
-
-    void cancel() { if (m_holder.get()) phip_cancel(m_holder.get()); }
+    PathHIP(const Properties &props) : PhipMonteCarloShim<PathHIP>(props) { }
+    PathHIP(Stream *stream, InstanceManager *manager) : PhipMonteCarloShim<PathHIP>(stream, manager) { }
 
     MTS_DECLARE_CLASS()
-private:
-    PhipSceneHolder m_holder;
-    ref<SamplingIntegrator> m_cpuPath;
 };
 
 MTS_IMPLEMENT_CLASS_S(PathHIP, false, MonteCarloIntegrator)

@@ -1,5 +1,6 @@
 /*
- * phip_flatten.h -- shared by the `path_hip` and `direct_hip` plugin shims: Scene -> phip_scene_desc -> phip_scene.
+ * phip_flatten.h -- shared by the `path_hip`, `volpath_simple_hip` and `direct_hip` plugin shims: Scene -> phip_scene_desc -> phip_scene
+ * (PhipSceneHolder), and the shim the two MonteCarloIntegrator plugins are leaves of (PhipMonteCarloShim, at the end).
  * (See path_hip.cpp for the build recipe; INTEGRATION.md lists the accessors the stand-in classes below assume.)
  */
 #pragma once
@@ -221,13 +222,24 @@ public:
     PhipSceneHolder() : m_qmcScramble(0), m_scene(NULL), m_device(0), m_deviceCount(1) { }
     ~PhipSceneHolder() { if (m_scene) phip_scene_destroy(m_scene); }
     phip_scene *get() const { return m_scene; }
-    void setDevice(int device) { m_device = device; }
-    int getDevice() const { return m_device; }
 
     /* Devices of the job: `devices` = how many GPUs the render spreads over (default 1; 0 = every visible GPU), starting at
-       `device`.  With more than one, libphip runs one host thread + stream per GPU and merges the films with ncclReduce. */
-    void setDeviceCount(int n) { m_deviceCount = n; }
-    int getDeviceCount() const { return m_deviceCount; }
+       `device`.  With more than one, libphip runs one host thread + stream per GPU and merges the films with ncclReduce.
+       Every plugin reads the two properties and carries them on the stream in this order. */
+    void configure(const Properties &props) { m_device = props.getInteger("device", 0); m_deviceCount = props.getInteger("devices", 1); }
+    void unserialize(Stream *stream) { m_device = stream->readInt(); m_deviceCount = stream->readInt(); }
+    void serialize(Stream *stream) const { stream->writeInt(m_device); stream->writeInt(m_deviceCount); }
+
+    /* integrator.cpp:90-93 */
+    void cancel() { if (m_scene) phip_cancel(m_scene); }
+
+    /* Li() of a plugin is reached only through an integrator that wraps it (`adaptive`, `irrcache`): those call Li() per sample on the host,
+       where the plugin's nested CPU integrator answers.  Said once per plugin: `told` is the calling plugin's own flag. */
+    static void warnLi(bool &told, const char *plugin, const char *nested) {
+        if (told) return;
+        told = true;
+        SLog(EWarn, "%s: Li() was called by a wrapping integrator -- these samples run on the CPU (nested `%s`), not on the GPU", plugin, nested);
+    }
 
     /* The scene's <sampler> (src/librender/integrator.cpp:104,169 clone it per worker): `independent` is honoured as "independent
        uniform samples" -- its SFMT stream is one sequential generator per worker thread (independent.cpp:71-103), which no
@@ -705,6 +717,64 @@ private:
     std::vector<phip_texture> m_textures; std::map<const Texture *, uint32_t> m_textureIds;
     std::vector<ref<Bitmap> > m_textureLevels;   /* float RGB copies of the textures' MIP levels */
     std::vector<ref<Bitmap> > m_envLevels;       /* float RGB copies of the environment map's MIP levels (alive until phip_scene_create) */
+};
+
+/* The shim of a MonteCarloIntegrator of the reference (path_hip.cpp, volpath_simple_hip.cpp): maxDepth / rrDepth / strictNormals / hideEmitters
+   parse, validate and serialise exactly like `path` (src/librender/integrator.cpp:190-225).  It has no Mitsuba Class of its own -- the plugins are
+   loaded into one process, and a class registered from a header would be registered once per plugin library -- so only a leaf carries
+   MTS_DECLARE_CLASS / MTS_IMPLEMENT_CLASS_S(Leaf, false, MonteCarloIntegrator) / MTS_EXPORT_PLUGIN.  A Leaf states what differs:
+       static const char *name()        its own plugin name
+       static const char *nested()      the CPU integrator that answers Li()
+       static uint32_t integrator()     PHIP_INTEGRATOR_* of include/phip.h
+       void checkScene(const Scene *)   what preprocess() refuses before the scene is flattened */
+template <typename Leaf> class PhipMonteCarloShim : public MonteCarloIntegrator {
+public:
+    PhipMonteCarloShim(const Properties &props) : MonteCarloIntegrator(props) {
+        m_holder.configure(props);
+        Properties p(Leaf::nested());
+        p.setInteger("maxDepth", m_maxDepth); p.setInteger("rrDepth", m_rrDepth);
+        p.setBoolean("strictNormals", m_strictNormals); p.setBoolean("hideEmitters", m_hideEmitters);
+        m_cpuPath = static_cast<SamplingIntegrator *>(PluginManager::getInstance()->createObject(MTS_CLASS(Integrator), p));
+    }
+
+    PhipMonteCarloShim(Stream *stream, InstanceManager *manager) : MonteCarloIntegrator(stream, manager) {
+        m_holder.unserialize(stream);
+        m_cpuPath = static_cast<SamplingIntegrator *>(manager->getInstance(stream));
+    }
+
+    void serialize(Stream *stream, InstanceManager *manager) const {
+        MonteCarloIntegrator::serialize(stream, manager);
+        m_holder.serialize(stream);
+        manager->serialize(stream, m_cpuPath.get());
+    }
+
+    Spectrum Li(const RayDifferential &ray, RadianceQueryRecord &rRec) const {
+        static bool told = false;
+        PhipSceneHolder::warnLi(told, Leaf::name(), Leaf::nested());
+        return m_cpuPath->Li(ray, rRec);
+    }
+
+    bool preprocess(const Scene *scene, RenderQueue *queue, const RenderJob *job, int sceneResID, int sensorResID, int samplerResID) {
+        if (!MonteCarloIntegrator::preprocess(scene, queue, job, sceneResID, sensorResID, samplerResID))
+            return false;
+        static_cast<Leaf *>(this)->checkScene(scene);
+        m_holder.flatten(scene);
+        return true;
+    }
+
+    bool render(Scene *scene, RenderQueue *queue, const RenderJob *job, int sceneResID, int sensorResID, int samplerResID) {
+        phip_render_params rp; memset(&rp, 0, sizeof(rp));
+        rp.integrator = Leaf::integrator();
+        rp.max_depth = m_maxDepth; rp.rr_depth = m_rrDepth;
+        rp.strict_normals = m_strictNormals; rp.hide_emitters = m_hideEmitters;
+        return m_holder.render(scene, queue, job, rp, Leaf::name());
+    }
+
+    void cancel() { m_holder.cancel(); }
+
+private:
+    PhipSceneHolder m_holder;
+    ref<SamplingIntegrator> m_cpuPath;
 };
 
 MTS_NAMESPACE_END

@@ -46,7 +46,7 @@ def test_single_process_helpers_are_noops():
 
 
 def test_librccl_exports_what_the_in_library_merge_binds():
-    """renderMultiDevice (mitsuba_amd/csrc/phip.hip: Rccl::bind) resolves six entry points of librccl with dlopen / dlsym at the first
+    """renderMultiDevice (mitsuba_amd/csrc/host_multi.h: Rccl::bind) resolves six entry points of librccl with dlopen / dlsym at the first
     multi-GPU render: a missing symbol must be found here, not on the first 8-GPU lease."""
     import ctypes
     lib = None
@@ -58,7 +58,7 @@ def test_librccl_exports_what_the_in_library_merge_binds():
             continue
     if lib is None:
         pytest.skip("no librccl on this machine")
-    src = open(os.path.join(ROOT, "mitsuba_amd", "csrc", "phip.hip")).read()
+    src = open(os.path.join(ROOT, "mitsuba_amd", "csrc", "host_multi.h")).read()
     bind = src[src.index("void bind()"):src.index("void check(ncclResult_t")]
     import re
     names = re.findall(r'sym\("(\w+)"\)', bind)

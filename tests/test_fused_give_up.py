@@ -50,7 +50,7 @@ def test_k_mega_no_longer_poisons_the_sample_row():
     assert re.search(r"if \(gaveUp && lane == 0u\) P\.stat\[\(size_t\) ST_GAVE_UP \* P\.nWaves \+ waveId\] = 1ull;", k)
     pool = code("k_pool.h")
     assert re.search(r"ST_SAMPLES, ST_ALIVE, ST_GAVE_UP, ST_COUNT", pool)
-    host = code("phip.hip")
+    host = code("host_render.h")
     assert "hc.total[ST_SAMPLES] > rc.totalIds" not in host
     assert re.search(r"gaveUp \|\| \(countKnown && hc\.total\[ST_SAMPLES\] != samplesTotal \* rc\.sppPass\)", host)
     assert re.search(r"#else\s*const bool countKnown = true;", host)

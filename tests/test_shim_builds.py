@@ -17,7 +17,7 @@ MODES = {"stock": [], "accessors": ["-DPHIP_REFERENCE_ACCESSORS"], "sources": ["
 
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "include", "mitsuba")), reason="the reference tree is not present")
 def test_plugin_shims_compile_against_the_reference_in_every_mode():
-    jobs = [(m, f) for m in MODES for f in ("path_hip.cpp", "direct_hip.cpp")]
+    jobs = [(m, f) for m in MODES for f in ("path_hip.cpp", "direct_hip.cpp", "volpath_simple_hip.cpp")]
 
     def compile_one(job):
         mode, f = job
