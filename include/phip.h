@@ -397,6 +397,33 @@ int  phip_trace(phip_scene *scene, const phip_ray *rays, size_t n,
    to each listed device (device-to-device copies over xGMI), so that a later multi-device render starts immediately. */
 int  phip_scene_replicate(phip_scene *scene, const int32_t *devices, int32_t n_devices);
 
+/* New vertex positions, vertex normals and / or camera for the scene as created: a REFIT of its acceleration structure, not a rebuild (a fly-through, a deforming
+   mesh).  After the call every entry point behaves exactly as if the scene had been created from the original descriptor with these positions, normals and camera:
+   per-sample radiance, film and the counters samples / closest_rays / shadow_rays / path_vertices / invalid_samples are the same bits (node-visit and triangle-test
+   counters, sah_cost and timings may differ: the refitted boxes are conservative, not the builder's).  The topology is the creation's -- indices, shapes, materials,
+   emitters, textures, film and crop window; node, record and leaf counts --, so fits_lds, fused_traversal and the kernels a render resolves do not change.
+   The call takes the scene's render lock (it serialises with renders), validates before it writes -- on any error the scene is unchanged -- and drops the replicas
+   on other devices, which the next multi-device render copies again.  Errors: PHIP_ERR_INVALID for a non-finite position, normal or camera transform, normals for a
+   scene created without them, an area emitter whose mesh has no area left, device_pointers = 1 with memory that is not the scene's device's; PHIP_ERR_UNSUPPORTED
+   (the count in phip_last_error) when a triangle that was degenerate at creation -- it got no Wald record -- is not degenerate now: a fresh build would give it a
+   record, a refit cannot.  The converse is served: a triangle that collapses gets the never-hit record and comes back with a later update.  PHIP_ERR_DEVICE without
+   a GPU: there is no CPU fallback.  How much slower a refitted tree traverses than a fresh one depends on how far the vertices went (DESIGN.md 3.12 has
+   measurements); the library fixes no threshold -- sah_cost is there for the caller to decide when to create the scene again. */
+typedef struct phip_update_desc {
+    const float *positions;      /* 3 * n_vertices of the scene as created, world space; NULL = unchanged */
+    const float *normals;        /* 3 * n_vertices; NULL = unchanged; PHIP_ERR_INVALID if the scene was created without normals */
+    const phip_camera *camera;   /* NULL = unchanged (film and crop window never change) */
+    uint32_t device_pointers;    /* 0: positions / normals are host memory; 1: device memory on the scene's device (a torch tensor's data_ptr()) */
+    void *stream;                /* device_pointers = 1: the hipStream_t the caller's producer ran on, or NULL; the update is ordered after it */
+} phip_update_desc;
+typedef struct phip_update_info {
+    double update_ms;            /* host wall clock of the call */
+    double kernel_ms;            /* HIP-event time of the device work */
+    float  sah_cost;             /* buildWide's cost formula on the refitted boxes; phip_scene_accel_info reports the same value from now on */
+    uint32_t n_degenerate;       /* triangles whose Wald record is the never-hit record after this update */
+} phip_update_info;
+int  phip_scene_update(phip_scene *scene, const phip_update_desc *update, phip_update_info *out_info /* may be NULL */);
+
 /* Thread-safe and sticky, like Scheduler::cancel on a process (src/libcore/sched.cpp): a running phip_render returns
    PHIP_ERR_CANCELLED; a request that arrives before the render starts cancels that render.  The flag is consumed by the
    call that observes it. */
@@ -427,7 +454,7 @@ int  phip_scene_accel_info(const phip_scene *scene, phip_accel_info *out);
 /* Utilities for callers that fill a phip_scene_desc without Mitsuba at hand (the test harness, bench.py): the table of the reference's default `gaussian` reconstruction
  * filter with the given standard deviation -- (radius, PHIP_FILTER_RESOLUTION + 1 values), rfilter.cpp:38-57 + gaussian.cpp:34-57; the Mitsuba shim copies the scene's own
  * filter instead -- and sizeof of the ABI's structs by index (0 phip_material, 1 phip_shape, 2 phip_emitter, 3 phip_camera, 4 phip_film, 5 phip_scene_desc,
- * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
+ * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info, 11 phip_update_desc, 12 phip_update_info), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
 void   phip_gaussian_filter(float stddev, float *radius, float *table);
 size_t phip_abi_sizeof(int which);
 

@@ -153,6 +153,18 @@ class phip_accel_info(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class phip_update_desc(C.Structure):
+    _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p), ("camera", C.POINTER(phip_camera)),
+                ("device_pointers", C.c_uint32), ("stream", C.c_void_p)]
+
+
+class phip_update_info(C.Structure):
+    _fields_ = [("update_ms", C.c_double), ("kernel_ms", C.c_double), ("sah_cost", C.c_float), ("n_degenerate", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 def default_render_params(**kw):
     """MonteCarloIntegrator defaults (src/librender/integrator.cpp:190-225)."""
     p = phip_render_params()

@@ -47,6 +47,8 @@ UNITS = [("phip_shade.hip", ["-DSHADE_FEAT=%d" % f, "-DSHADE_PART=%d" % q], "phi
 # phip_shade_w.hip (k_shade_trace_w: a persistent loop around the vertex code, so MachineLICM costs it what it costs k_mega -- 164..580 B of scratch per lane with it,
 # 12..308 B without): once per feature set, appended so that the units above keep their place
 UNITS += [("phip_shade_w.hip", MEGA_FLAGS + ["-DSHADE_FEAT=%d" % f], "phip_tracew%d.o" % f) for f in SHADE_FEATS]
+# phip_update.hip (the refit kernels of phip_scene_update, k_update.h): one small object, appended likewise
+UNITS += [("phip_update.hip", [], "phip_update.o")]
 
 
 DEBUG_UNIT = ("phip.hip", ["-DPHIP_DEBUG_HOOKS=1"], "phip_dbg.o")
@@ -124,6 +126,8 @@ def _build_locked(sid, out_lib, verbose):
             return feat_cost.get(int(f), 20.0) * (0.42 if q == "2" else 1.0)
         if name.startswith("phip_tracew"):
             return 2.0 * feat_cost.get(int(re.match(r"phip_tracew(\d+)", name).group(1)), 20.0)
+        if name.startswith("phip_update"):
+            return 3.0
         return 31.0 if name.startswith("phip_mega") else 14.0
     cmds.sort(key=cost, reverse=True)
     import concurrent.futures
@@ -160,7 +164,7 @@ TEST_VARIANTS = {"fault": "-DMEGA_MB_FAULT=1",       # waves of fused launches r
                  "cap32": "-DWP_CAP=32u",            # 32-entry task stacks: nearly every push of a big scene spills to memory
                  "overflow": "-DWP_CAP=64u -DWP_SPILL_CAP=64u"}      # 128-entry task stacks, half of them spilled: the tree-in-memory scenes outgrow them -- the wave stops, the pass is re-rendered
 # sources whose objects a variant takes from the product build: its flags do not concern them (the task stacks are k_mega's and k_shade_trace_w's)
-VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip", "cap32": "phip_shade.hip", "overflow": "phip_shade.hip"}
+VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip phip_update.hip", "cap32": "phip_shade.hip phip_update.hip", "overflow": "phip_shade.hip phip_update.hip"}
 
 
 def build_test_variant(tag):
@@ -204,6 +208,7 @@ def lib():
     L.phip_trace.argtypes = [C.c_void_p, C.POINTER(A.phip_ray), C.c_size_t, C.POINTER(A.phip_hit), u8p, C.POINTER(A.phip_stats)]
     L.phip_cancel.argtypes = [C.c_void_p]
     L.phip_scene_replicate.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
+    L.phip_scene_update.argtypes = [C.c_void_p, C.POINTER(A.phip_update_desc), C.POINTER(A.phip_update_info)]
     L.phip_develop.argtypes = [fp, C.c_size_t, fp]
     L.phip_scene_accel_info.argtypes = [C.c_void_p, C.POINTER(A.phip_accel_info)]
     L.phip_gaussian_filter.argtypes = [C.c_float, fp, fp]
@@ -255,6 +260,8 @@ def debug_lib():
     L.phip_debug_host_mip_eval.argtypes = [C.POINTER(A.phip_texture), C.c_size_t, fp, fp, fp, fp]
     L.phip_debug_host_build_bvh.argtypes = [fp, u32, C.POINTER(C.c_uint32), u32, C.POINTER(A.phip_accel_info), fp]
     L.phip_debug_host_trace_wide.argtypes = [fp, u32, C.POINTER(C.c_uint32), u32, C.POINTER(A.phip_ray), C.c_size_t, C.POINTER(A.phip_hit), C.c_int, C.POINTER(A.phip_accel_info), u8p, u32]
+    L.phip_debug_host_refit_trace_wide.argtypes = [fp, fp, fp, u32, C.POINTER(C.c_uint32), u32, fp, C.POINTER(A.phip_ray), C.c_size_t, C.POINTER(A.phip_hit),
+                                                   C.POINTER(A.phip_accel_info), C.POINTER(C.c_uint32), fp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.phip_debug_fmath.argtypes = [C.c_int, C.c_int, C.c_size_t, fp, fp, fp]
     L.phip_debug_selected_kernel.argtypes = [C.c_int] * 7; L.phip_debug_selected_kernel.restype = C.c_char_p
     _debug = L

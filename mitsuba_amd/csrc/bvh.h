@@ -31,6 +31,7 @@
 #include <functional>
 #include <thread>
 #include <exception>
+#include "refit_hd.h"      /* waldLoad, padOf, sceneBoxOf, wideGridOf / wideQuantise: the arithmetic this builder shares with the refit kernels (k_update.h) */
 
 namespace pt {
 
@@ -44,6 +45,7 @@ struct HostBVH {
     std::vector<uint32_t> wnodes; /* 20 dwords per node */
     std::vector<float> wtris;     /* 12 floats per triangle record, grouped per wide node (each node's leaf triangles are consecutive) */
     uint32_t nWNodes = 0, wMaxDepth = 0, nWTris = 0; float wSahCost = 0;
+    std::vector<uint32_t> wLevels; /* the nodes are in breadth-first order: level l is nodes wLevels[l] .. wLevels[l + 1] (what a refit walks from the deepest level up) */
     std::vector<float> nodes2;    /* 16 floats per node of the intermediate binary tree (released when the wide tree is built) */
     uint32_t nNodes2 = 0;
     std::vector<float> tris;      /* 12 floats per triangle record, leaf order */
@@ -59,34 +61,7 @@ struct HostBVH {
 
 namespace detail {
 
-inline float bits2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-
-/* TriAccel::load, triaccel.h:61-93 -- returns false for degenerate triangles (k = 3) */
-inline bool waldLoad(const float *A, const float *B, const float *C, uint32_t prim, float *out12) {
-    static const int waldModulo[4] = { 1, 2, 0, 1 };
-    float b[3] = { C[0] - A[0], C[1] - A[1], C[2] - A[2] };
-    float c[3] = { B[0] - A[0], B[1] - A[1], B[2] - A[2] };
-    float N[3] = { c[1] * b[2] - c[2] * b[1], c[2] * b[0] - c[0] * b[2], c[0] * b[1] - c[1] * b[0] };
-    uint32_t k = 0;
-    for (int j = 0; j < 3; j++)
-        if (std::fabs(N[j]) > std::fabs(N[k])) k = j;
-    uint32_t u = waldModulo[k], v = waldModulo[k + 1];
-    const float n_k = N[k], denom = b[u] * c[v] - b[v] * c[u];
-    if (denom == 0) return false;
-    out12[0] = bits2f(k);
-    out12[1] = N[u] / n_k;
-    out12[2] = N[v] / n_k;
-    out12[3] = (A[0] * N[0] + A[1] * N[1] + A[2] * N[2]) / n_k;
-    out12[4] = A[u];
-    out12[5] = A[v];
-    out12[6] = b[u] / denom;
-    out12[7] = -b[v] / denom;
-    out12[8] = c[v] / denom;
-    out12[9] = -c[u] / denom;
-    out12[10] = bits2f(prim);
-    out12[11] = 0.0f;
-    return true;
-}
+/* (bits2f, waldLoad -- TriAccel::load, triaccel.h:61-93 --: refit_hd.h) */
 
 struct Box {
     float mn[3], mx[3];
@@ -180,7 +155,7 @@ struct Builder {
         /* (the LARGEST extent on every axis: a scene that is flat on one axis -- everything in the plane y = 0 -- must not lose its pad there) */
         const float maxExtent = std::max(extent[0], std::max(extent[1], extent[2]));
         for (int i = 0; i < 3; ++i) {
-            float e = 1e-5f * std::max(std::fabs(b.mn[i]), std::fabs(b.mx[i])) + 1e-7f * (b.mx[i] - b.mn[i]) + 2e-6f * maxExtent + camPad[i] + 1e-30f;
+            float e = padOf(b.mn[i], b.mx[i], maxExtent, camPad[i]);
             b.mn[i] -= e; b.mx[i] += e;
         }
     }
@@ -200,7 +175,7 @@ struct Builder {
         }
         out.nLeaves++; out.nTriRefs += count;
         if (count == 0) { /* keep a well-formed (never-hit) leaf: one record with k = 3 */
-            float rec[12] = { 0 }; rec[0] = bits2f(3u); rec[10] = bits2f(0xFFFFFFFFu);
+            float rec[12]; waldNeverHit(rec);
             out.tris.insert(out.tris.end(), rec, rec + 12);
             count = 1;
         }
@@ -593,7 +568,7 @@ struct Reinserter {
  */
 template <typename Children2>
 inline void buildWide(HostBVH &out, int32_t root2, const detail::Box &rootBox, Children2 children2) {
-    out.wnodes.clear(); out.wtris.clear(); out.nWNodes = 0; out.wMaxDepth = 0; out.nWTris = 0; out.wSahCost = 0;
+    out.wnodes.clear(); out.wtris.clear(); out.nWNodes = 0; out.wMaxDepth = 0; out.nWTris = 0; out.wSahCost = 0; out.wLevels.clear();
     /* (root2 < 0: the whole scene is ONE leaf -- round 6: it still gets a wide root whose only children are the pieces of that leaf, because every scene's ray kernels walk
        the wide tree; the collapse below has nothing to decide then) */
     typedef detail::ChildRef Child;
@@ -654,6 +629,7 @@ inline void buildWide(HostBVH &out, int32_t root2, const detail::Box &rootBox, C
     for (size_t head = 0; head < queue.size(); ++head) {
         const Item it = queue[head];
         out.wMaxDepth = std::max(out.wMaxDepth, it.depth);
+        if (out.wLevels.size() < it.depth) out.wLevels.push_back(it.index);            /* (breadth first: depths do not decrease along the queue, index = place in it) */
         /* the children of this wide node, as the SAH-optimal collapse (cost table below) distributes its 8 slots */
         std::vector<Child> ch;
         if (it.ref2 < 0) ch.push_back(Child{ it.ref2, it.box }); else expand(it.ref2, 8, ch);
@@ -667,16 +643,8 @@ inline void buildWide(HostBVH &out, int32_t root2, const detail::Box &rootBox, C
         /* node box = union of the (padded) child boxes */
         detail::Box nb; nb.reset();
         for (const WChild &w : wc) nb.grow(w.c.box.mn, w.c.box.mx);
-        float p[3]; uint32_t e8[3]; double step[3];
-        for (int a = 0; a < 3; ++a) {
-            p[a] = nb.mn[a];
-            const double ext = (double) nb.mx[a] - (double) p[a];
-            int e = -120;
-            if (ext > 0) { int ex; std::frexp(ext / 255.0, &ex); e = ex; }            /* 2^e >= ext / 255 */
-            while (std::ldexp(1.0, e) * 255.0 < ext) ++e;
-            e = std::min(127, std::max(-120, e));
-            e8[a] = (uint32_t) (e + 127); step[a] = std::ldexp(1.0, e);
-        }
+        detail::WideGrid grid; detail::wideGridOf(nb.mn, nb.mx, grid);
+        const float *p = grid.p; const uint32_t *e8 = grid.e8;
         /* slot assignment by octant direction (greedy on the dot product) */
         const float cen[3] = { 0.5f * (nb.mn[0] + nb.mx[0]), 0.5f * (nb.mn[1] + nb.mx[1]), 0.5f * (nb.mn[2] + nb.mx[2]) };
         int slotOf[8]; bool slotUsed[8] = { false }, childDone[8] = { false };
@@ -709,12 +677,8 @@ inline void buildWide(HostBVH &out, int32_t root2, const detail::Box &rootBox, C
             const int c = childAt[sl];
             if (c < 0) continue;
             const WChild &w = wc[c];
-            for (int a = 0; a < 3; ++a) {
-                const double lo = std::floor(((double) w.c.box.mn[a] - (double) p[a]) / step[a]);
-                const double hi = std::ceil(((double) w.c.box.mx[a] - (double) p[a]) / step[a]);
-                q[a][sl] = (uint8_t) std::min(255.0, std::max(0.0, lo));
-                q[3 + a][sl] = (uint8_t) std::min(255.0, std::max(0.0, hi));
-            }
+            uint8_t qlo[3], qhi[3]; detail::wideQuantise(grid, w.c.box.mn, w.c.box.mx, qlo, qhi);
+            for (int a = 0; a < 3; ++a) { q[a][sl] = qlo[a]; q[3 + a][sl] = qhi[a]; }
             cost += w.c.box.area() / rootA * (w.c.ref < 0 ? (double) w.nTris : 1.0);
             if (w.c.ref >= 0) {
                 imask |= 1u << sl;
@@ -736,6 +700,7 @@ inline void buildWide(HostBVH &out, int32_t root2, const detail::Box &rootBox, C
         nd[16] = pack4(q[4]); nd[17] = pack4(q[4] + 4); nd[18] = pack4(q[5]); nd[19] = pack4(q[5] + 4);
     }
     out.wSahCost = (float) (cost + 1.0);
+    out.wLevels.push_back(out.nWNodes);
 }
 
 inline void buildBVH(const float *positions, const uint32_t *indices, uint32_t nTris, HostBVH &out, const float *cameraPosition = nullptr) {
@@ -759,16 +724,10 @@ inline void buildBVH(const float *positions, const uint32_t *indices, uint32_t n
     for (int a = 0; a < 3; ++a) { out.tightMin[a] = tight.mn[a]; out.tightMax[a] = tight.mx[a]; }
     /* scene box: tight box enlarged exactly like the reference's kd-tree root (gkdtree.h:1213-1220):
        min -= (max-min)*eps + eps; max += (max-min_new)*eps + eps */
-    const float eps = 1e-3f;
-    for (int a = 0; a < 3; ++a) {
-        float mn = tight.mn[a], mx = tight.mx[a];
-        mn -= (mx - mn) * eps + eps;
-        mx += (mx - mn) * eps + eps;
-        out.sceneMin[a] = mn; out.sceneMax[a] = mx;
-    }
+    detail::sceneBoxOf(tight.mn, tight.mx, out.sceneMin, out.sceneMax);
     if (nTris == 0) {
         /* empty scene: a single never-hit leaf */
-        float rec[12] = { 0 }; rec[0] = detail::bits2f(3u); rec[10] = detail::bits2f(0xFFFFFFFFu);
+        float rec[12]; detail::waldNeverHit(rec);
         out.tris.assign(rec, rec + 12);
         for (int a = 0; a < 3; ++a) { out.sceneMin[a] = out.tightMin[a] = 0; out.sceneMax[a] = out.tightMax[a] = 0; }
         return;
@@ -780,8 +739,7 @@ inline void buildBVH(const float *positions, const uint32_t *indices, uint32_t n
            arbiter: the oracle's sweep over all triangles -- then accepts rays that pass a triangle's silhouette by up to ~4 ulp(|o|) ON ANY AXIS (the plane equation's numerator
            is rounded at the magnitude of the origin's LARGEST component and divided by the dominant component of the normal; round 6 found one such sample in 32768: the ray
            0.03 units beside the tall block of the Cornell box).  So every axis is padded by the largest component, not by its own (8 ulp). */
-        const float m = std::max(std::fabs(cameraPosition[0]), std::max(std::fabs(cameraPosition[1]), std::fabs(cameraPosition[2])));
-        for (int a = 0; a < 3; ++a) B.camPad[a] = 4.8e-7f * m;
+        for (int a = 0; a < 3; ++a) B.camPad[a] = detail::camPadOf(cameraPosition);
     }
     detail::Box rootBox;
     /* spatial splits for the scenes that use the wide tree (small scenes are laid out for LDS record by record) */

@@ -108,7 +108,7 @@ void spiralBlocks(int sizeX, int sizeY, int bs, std::vector<std::pair<int, int>>
 }
 
 } // namespace
-/* Everything that lives on ONE GPU: the immutable scene arrays and the render-time buffers of the jobs that run there.
+/* Everything that lives on ONE GPU: the scene arrays (written by the creation and by phip_scene_update, never by a render) and the render-time buffers of the jobs that run there.
    devs[0] of a phip_scene is the device of phip_scene_create; further entries are replicas made by device-to-device copies.
    A new scene buffer is declared below, added to forEachSceneBuffer (the one list replicateScene clones through) and given its line in bind()
    (the only code that writes a buffer pointer into the DevScene); SceneBuild::uploadScene fills it. */
@@ -166,6 +166,25 @@ struct SceneDev {
     }
 };
 
+/* What phip_scene_update needs of the creation (host_update.h): the topology it keeps fixed.  The host side is filled by SceneBuild::keepForUpdate; the device side is
+   made by the first update, so a scene that is never updated pays a few host copies and no device memory */
+struct SceneUpdateState {
+    uint32_t nVertices = 0, nTriangles = 0; bool hasNormals = false;
+    std::vector<uint32_t> indices;                   /* 3 x nTriangles */
+    std::vector<uint32_t> wRecPrim, recPrim;         /* the primitive of every Wald record of wtris / tris (0xFFFFFFFF: a leaf's never-hit placeholder): the side table that lets a collapsed triangle come back */
+    std::vector<uint32_t> hadRecord;                 /* one bit per triangle: it got a Wald record (degenerate triangles are dropped by makeLeaf: a refit cannot give them one) */
+    std::vector<uint32_t> wLevels;                   /* HostBVH::wLevels */
+    std::vector<int32_t> leafRefs;                   /* the references of the packed leaf table's leaves, in its order */
+    struct EmitterMesh { uint32_t emitter, firstTri, nTris, firstVertex, endVertex; };      /* area emitters: their triangles and the vertex range those use */
+    std::vector<EmitterMesh> emitterMeshes;
+    std::vector<float> tab; size_t ecdfSize = 0;     /* the packed emitter table as uploaded; its selection cdf's length */
+    std::vector<float> hostPositions;                /* device-pointer updates: the emitter meshes' vertex ranges, copied back */
+    uint32_t nDegenerate = 0;
+    bool onDevice = false;
+    DevBuf<uint32_t> dIndices, dWRecPrim, dRecPrim, dHadRecord, dCounters; DevBuf<int32_t> dLeafRefs;
+    DevBuf<float> dPositions, dNormals, dNodeBox, dSahTerm, dPartials; DevBuf<detail::RefitConsts> dConsts;
+};
+
 struct phip_scene {
     phip_scene_desc descCopy;        /* scalar fields only */
     HostBVH bvh;                     /* tree statistics (the node / record arrays are released after the upload) */
@@ -178,6 +197,7 @@ struct phip_scene {
     bool fitsLds = false;            /* tree, Wald records, shading records, emitter table and materials fit the fused kernel's LDS plan */
     bool wideTrace = false;          /* k_shade_trace_w can run the scene's iterations: it is on the 8-wide tree only, with any feature set k_shade serves (textures, UVs, `constant`, `envmap`) */
     int fusedWide = 0;               /* round 6: 4 / 5 = the fused kernel walks the 8-wide tree from memory (k_mega<.., FLAT 4 / 5, ..>: emitter table in LDS; materials in LDS / in memory) */
+    SceneUpdateState upd;
     std::vector<std::unique_ptr<SceneDev>> devs;
     int *cancelFlag = nullptr;       /* host-pinned (portable, mapped): phip_cancel writes it, host loops and k_mega poll it */
     std::mutex renderLock;
@@ -279,6 +299,42 @@ static bool anisotropic(const phip_scene_desc &d, uint32_t m, int depth = 0) {
     return false;
 }
 
+/* TriMesh::prepareSamplingTable, trimesh.cpp:388-404 + DiscreteDistribution::normalize: the area CDF of a mesh's triangles (n + 1 entries); returns 1 / surface area */
+static float areaCdfOf(const float *positions, const uint32_t *indices, uint32_t firstTri, uint32_t nTris, std::vector<float> &cdf) {
+    cdf.assign(1, 0.0f);
+    for (uint32_t j = 0; j < nTris; ++j) {
+        const uint32_t *ix = indices + 3 * (size_t) (firstTri + j);
+        const float *p0 = positions + 3 * (size_t) ix[0], *p1 = positions + 3 * (size_t) ix[1], *p2 = positions + 3 * (size_t) ix[2];
+        V3 a(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]), b(p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]);
+        cdf.push_back(cdf.back() + 0.5f * cross(a, b).length());
+    }
+    const float sum = cdf.back();
+    if (!(sum > 0)) throw std::runtime_error("area emitter with zero surface area");
+    const float norm = 1.0f / sum;
+    for (size_t j = 1; j < cdf.size(); ++j) cdf[j] *= norm;
+    cdf.back() = 1.0f;
+    return 1.0f / sum;
+}
+
+/* ConstantBackgroundEmitter::createShape (constant.cpp:67-72) as seen from Scene::initializeBidirectional
+   (scene.cpp:384-413): bounding sphere (aabb.cpp:44-47) of the kd-tree's enlarged box expanded by the sensor
+   position (track.cpp:79-83), radius x 1.5 */
+static void environmentSphereOf(const float *sceneMin, const float *sceneMax, uint32_t nTriangles, const phip_camera &camera, DevScene &D) {
+    float mn[3], mx[3];
+    for (int a = 0; a < 3; ++a) {
+        mn[a] = nTriangles ? sceneMin[a] : INFINITY; mx[a] = nTriangles ? sceneMax[a] : -INFINITY;
+    }
+    const float *m = camera.to_world;
+    V3 sp(m[3], m[7], m[11]);
+    if (m[15] != 1.0f) sp = sp / m[15];
+    const float spv[3] = { sp.x, sp.y, sp.z };
+    for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], spv[a]); mx[a] = std::max(mx[a], spv[a]); }
+    const V3 center = (V3(mx[0], mx[1], mx[2]) + V3(mn[0], mn[1], mn[2])) * 0.5f;
+    const float radius = (center - V3(mx[0], mx[1], mx[2])).length();
+    D.envCenter[0] = center.x; D.envCenter[1] = center.y; D.envCenter[2] = center.z;
+    D.envRadius = std::max(PT_EPSILON, radius * 1.5f);
+}
+
 /* One phip_scene_create: what the stages of buildScene hand to each other.  Every stage up to chooseDevicePaths works on host arrays and calls no HIP
    function; uploadScene is the only one that allocates or copies scene buffers. */
 struct SceneBuild {
@@ -333,19 +389,8 @@ struct SceneBuild {
                 /* TriMesh::prepareSamplingTable, trimesh.cpp:388-404 + DiscreteDistribution::normalize */
                 if (s.n_triangles == 0) throw std::runtime_error("area emitter on an empty mesh");
                 o.cdfOffset = (uint32_t) areaCdf.size();
-                std::vector<float> cdf(1, 0.0f);
-                for (uint32_t j = 0; j < s.n_triangles; ++j) {
-                    const uint32_t *ix = d.indices + 3 * (size_t) (s.first_triangle + j);
-                    const float *p0 = d.positions + 3 * (size_t) ix[0], *p1 = d.positions + 3 * (size_t) ix[1], *p2 = d.positions + 3 * (size_t) ix[2];
-                    V3 a(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]), b(p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]);
-                    cdf.push_back(cdf.back() + 0.5f * cross(a, b).length());
-                }
-                const float sum = cdf.back();
-                if (!(sum > 0)) throw std::runtime_error("area emitter with zero surface area");
-                const float norm = 1.0f / sum;
-                for (size_t j = 1; j < cdf.size(); ++j) cdf[j] *= norm;
-                cdf.back() = 1.0f;
-                o.invSurfaceArea = 1.0f / sum;
+                std::vector<float> cdf;
+                o.invSurfaceArea = areaCdfOf(d.positions, d.indices, s.first_triangle, s.n_triangles, cdf);
                 areaCdf.insert(areaCdf.end(), cdf.begin(), cdf.end());
             }
         }
@@ -445,38 +490,25 @@ struct SceneBuild {
             const uint32_t front = twosided ? m.nested0 : sh.material, back = twosided ? m.nested1 : sh.material;     /* (tagShadeClasses reads them back from the record) */
             uint32_t flags = (sh.hasNormals ? TS_VERTEX_NORMALS : 0u) | (twosided ? TS_TWOSIDED : 0u) | (texcoords ? TS_TEXCOORDS : 0u)
                            | ((m.flags & MF_SMOOTH) ? TS_MF_SMOOTH : 0u) | ((m.flags & MF_TRANS_OR_BACK) ? TS_TRANS_OR_BACK : 0u);
-            const V3 side1(p1 - p0), side2(p2 - p0);
-            V3 dpdu = side1, dpdv = side2;                      /* skdtree.h:378-379 */
             float4 *r = ts.data() + (size_t) stride * i;
+            V2 t0(0, 0), t1(0, 0), t2(0, 0);
             if (texcoords) {
-                /* TriMesh::computeUVTangents, trimesh.cpp:683-735 (zero tangents for degenerate triangles) */
-                const float *t0 = d.texcoords + 2 * (size_t) ix[0], *t1 = d.texcoords + 2 * (size_t) ix[1], *t2 = d.texcoords + 2 * (size_t) ix[2];
-                dpdu = V3(0.0f); dpdv = V3(0.0f);
-                const V2 dUV1(t1[0] - t0[0], t1[1] - t0[1]), dUV2(t2[0] - t0[0], t2[1] - t0[1]);
-                const V3 n = cross(side1, side2);
-                const float length = n.length();
-                if (length != 0) {
-                    const float determinant = dUV1.x * dUV2.y - dUV1.y * dUV2.x;
-                    if (determinant == 0) {
-                        coordinateSystem(n / length, dpdu, dpdv);
-                    } else {
-                        const float invDet = 1.0f / determinant;
-                        dpdu = (side1 * dUV2.y - side2 * dUV1.y) * invDet;
-                        dpdv = (side1 * (-dUV2.x) + side2 * dUV1.x) * invDet;
-                    }
-                }
-                r[6] = make_float4(t0[0], t0[1], t1[0], t1[1]);
-                r[7] = make_float4(t2[0], t2[1], dpdu.x, dpdu.y);
-                r[8] = make_float4(dpdu.z, dpdv.x, dpdv.y, dpdv.z);
+                const float *c0 = d.texcoords + 2 * (size_t) ix[0], *c1 = d.texcoords + 2 * (size_t) ix[1], *c2 = d.texcoords + 2 * (size_t) ix[2];
+                t0 = V2(c0[0], c0[1]); t1 = V2(c1[0], c1[1]); t2 = V2(c2[0], c2[1]);
             }
-            V3 a, b, c;
+            V3 n0(0.0f), n1(0.0f), n2(0.0f);
             if (sh.hasNormals) {
-                a = V3(d.normals[3 * ix[0]], d.normals[3 * ix[0] + 1], d.normals[3 * ix[0] + 2]);
-                b = V3(d.normals[3 * ix[1]], d.normals[3 * ix[1] + 1], d.normals[3 * ix[1] + 2]);
-                c = V3(d.normals[3 * ix[2]], d.normals[3 * ix[2] + 1], d.normals[3 * ix[2] + 2]);
-            } else {
-                Frame f; triShadingFrame(triFaceNormal(side1, side2), dpdu, f);
-                a = f.n; b = f.s; c = f.t;
+                n0 = V3(d.normals[3 * ix[0]], d.normals[3 * ix[0] + 1], d.normals[3 * ix[0] + 2]);
+                n1 = V3(d.normals[3 * ix[1]], d.normals[3 * ix[1] + 1], d.normals[3 * ix[1] + 2]);
+                n2 = V3(d.normals[3 * ix[2]], d.normals[3 * ix[2] + 1], d.normals[3 * ix[2] + 2]);
+            }
+            /* dpdu / dpdv (skdtree.h:378-379, or TriMesh::computeUVTangents) and the frame or the vertex normals: refit_hd.h, which the update's kernel runs too */
+            V3 dpdu, dpdv, a, b, c;
+            detail::triShadeGeometry(p0, p1, p2, texcoords, t0, t1, t2, sh.hasNormals != 0, n0, n1, n2, dpdu, dpdv, a, b, c);
+            if (texcoords) {
+                r[6] = make_float4(t0.x, t0.y, t1.x, t1.y);
+                r[7] = make_float4(t2.x, t2.y, dpdu.x, dpdu.y);
+                r[8] = make_float4(dpdu.z, dpdv.x, dpdv.y, dpdv.z);
             }
             r[0] = make_float4(p0.x, p0.y, p0.z, pm_from_bits(front));
             r[1] = make_float4(p1.x, p1.y, p1.z, pm_from_bits(back));
@@ -561,24 +593,9 @@ struct SceneBuild {
         tab.resize((tab.size() + 3) / 4 * 4, 0.0f);              /* whole float4s: the shading kernels stage the table in LDS with 16-byte loads */
     }
 
-    /* ConstantBackgroundEmitter::createShape (constant.cpp:67-72) as seen from Scene::initializeBidirectional
-       (scene.cpp:384-413): bounding sphere (aabb.cpp:44-47) of the kd-tree's enlarged box expanded by the sensor
-       position (track.cpp:79-83), radius x 1.5 */
+    /* the environment emitter's bounding sphere (environmentSphereOf) */
     void environmentSphere() {
-        if (envEmitter < 0) return;
-        float mn[3], mx[3];
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = d.n_triangles ? sc->bvh.sceneMin[a] : INFINITY; mx[a] = d.n_triangles ? sc->bvh.sceneMax[a] : -INFINITY;
-        }
-        const float *m = d.camera.to_world;
-        V3 sp(m[3], m[7], m[11]);
-        if (m[15] != 1.0f) sp = sp / m[15];
-        const float spv[3] = { sp.x, sp.y, sp.z };
-        for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], spv[a]); mx[a] = std::max(mx[a], spv[a]); }
-        const V3 center = (V3(mx[0], mx[1], mx[2]) + V3(mn[0], mn[1], mn[2])) * 0.5f;
-        const float radius = (center - V3(mx[0], mx[1], mx[2])).length();
-        D.envCenter[0] = center.x; D.envCenter[1] = center.y; D.envCenter[2] = center.z;
-        D.envRadius = std::max(PT_EPSILON, radius * 1.5f);
+        if (envEmitter >= 0) environmentSphereOf(sc->bvh.sceneMin, sc->bvh.sceneMax, d.n_triangles, d.camera, D);
     }
 
     /* EnvironmentMap::configure, envmap.cpp:262-328: the pyramid's texels, marginal / conditional CDFs over luminance * sin(theta), the transforms */
@@ -699,14 +716,12 @@ struct SceneBuild {
             const float ext = std::max(sc->bvh.tightMax[0] - sc->bvh.tightMin[0], std::max(sc->bvh.tightMax[1] - sc->bvh.tightMin[1], sc->bvh.tightMax[2] - sc->bvh.tightMin[2]));
             const float camMax = std::max(std::fabs(d.camera.to_world[3]), std::max(std::fabs(d.camera.to_world[7]), std::fabs(d.camera.to_world[11])));
             float c[3], h[3];
-            const float *lo = leaf.mn, *hi = leaf.mx;
-            for (int a = 0; a < 3; ++a) {
-                c[a] = (float) (0.5 * ((double) lo[a] + (double) hi[a]));
-                const double need = std::max((double) c[a] - (double) lo[a], (double) hi[a] - (double) c[a]);
+            /* (the arithmetic: detail::leafCentreHalf, refit_hd.h -- h = nextafter(need) + 2.4e-7 |c| + 4e-6 ext + 4.8e-7 camMax, need = the larger distance from c to a face) */
+            {
                 /* ... and the rounding of o rcp, which grows with the ORIGIN's magnitude (two roundings of |o rcp| move a plane by ~2^-23 |o|): the only rays
                    that start outside the scene box are the camera's, so the camera position pays for it (a camera 60 scene extents away used to lose
                    leaf boxes; tests/test_gpu_parity.py: far camera) */
-                h[a] = std::nextafter((float) need, INFINITY) + 2.4e-7f * std::fabs(c[a]) + 4e-6f * ext + 4.8e-7f * camMax;      /* (the largest component on every axis: bvh.h, buildBVH) */
+                detail::leafCentreHalf(leaf.mn, leaf.mx, ext, camMax, c, h);      /* (the camera's largest component on every axis: bvh.h, buildBVH) */
             }
             flat.push_back(make_float4(c[0], c[1], c[2], pm_from_bits(bitsHi)));
             flat.push_back(make_float4(h[0], h[1], h[2], pm_from_bits(bits)));
@@ -742,6 +757,34 @@ struct SceneBuild {
            k_shade -7 %); on a diffuse + dielectric mix the extra round trip costs more than the cheap Fresnel branch (glass room: +8 %).
            k_shade_trace deals its lanes by BSDF model where there is more than one (the kernel traces its own rays and leaves the class in the hit word) */
         D.shadeSort = ((mask & MM_ROUGH) || (traceable && mask != 0)) ? 1u : 0u;
+    }
+
+    /* the topology a later phip_scene_update keeps fixed (SceneUpdateState); before uploadScene releases the builder's arrays */
+    void keepForUpdate() {
+        SceneUpdateState &U = sc->upd;
+        const HostBVH &bvh = sc->bvh;
+        U.nVertices = d.n_vertices; U.nTriangles = d.n_triangles; U.hasNormals = d.normals != nullptr;
+        U.indices.assign(d.indices, d.indices + 3 * (size_t) d.n_triangles);
+        U.hadRecord.assign(((size_t) d.n_triangles + 31) / 32 + 1, 0u);
+        auto prims = [&](const std::vector<float> &recs, std::vector<uint32_t> &out) {
+            out.resize(recs.size() / 12);
+            for (size_t r = 0; r < out.size(); ++r) {
+                memcpy(&out[r], &recs[12 * r + 10], 4);
+                if (out[r] < d.n_triangles) U.hadRecord[out[r] >> 5] |= 1u << (out[r] & 31u);
+            }
+        };
+        prims(bvh.wtris, U.wRecPrim);
+        if (!sc->wideOnly) prims(bvh.tris, U.recPrim);
+        U.wLevels = bvh.wLevels;
+        if (!flat.empty()) for (const HostBVH::LeafBox &leaf : bvh.leaves) U.leafRefs.push_back(leaf.ref);
+        for (uint32_t i = 0; i < d.n_emitters; ++i) {
+            if (ems[i].shape == 0xFFFFFFFFu) continue;
+            const DevShape &sh = shapes[ems[i].shape];
+            SceneUpdateState::EmitterMesh m = { i, sh.firstTri, sh.nTris, 0xFFFFFFFFu, 0u };
+            for (size_t k = 3 * (size_t) sh.firstTri; k < 3 * (size_t) (sh.firstTri + sh.nTris); ++k) { m.firstVertex = std::min(m.firstVertex, d.indices[k]); m.endVertex = std::max(m.endVertex, d.indices[k] + 1u); }
+            U.emitterMeshes.push_back(m);
+        }
+        U.tab = tab; U.ecdfSize = ecdf.size();
     }
 
     /* every immutable scene buffer of the device (placeholders where a kernel argument must not be NULL), the DevScene's pointers, the per-device counters */
@@ -790,6 +833,7 @@ static void buildScene(phip_scene *sc, const phip_scene_desc &d) {
     B.packEmitterTable(); B.environmentSphere(); B.buildEnvmap();
     B.sceneConstants();
     B.ldsPlan(); B.flatLeafTable(); B.chooseDevicePaths();
+    B.keepForUpdate();
     B.uploadScene();
 }
 

@@ -15,7 +15,7 @@
  *       iteration that shades a slot's vertex and traces its shadow ray and its next ray on the packed leaf table in LDS (k_shade_trace.h); scenes of that
  *       kind whose tree lives in L2: k_shade_trace_w, the same iteration on the 8-wide tree in memory (k_shade_trace_w.h)
  *
- * libphip.so is 34 objects of four sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
+ * libphip.so is 35 objects of five sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
  * at plan time (host_render.h -- shadeUnit: the one table over the feature sets; megaKernelOf -> FusedPlan::kernel in planFused, shadeKernelOf / shadeTraceWideKernelOf ->
  * WavefrontPlan::vertex / vertexWide in selectVertexKernel), asks the runtime for the residency of the persistent ones (residentBlocksPerCU) and launches them.
  * Kernels and where they live:
@@ -35,6 +35,7 @@
  *   k_film.h      k_film_splat + k_film_merge (filters of reach <= 2 pixels: register accumulators, no float atomics, deterministic), k_film_tiled /
  *                 k_film (wider filters, small blocks): ImageBlock::put, include/mitsuba/render/imageblock.h:124-204;
  *                 k_reduce_stats, k_export_samples                                                                [this unit]
+ *   k_update.h    the refit of phip_scene_update: check, shading and Wald records, scene box, the 8-wide tree level by level, the leaf table   [phip_update.hip]
  *
  * This file: the C ABI -- error state, the guard that maps what an entry point's body throws to its error code, the entry of both render functions, the film's way
  * to the host and the extern "C" entry points.  The rest of the host side is three headers by concern, each including the ones before it:
@@ -42,6 +43,7 @@
  *                  camera set-up), replication of the scene to further GPUs through SceneDev's one list of buffers
  *   host_render.h  the choice of each render's kernels and the render loop of one device
  *   host_multi.h   the multi-device orchestration (one host thread + stream per GPU, ncclReduce of the films over RCCL/xGMI)
+ *   host_update.h  phip_scene_update: new vertices and camera on the tree as built (the kernels: k_update.h in phip_update.hip)
  * Not MFMA work: irregular traversal and gathers.  The product never includes, links or calls anything under oracle/.
  */
 #include "phip_common.h"
@@ -71,6 +73,7 @@ static int setErr(int code, const std::string &msg) { g_err = msg; return code; 
 #include "host_scene.h"
 #include "host_render.h"
 #include "host_multi.h"
+#include "host_update.h"
 
 /* Entry of both render functions: validation, the scene's render lock, single- or multi-device dispatch, the sticky
    cancellation flag (consumed by the call that observed it). */
@@ -103,7 +106,7 @@ static int renderImpl(phip_scene *sc, const phip_render_params *p, float *dOut, 
 struct ErrorCodes { int invalid, other; };
 static const ErrorCodes CREATE_ERRORS = { PHIP_ERR_UNSUPPORTED, PHIP_ERR_INVALID };     /* phip_scene_create: a scene the back end does not serve / a malformed one */
 static const ErrorCodes RENDER_ERRORS = { PHIP_ERR_INVALID, PHIP_ERR_DEVICE };          /* phip_render, phip_render_device: a bad argument / the runtime */
-static const ErrorCodes DEVICE_ERRORS = { PHIP_ERR_DEVICE, PHIP_ERR_DEVICE };           /* phip_scene_replicate, phip_film_to_host, phip_trace: their bodies check arguments themselves */
+static const ErrorCodes DEVICE_ERRORS = { PHIP_ERR_DEVICE, PHIP_ERR_DEVICE };           /* phip_scene_replicate, phip_scene_update, phip_film_to_host, phip_trace: their bodies check arguments themselves */
 template <typename Body> static int guarded(const ErrorCodes &codes, Body body) {
     try {
         return body();
@@ -159,6 +162,17 @@ int phip_scene_replicate(phip_scene *scene, const int32_t *devices, int32_t n_de
         if (const char *bad = ensureReplicas(scene, devices, n_devices)) return setErr(PHIP_ERR_INVALID, bad);
         HIP_TRY(hipSetDevice(scene->devs[0]->device));
         return PHIP_OK;
+    });
+}
+
+int phip_scene_update(phip_scene *scene, const phip_update_desc *u, phip_update_info *out_info) {
+    if (!scene || !u) return setErr(PHIP_ERR_INVALID, "NULL argument");
+    if (out_info) memset(out_info, 0, sizeof(*out_info));
+    int n = phip_device_count();
+    if (n <= 0) return n == 0 ? setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback") : PHIP_ERR_DEVICE;
+    return guarded(DEVICE_ERRORS, [&]() -> int {
+        std::lock_guard<std::mutex> lock(scene->renderLock);          /* serialises with renders */
+        return updateScene(scene, *u, out_info);
     });
 }
 
@@ -385,6 +399,8 @@ size_t phip_abi_sizeof(int which) {
         case 8: return sizeof(phip_ray);
         case 9: return sizeof(phip_hit);
         case 10: return sizeof(phip_accel_info);
+        case 11: return sizeof(phip_update_desc);
+        case 12: return sizeof(phip_update_info);
         default: return 0;
     }
 }

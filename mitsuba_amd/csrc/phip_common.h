@@ -2,7 +2,7 @@
  * phip_common.h -- what every translation unit of libphip.so starts with: HIP, the C ABI, the device scene layout and
  * shading functions (dv_scene.h), the path-pool layout (k_pool.h), the error macro.
  *
- * libphip.so is built from four sources (34 objects) so that they compile in parallel:
+ * libphip.so is built from five sources (35 objects) so that they compile in parallel:
  *   phip.hip          the C ABI + traversal and film kernels, with the host side it includes by concern: host_scene.h (scene build, replicas), host_render.h (kernel
  *                     selection, one device's render loop), host_multi.h (multi-device orchestration, RCCL): 1 object
  *   phip_shade.hip    k_shade / k_shade_direct / k_shade_trace instantiations behind the look-ups phipShade*KernelF<n> -- compiled per feature set (-DSHADE_FEAT=0..3, 8
@@ -10,6 +10,7 @@
  *   phip_shade_w.hip  k_shade_trace_w instantiations behind phipShadeTraceWideKernelF<n>, per feature set: 6 objects
  *   phip_mega.hip     k_mega instantiations behind phipMegaKernel (-DMEGA_PART=0: scenes in LDS) / phipMegaKernelWide (-DMEGA_PART=1: the 8-wide tree in memory) /
  *                     phipMegaKernelDirect (-DMEGA_PART=2: `direct`): 3 objects
+ *   phip_update.hip   the kernels of phip_scene_update (k_update.h) behind phipUpdateKernels: 1 object
  * The other units hold kernels and the look-ups that return them, nothing else: every launch and every query of the runtime is in phip.hip and its host headers.
  * No device function is called across units (everything on the device side is inline in headers), so no -fgpu-rdc.
  */
@@ -63,3 +64,11 @@ PHIP_DECLARE_SHADE_KERNELS(0) PHIP_DECLARE_SHADE_KERNELS(1) PHIP_DECLARE_SHADE_K
 MegaKernel phipMegaKernel(int materialMask, bool strictNormals, int flat, bool qmc);
 MegaKernel phipMegaKernelWide(int materialMask, bool strictNormals, int flat, bool qmc);
 MegaKernel phipMegaKernelDirect(int materialMask, bool strictNormals, int flat, bool qmc);
+/* the kernels of phip_scene_update (phip_update.hip, k_update.h); UpdateArgs is theirs */
+struct UpdateArgs;
+struct UpdateKernels {
+    void (*check)(UpdateArgs), (*shade)(UpdateArgs), (*box)(UpdateArgs), (*boxFinal)(UpdateArgs, uint32_t);
+    void (*wald)(UpdateArgs, float4 *, const uint32_t *, uint32_t);
+    void (*refitLevel)(UpdateArgs, uint32_t, uint32_t), (*leafTable)(UpdateArgs);
+};
+UpdateKernels phipUpdateKernels();

@@ -151,6 +151,81 @@ int phip_debug_host_build_bvh(const float *positions, uint32_t n_vertices, const
     } catch (const std::exception &e) { return setErr(PHIP_ERR_INVALID, e.what()); }
 }
 
+} // extern "C"
+
+/* the rays of the two hooks below through a wide tree on the host: scene-box clip, then the walk (use_wide) or every record in turn */
+static void hostTraceRays(const float *sceneMin, const float *sceneMax, const float4 *recs, size_t nRecs, const uint4 *wn, uint32_t nWNodes, int use_wide,
+                          const phip_ray *rays, size_t n_rays, phip_hit *hits, uint8_t *seq, uint32_t seq_stride) {
+    for (size_t i = 0; i < n_rays; ++i) {
+        const V3 o(rays[i].o[0], rays[i].o[1], rays[i].o[2]), d(rays[i].d[0], rays[i].d[1], rays[i].d[2]);
+        phip_hit h; h.t = INFINITY; h.u = h.v = 0; h.prim = PHIP_NO_HIT;
+        /* scene-box clip + adaptive epsilon, skdtree.cpp:112-142 (the host twin of clipToScene<false>) */
+        float nearT = -INFINITY, farT = INFINITY; bool ok = true;
+        const float oo[3] = { o.x, o.y, o.z }, dd[3] = { d.x, d.y, d.z };
+        for (int a = 0; a < 3 && ok; ++a) {
+            if (dd[a] == 0) { if (oo[a] < sceneMin[a] || oo[a] > sceneMax[a]) ok = false; }
+            else {
+                const float rcp = 1.0f / dd[a];
+                float t1 = (sceneMin[a] - oo[a]) * rcp, t2 = (sceneMax[a] - oo[a]) * rcp;
+                if (t1 > t2) std::swap(t1, t2);
+                nearT = smax(t1, nearT); farT = smin(t2, farT);
+                if (!(nearT <= farT)) ok = false;
+            }
+        }
+        float mint = nearT, maxt = farT;
+        if (ok) {
+            float rayMinT = rays[i].mint;
+            if (rayMinT == PT_EPSILON) rayMinT *= smax(smax(smax(fabsf(o.x), fabsf(o.y)), fabsf(o.z)), PT_EPSILON);
+            if (rayMinT > mint) mint = rayMinT;
+            if (rays[i].maxt < maxt) maxt = rays[i].maxt;
+            ok = maxt > mint;
+        }
+        if (ok && !use_wide) {
+            for (size_t k = 0; k < nRecs; ++k) {
+                float tu, tv, tt;
+                if (waldIntersect(recs[3 * k], recs[3 * k + 1], recs[3 * k + 2], o, d, mint, maxt, tu, tv, tt) && winsTie(tt, pm_to_bits(recs[3 * k + 2].z), h.t, h.prim)) { maxt = tt; h.t = tt; h.u = tu; h.v = tv; h.prim = pm_to_bits(recs[3 * k + 2].z); }
+            }
+        } else if (ok) {
+            WideRay ray; wideRaySetup(ray, o, d, V3(slabRcp(d.x), slabRcp(d.y), slabRcp(d.z)), mint, maxt);
+            std::vector<uint2> stack;
+            uint32_t nSeq = 0;
+            auto note = [&](uint8_t what) { if (seq && nSeq + 1 < seq_stride) seq[i * seq_stride + nSeq++] = what; };
+            uint2 ng = make_uint2(0u, 0x80000000u), tg = make_uint2(0u, 0u);
+            for (;;) {
+                if (tg.y == 0u && (ng.y & 0xff000000u)) {
+                    const uint32_t bit = 31u - (uint32_t) __builtin_clz(ng.y);
+                    ng.y &= ~(1u << bit);
+                    if (ng.y & 0xff000000u) stack.push_back(ng);
+                    const uint32_t slot = (bit - 24u) ^ (ray.octinv4 & 7u);
+                    const uint32_t idx = ng.x + (uint32_t) __builtin_popcount(ng.y & ((1u << slot) - 1u) & 0xffu);
+                    if (idx >= nWNodes) throw std::runtime_error("wide BVH: child index out of range");
+                    const uint4 *g = wn + 5 * (size_t) idx;
+                    note(1);
+                    const uint32_t hitsMask = wideNodeHits(g[0], g[1], g[2], g[3], g[4], ray);
+                    ng = make_uint2(g[1].x, (hitsMask & 0xff000000u) | (g[0].w >> 24));
+                    tg = make_uint2(g[1].y, hitsMask & 0x00ffffffu);
+                }
+                if (tg.y) {
+                    const uint32_t bit = (uint32_t) __builtin_ctz(tg.y);
+                    tg.y &= tg.y - 1u;
+                    const size_t k = (size_t) tg.x + bit;
+                    if (k >= nRecs) throw std::runtime_error("wide BVH: triangle index out of range");
+                    note(2);
+                    float tu, tv, tt;
+                    if (waldIntersect(recs[3 * k], recs[3 * k + 1], recs[3 * k + 2], o, d, ray.mint, ray.maxt, tu, tv, tt) && winsTie(tt, pm_to_bits(recs[3 * k + 2].z), h.t, h.prim)) { ray.maxt = tt; h.t = tt; h.u = tu; h.v = tv; h.prim = pm_to_bits(recs[3 * k + 2].z); }
+                }
+                if (tg.y == 0u && !(ng.y & 0xff000000u)) {
+                    if (stack.empty()) break;
+                    ng = stack.back(); stack.pop_back();
+                }
+            }
+        }
+        hits[i] = h;
+    }
+}
+
+extern "C" {
+
 /* Closest-hit ray casts through the compressed wide BVH ON THE HOST: the tree of buildWide() walked with the node-step
    arithmetic of k_wide.h (wideNodeHits is __host__ __device__) and the Wald test of dv_scene.h.  Lets the CPU test-suite pin
    the builder's encoding (quantisation, slots, child / triangle indexing) and the group stack logic against the oracle
@@ -167,77 +242,64 @@ int phip_debug_host_trace_wide(const float *positions, uint32_t n_vertices, cons
             info->sah_cost = bvh.wSahCost; info->build_ms = bvh.buildMs;
         }
         if (use_wide && bvh.nWNodes == 0) return setErr(PHIP_ERR_INVALID, "the scene has no wide tree (a single leaf)");
-        DevScene S; memset(&S, 0, sizeof(S));
-        for (int a = 0; a < 3; ++a) { S.sceneMin[a] = bvh.sceneMin[a]; S.sceneMax[a] = bvh.sceneMax[a]; }
-        const float4 *recs = (const float4 *) (use_wide ? bvh.wtris.data() : bvh.tris.data());
-        const size_t nRecs = (use_wide ? bvh.wtris.size() : bvh.tris.size()) / 12;
-        const uint4 *wn = (const uint4 *) bvh.wnodes.data();
-        for (size_t i = 0; i < n_rays; ++i) {
-            const V3 o(rays[i].o[0], rays[i].o[1], rays[i].o[2]), d(rays[i].d[0], rays[i].d[1], rays[i].d[2]);
-            phip_hit h; h.t = INFINITY; h.u = h.v = 0; h.prim = PHIP_NO_HIT;
-            /* scene-box clip + adaptive epsilon, skdtree.cpp:112-142 (the host twin of clipToScene<false>) */
-            float nearT = -INFINITY, farT = INFINITY; bool ok = true;
-            const float oo[3] = { o.x, o.y, o.z }, dd[3] = { d.x, d.y, d.z };
-            for (int a = 0; a < 3 && ok; ++a) {
-                if (dd[a] == 0) { if (oo[a] < S.sceneMin[a] || oo[a] > S.sceneMax[a]) ok = false; }
-                else {
-                    const float rcp = 1.0f / dd[a];
-                    float t1 = (S.sceneMin[a] - oo[a]) * rcp, t2 = (S.sceneMax[a] - oo[a]) * rcp;
-                    if (t1 > t2) std::swap(t1, t2);
-                    nearT = smax(t1, nearT); farT = smin(t2, farT);
-                    if (!(nearT <= farT)) ok = false;
-                }
+        hostTraceRays(bvh.sceneMin, bvh.sceneMax, (const float4 *) (use_wide ? bvh.wtris.data() : bvh.tris.data()), (use_wide ? bvh.wtris.size() : bvh.tris.size()) / 12,
+                      (const uint4 *) bvh.wnodes.data(), bvh.nWNodes, use_wide, rays, n_rays, hits, seq, seq_stride);
+        return PHIP_OK;
+    } catch (const std::exception &e) { return setErr(PHIP_ERR_INVALID, e.what()); }
+}
+
+/* The refit of phip_scene_update ON THE HOST, sibling of phip_debug_host_trace_wide: the tree is built on positions_a (no camera), then refitted to positions_b and the
+   camera position camera3 (NULL: none) -- and, if positions_c is given, once more to positions_c -- by the __host__ __device__ functions the kernels of k_update.h run
+   (refit_hd.h), in their order; the rays are traced on the CPU twin of the wide traversal.  out_nodes (20 words per node), out_records (12 floats per record) and
+   out_rec_prim (the creation's primitive of every record) receive the refitted tree when they are given: info->n_nodes and info->n_triangle_refs are their sizes (call
+   once without them).  PHIP_ERR_UNSUPPORTED as phip_scene_update gives it. */
+int phip_debug_host_refit_trace_wide(const float *positions_a, const float *positions_b, const float *positions_c, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles,
+                                     const float *camera3, const phip_ray *rays, size_t n_rays, phip_hit *hits, phip_accel_info *info,
+                                     uint32_t *out_nodes, float *out_records, uint32_t *out_rec_prim, uint32_t *out_n_degenerate) {
+    try {
+        for (uint32_t i = 0; i < 3 * n_triangles; ++i) if (indices[i] >= n_vertices) return setErr(PHIP_ERR_INVALID, "index out of range");
+        HostBVH bvh; buildBVH(positions_a, indices, n_triangles, bvh);
+        if (bvh.nWNodes == 0) return setErr(PHIP_ERR_INVALID, "the scene has no wide tree");
+        const size_t nRecs = bvh.wtris.size() / 12;
+        std::vector<uint32_t> recPrim(nRecs), had(((size_t) n_triangles + 31) / 32 + 1, 0u);
+        for (size_t r = 0; r < nRecs; ++r) { memcpy(&recPrim[r], &bvh.wtris[12 * r + 10], 4); if (recPrim[r] < n_triangles) had[recPrim[r] >> 5] |= 1u << (recPrim[r] & 31u); }
+        std::vector<float4> ts((size_t) TRISHADE_FLOAT4S * n_triangles, make_float4(0, 0, 0, 0));
+        std::vector<float> nodeBox(6 * (size_t) bvh.nWNodes);
+        const float noCamera[3] = { 0, 0, 0 };
+        detail::RefitConsts K; memset(&K, 0, sizeof(K));
+        uint32_t nDegenerate = 0;
+        for (const float *pos : { positions_b, positions_c }) {
+            if (!pos) continue;
+            uint32_t grown = 0; nDegenerate = 0;
+            for (uint32_t i = 0; i < n_triangles; ++i) {            /* k_upd_check */
+                float rec[12];
+                const bool ok = detail::waldLoad(pos + 3 * (size_t) indices[3 * (size_t) i], pos + 3 * (size_t) indices[3 * (size_t) i + 1], pos + 3 * (size_t) indices[3 * (size_t) i + 2], i, rec);
+                const bool h = (had[i >> 5] >> (i & 31u)) & 1u;
+                grown += ok && !h; nDegenerate += !ok && h;
             }
-            float mint = nearT, maxt = farT;
-            if (ok) {
-                float rayMinT = rays[i].mint;
-                if (rayMinT == PT_EPSILON) rayMinT *= smax(smax(smax(fabsf(o.x), fabsf(o.y)), fabsf(o.z)), PT_EPSILON);
-                if (rayMinT > mint) mint = rayMinT;
-                if (rays[i].maxt < maxt) maxt = rays[i].maxt;
-                ok = maxt > mint;
-            }
-            if (ok && !use_wide) {
-                for (size_t k = 0; k < nRecs; ++k) {
-                    float tu, tv, tt;
-                    if (waldIntersect(recs[3 * k], recs[3 * k + 1], recs[3 * k + 2], o, d, mint, maxt, tu, tv, tt) && winsTie(tt, pm_to_bits(recs[3 * k + 2].z), h.t, h.prim)) { maxt = tt; h.t = tt; h.u = tu; h.v = tv; h.prim = pm_to_bits(recs[3 * k + 2].z); }
-                }
-            } else if (ok) {
-                WideRay ray; wideRaySetup(ray, o, d, V3(slabRcp(d.x), slabRcp(d.y), slabRcp(d.z)), mint, maxt);
-                std::vector<uint2> stack;
-                uint32_t nSeq = 0;
-                auto note = [&](uint8_t what) { if (seq && nSeq + 1 < seq_stride) seq[i * seq_stride + nSeq++] = what; };
-                uint2 ng = make_uint2(0u, 0x80000000u), tg = make_uint2(0u, 0u);
-                for (;;) {
-                    if (tg.y == 0u && (ng.y & 0xff000000u)) {
-                        const uint32_t bit = 31u - (uint32_t) __builtin_clz(ng.y);
-                        ng.y &= ~(1u << bit);
-                        if (ng.y & 0xff000000u) stack.push_back(ng);
-                        const uint32_t slot = (bit - 24u) ^ (ray.octinv4 & 7u);
-                        const uint32_t idx = ng.x + (uint32_t) __builtin_popcount(ng.y & ((1u << slot) - 1u) & 0xffu);
-                        if (idx >= bvh.nWNodes) throw std::runtime_error("wide BVH: child index out of range");
-                        const uint4 *g = wn + 5 * (size_t) idx;
-                        note(1);
-                        const uint32_t hitsMask = wideNodeHits(g[0], g[1], g[2], g[3], g[4], ray);
-                        ng = make_uint2(g[1].x, (hitsMask & 0xff000000u) | (g[0].w >> 24));
-                        tg = make_uint2(g[1].y, hitsMask & 0x00ffffffu);
-                    }
-                    if (tg.y) {
-                        const uint32_t bit = (uint32_t) __builtin_ctz(tg.y);
-                        tg.y &= tg.y - 1u;
-                        const size_t k = (size_t) tg.x + bit;
-                        if (k >= nRecs) throw std::runtime_error("wide BVH: triangle index out of range");
-                        note(2);
-                        float tu, tv, tt;
-                        if (waldIntersect(recs[3 * k], recs[3 * k + 1], recs[3 * k + 2], o, d, ray.mint, ray.maxt, tu, tv, tt) && winsTie(tt, pm_to_bits(recs[3 * k + 2].z), h.t, h.prim)) { ray.maxt = tt; h.t = tt; h.u = tu; h.v = tv; h.prim = pm_to_bits(recs[3 * k + 2].z); }
-                    }
-                    if (tg.y == 0u && !(ng.y & 0xff000000u)) {
-                        if (stack.empty()) break;
-                        ng = stack.back(); stack.pop_back();
-                    }
-                }
-            }
-            hits[i] = h;
+            if (grown) return setErr(PHIP_ERR_UNSUPPORTED, std::to_string(grown) + " triangles that were degenerate at creation are not degenerate now");
+            for (uint32_t i = 0; i < n_triangles; ++i) detail::refitShadeRecord(pos, nullptr, indices, i, ts.data() + (size_t) TRISHADE_FLOAT4S * i);      /* k_upd_shade */
+            float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
+            for (uint32_t i = 0; i < n_triangles; ++i) detail::growByTriangle(ts.data(), TRISHADE_FLOAT4S, i, mn, mx);                                     /* k_upd_box */
+            detail::refitConstsOf(mn, mx, camera3 ? camera3 : noCamera, K);
+            for (size_t r = 0; r < nRecs; ++r) detail::refitWaldRecord(ts.data(), TRISHADE_FLOAT4S, recPrim[r], (float4 *) bvh.wtris.data() + 3 * r);     /* k_upd_wald */
+            double cost = 0;
+            for (size_t l = bvh.wLevels.size(); l-- > 1; )                                                                                                 /* k_upd_refit_level */
+                for (uint32_t idx = bvh.wLevels[l - 1]; idx < bvh.wLevels[l]; ++idx)
+                    cost += detail::refitWideNode((uint4 *) bvh.wnodes.data() + 5 * (size_t) idx, idx, ts.data(), TRISHADE_FLOAT4S, recPrim.data(), K, nodeBox.data());
+            bvh.wSahCost = (float) (cost + 1.0);
+            for (int a = 0; a < 3; ++a) { bvh.sceneMin[a] = K.sceneMin[a]; bvh.sceneMax[a] = K.sceneMax[a]; }
         }
+        if (info) {
+            memset(info, 0, sizeof(*info));
+            info->n_nodes = bvh.nWNodes; info->max_depth = bvh.wMaxDepth; info->n_triangle_refs = bvh.nWTris; info->node_bytes = 80; info->triangle_bytes = 48;
+            info->sah_cost = bvh.wSahCost; info->build_ms = bvh.buildMs;
+        }
+        if (out_nodes) memcpy(out_nodes, bvh.wnodes.data(), (size_t) bvh.nWNodes * 80);
+        if (out_records) memcpy(out_records, bvh.wtris.data(), nRecs * 48);
+        if (out_rec_prim) memcpy(out_rec_prim, recPrim.data(), nRecs * 4);
+        if (out_n_degenerate) *out_n_degenerate = nDegenerate;
+        hostTraceRays(bvh.sceneMin, bvh.sceneMax, (const float4 *) bvh.wtris.data(), nRecs, (const uint4 *) bvh.wnodes.data(), bvh.nWNodes, 1, rays, n_rays, hits, nullptr, 0);
         return PHIP_OK;
     } catch (const std::exception &e) { return setErr(PHIP_ERR_INVALID, e.what()); }
 }

@@ -86,6 +86,47 @@ class Scene:
         if rc != 0:
             raise _ffi.PhipError(rc, "phip_scene_replicate")
 
+    def update(self, positions=None, normals=None, camera=None, stream=None):
+        """New vertex positions / normals / camera on the scene as created: a refit of the acceleration structure, not a rebuild (phip_scene_update).
+        positions, normals: numpy arrays (host memory), or float32 contiguous torch tensors on the scene's device, whose data_ptr() the library reads in place
+        (`stream`: the stream their producer ran on -- a torch.cuda.Stream or a raw handle; the update is ordered after it); shape n_vertices x 3 of the scene as
+        created.  camera: a phip_camera.  Returns the phip_update_info (update_ms, kernel_ms, sah_cost, n_degenerate); PhipError on a refusal, the scene unchanged."""
+        n = self.desc.n_vertices
+        u = A.phip_update_desc()
+        keep, on_device = [], []
+        for name, a in (("positions", positions), ("normals", normals)):
+            if a is None:
+                continue
+            if isinstance(a, np.ndarray) or not hasattr(a, "data_ptr"):
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.size != 3 * n:
+                    raise ValueError("%s: expected %d x 3 values" % (name, n))
+                setattr(u, name, a.ctypes.data)
+                on_device.append(False)
+            else:
+                import torch
+                if a.dtype != torch.float32 or not a.is_contiguous() or tuple(a.shape) != (n, 3):
+                    raise ValueError("%s: expected a contiguous float32 tensor of shape (%d, 3)" % (name, n))
+                if not a.is_cuda or (a.device.index or 0) != self.device:
+                    raise ValueError("%s: the tensor is not on the scene's device" % name)
+                setattr(u, name, a.data_ptr())
+                on_device.append(True)
+            keep.append(a)
+        if len(set(on_device)) > 1:
+            raise ValueError("positions and normals must both be host arrays or both be device tensors")
+        u.device_pointers = 1 if on_device and on_device[0] else 0
+        if stream is not None:
+            u.stream = getattr(stream, "cuda_stream", stream)
+        if camera is not None:
+            u.camera = C.pointer(camera)
+        info = A.phip_update_info()
+        rc = self._L.phip_scene_update(self._h, C.byref(u), C.byref(info))
+        if rc != 0:
+            raise _ffi.PhipError(rc, "phip_scene_update")
+        if camera is not None:
+            self.desc.camera = camera
+        return info
+
     def film_to_host(self, d_ptr, host_ptr):
         """a device-resident frame (render_device's output, e.g. after an RCCL reduce) to host memory, as phip_render delivers it"""
         rc = self._L.phip_film_to_host(self._h, C.c_void_p(d_ptr), C.c_void_p(host_ptr))

@@ -286,6 +286,18 @@ class SceneBuilder:
         d._keep = (pos, nrm, idx, shapes, mats, ems, env, tcs, texs, [t["levels"] for t in self.textures])   # keep the buffers alive with the struct
         return d
 
+    # ---- a second frame of the same topology (Scene.update) ---------------------------------
+    def flat_positions(self):
+        """the vertex positions of every mesh in the order of desc(): move a mesh (`sb.positions[shape_id]`) or the camera (`perspective`), then pass this to
+        Scene.update -- or build desc() again for the scene a fresh creation makes of the same arrays"""
+        return np.ascontiguousarray(np.concatenate(self.positions), dtype=np.float32) if self.positions else np.zeros((0, 3), np.float32)
+
+    def flat_normals(self):
+        """the vertex normals in the order of desc() (zeros for meshes without), or None if no mesh has any"""
+        if not any(n is not None for n in self.normals):
+            return None
+        return np.ascontiguousarray(np.concatenate([n if n is not None else np.zeros_like(p) for n, p in zip(self.normals, self.positions)]), dtype=np.float32)
+
     @property
     def n_triangles(self):
         return sum(len(t) for t in self.indices)
