@@ -408,7 +408,8 @@ int  phip_scene_replicate(phip_scene *scene, const int32_t *devices, int32_t n_d
    (the count in phip_last_error) when a triangle that was degenerate at creation -- it got no Wald record -- is not degenerate now: a fresh build would give it a
    record, a refit cannot.  The converse is served: a triangle that collapses gets the never-hit record and comes back with a later update.  PHIP_ERR_DEVICE without
    a GPU: there is no CPU fallback.  How much slower a refitted tree traverses than a fresh one depends on how far the vertices went (DESIGN.md 3.12 has
-   measurements); the library fixes no threshold -- sah_cost is there for the caller to decide when to create the scene again. */
+   measurements); the library fixes no threshold -- sah_cost is there for the caller to decide when to call phip_scene_rebuild (below), which builds a new tree on
+   the device in place of destroying the scene and creating it again. */
 typedef struct phip_update_desc {
     const float *positions;      /* 3 * n_vertices of the scene as created, world space; NULL = unchanged */
     const float *normals;        /* 3 * n_vertices; NULL = unchanged; PHIP_ERR_INVALID if the scene was created without normals */
@@ -423,6 +424,24 @@ typedef struct phip_update_info {
     uint32_t n_degenerate;       /* triangles whose Wald record is the never-hit record after this update */
 } phip_update_info;
 int  phip_scene_update(phip_scene *scene, const phip_update_desc *update, phip_update_info *out_info /* may be NULL */);
+
+/* phip_scene_update with a NEW topology of the 8-wide tree, built on the device from the positions where they are: the remedy for a tree that a
+   refit has made slow (the builder's spatial splits on scenes of 4096 triangles or more do not survive moving vertices), without the host builder and without
+   uploading materials, textures and the environment map again.  The same sentence holds after the call, with the same list of bits: every entry point behaves as if
+   the scene had been created from the original descriptor with these positions, normals and camera.  What differs from phip_scene_update:
+     * n_nodes, max_depth, n_leaves and n_triangle_refs of phip_scene_accel_info may change (the new tree has one record per non-degenerate triangle and no split
+       references), sah_cost is buildWide's formula on the new tree, and what the creation derives from those counts -- the node cache, fused_traversal with the
+       PHIP_FUSED_WIDE_MAX_NODES gate -- is derived again;
+     * a triangle that was degenerate at creation and is not degenerate now gets its record: no PHIP_ERR_UNSUPPORTED for it, and later phip_scene_update calls start
+       from the new state.  n_degenerate is 0: a degenerate triangle has no record in the new tree;
+     * one refusal of its own, PHIP_ERR_UNSUPPORTED: the new tree is deeper than the traversal stacks allow (52 levels).  The tree is a radix tree over 30-bit Morton
+       keys, so it has at most 31 + ceil(log2 m) levels, m being the largest number of triangles whose centres share one cell of a 1024^3 grid over the scene box:
+       the refusal needs more than two million triangles in one cell.
+   update may be NULL (or all-zero): the scene's current vertices and camera, e.g. after a series of phip_scene_update calls.  Locking, validation before anything is
+   written (on any error the scene is unchanged: the call builds into fresh buffers and swaps them in at the end), the dropped replicas and the other error codes are
+   phip_scene_update's.  A scene that is not on the 8-wide tree alone -- at most 64 Wald records: it has the packed leaf table, no split references, nothing to
+   gain -- is served by phip_scene_update itself, with that call's refusals (the degenerate-at-creation triangle included) and its unchanged counts. */
+int  phip_scene_rebuild(phip_scene *scene, const phip_update_desc *update /* may be NULL */, phip_update_info *out_info /* may be NULL */);
 
 /* Thread-safe and sticky, like Scheduler::cancel on a process (src/libcore/sched.cpp): a running phip_render returns
    PHIP_ERR_CANCELLED; a request that arrives before the render starts cancels that render.  The flag is consumed by the

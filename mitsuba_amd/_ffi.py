@@ -49,6 +49,8 @@ UNITS = [("phip_shade.hip", ["-DSHADE_FEAT=%d" % f, "-DSHADE_PART=%d" % q], "phi
 UNITS += [("phip_shade_w.hip", MEGA_FLAGS + ["-DSHADE_FEAT=%d" % f], "phip_tracew%d.o" % f) for f in SHADE_FEATS]
 # phip_update.hip (the refit kernels of phip_scene_update, k_update.h): one small object, appended likewise
 UNITS += [("phip_update.hip", [], "phip_update.o")]
+# phip_rebuild.hip (the device build of phip_scene_rebuild, k_rebuild.h, with rocPRIM's sort and scan): one object, appended likewise
+UNITS += [("phip_rebuild.hip", [], "phip_rebuild.o")]
 
 
 DEBUG_UNIT = ("phip.hip", ["-DPHIP_DEBUG_HOOKS=1"], "phip_dbg.o")
@@ -128,6 +130,8 @@ def _build_locked(sid, out_lib, verbose):
             return 2.0 * feat_cost.get(int(re.match(r"phip_tracew(\d+)", name).group(1)), 20.0)
         if name.startswith("phip_update"):
             return 3.0
+        if name.startswith("phip_rebuild"):
+            return 13.0
         return 31.0 if name.startswith("phip_mega") else 14.0
     cmds.sort(key=cost, reverse=True)
     import concurrent.futures
@@ -164,7 +168,8 @@ TEST_VARIANTS = {"fault": "-DMEGA_MB_FAULT=1",       # waves of fused launches r
                  "cap32": "-DWP_CAP=32u",            # 32-entry task stacks: nearly every push of a big scene spills to memory
                  "overflow": "-DWP_CAP=64u -DWP_SPILL_CAP=64u"}      # 128-entry task stacks, half of them spilled: the tree-in-memory scenes outgrow them -- the wave stops, the pass is re-rendered
 # sources whose objects a variant takes from the product build: its flags do not concern them (the task stacks are k_mega's and k_shade_trace_w's)
-VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip phip_update.hip", "cap32": "phip_shade.hip phip_update.hip", "overflow": "phip_shade.hip phip_update.hip"}
+VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip phip_update.hip phip_rebuild.hip", "cap32": "phip_shade.hip phip_update.hip phip_rebuild.hip",
+                 "overflow": "phip_shade.hip phip_update.hip phip_rebuild.hip"}
 
 
 def build_test_variant(tag):
@@ -209,6 +214,7 @@ def lib():
     L.phip_cancel.argtypes = [C.c_void_p]
     L.phip_scene_replicate.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
     L.phip_scene_update.argtypes = [C.c_void_p, C.POINTER(A.phip_update_desc), C.POINTER(A.phip_update_info)]
+    L.phip_scene_rebuild.argtypes = [C.c_void_p, C.POINTER(A.phip_update_desc), C.POINTER(A.phip_update_info)]
     L.phip_develop.argtypes = [fp, C.c_size_t, fp]
     L.phip_scene_accel_info.argtypes = [C.c_void_p, C.POINTER(A.phip_accel_info)]
     L.phip_gaussian_filter.argtypes = [C.c_float, fp, fp]
@@ -262,6 +268,7 @@ def debug_lib():
     L.phip_debug_host_trace_wide.argtypes = [fp, u32, C.POINTER(C.c_uint32), u32, C.POINTER(A.phip_ray), C.c_size_t, C.POINTER(A.phip_hit), C.c_int, C.POINTER(A.phip_accel_info), u8p, u32]
     L.phip_debug_host_refit_trace_wide.argtypes = [fp, fp, fp, u32, C.POINTER(C.c_uint32), u32, fp, C.POINTER(A.phip_ray), C.c_size_t, C.POINTER(A.phip_hit),
                                                    C.POINTER(A.phip_accel_info), C.POINTER(C.c_uint32), fp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.phip_debug_host_rebuild_trace_wide.argtypes = L.phip_debug_host_refit_trace_wide.argtypes
     L.phip_debug_fmath.argtypes = [C.c_int, C.c_int, C.c_size_t, fp, fp, fp]
     L.phip_debug_selected_kernel.argtypes = [C.c_int] * 7; L.phip_debug_selected_kernel.restype = C.c_char_p
     _debug = L

@@ -645,23 +645,10 @@ inline void buildWide(HostBVH &out, int32_t root2, const detail::Box &rootBox, C
         for (const WChild &w : wc) nb.grow(w.c.box.mn, w.c.box.mx);
         detail::WideGrid grid; detail::wideGridOf(nb.mn, nb.mx, grid);
         const float *p = grid.p; const uint32_t *e8 = grid.e8;
-        /* slot assignment by octant direction (greedy on the dot product) */
-        const float cen[3] = { 0.5f * (nb.mn[0] + nb.mx[0]), 0.5f * (nb.mn[1] + nb.mx[1]), 0.5f * (nb.mn[2] + nb.mx[2]) };
-        int slotOf[8]; bool slotUsed[8] = { false }, childDone[8] = { false };
-        for (size_t k = 0; k < wc.size(); ++k) {
-            float bestV = -INFINITY; int bc = -1, bs = -1;
-            for (size_t c = 0; c < wc.size(); ++c) {
-                if (childDone[c]) continue;
-                const float d[3] = { 0.5f * (wc[c].c.box.mn[0] + wc[c].c.box.mx[0]) - cen[0], 0.5f * (wc[c].c.box.mn[1] + wc[c].c.box.mx[1]) - cen[1],
-                                     0.5f * (wc[c].c.box.mn[2] + wc[c].c.box.mx[2]) - cen[2] };
-                for (int sl = 0; sl < 8; ++sl) {
-                    if (slotUsed[sl]) continue;
-                    const float v = ((sl & 1) ? d[0] : -d[0]) + ((sl & 2) ? d[1] : -d[1]) + ((sl & 4) ? d[2] : -d[2]);
-                    if (v > bestV) { bestV = v; bc = (int) c; bs = sl; }
-                }
-            }
-            childDone[bc] = true; slotUsed[bs] = true; slotOf[bc] = bs;
-        }
+        /* slot assignment by octant direction (greedy on the dot product): detail::wideAssignSlots, refit_hd.h -- the collapse of phip_scene_rebuild calls it too */
+        float cmn[8][3], cmx[8][3]; int slotOf[8];
+        for (size_t c = 0; c < wc.size(); ++c) for (int a = 0; a < 3; ++a) { cmn[c][a] = wc[c].c.box.mn[a]; cmx[c][a] = wc[c].c.box.mx[a]; }
+        detail::wideAssignSlots(cmn, cmx, (int) wc.size(), nb.mn, nb.mx, slotOf);
         int childAt[8]; for (int sl = 0; sl < 8; ++sl) childAt[sl] = -1;
         for (size_t c = 0; c < wc.size(); ++c) childAt[slotOf[c]] = (int) c;
         /* emit */

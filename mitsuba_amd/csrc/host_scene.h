@@ -17,6 +17,7 @@ template <typename T> struct DevBuf {
     void upload(const T *src, size_t count) { alloc(count); if (count) HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice)); }
     void cloneFrom(const DevBuf<T> &src) { alloc(src.n); if (src.n) HIP_TRY(hipMemcpy(p, src.p, src.n * sizeof(T), hipMemcpyDeviceToDevice)); }   /* UVA: also across GPUs (xGMI) */
     void release() { if (p) { (void) hipFree(p); p = nullptr; } n = 0; cap = 0; }
+    void swapWith(DevBuf<T> &o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(cap, o.cap); }
     ~DevBuf() { release(); }
 };
 
@@ -173,6 +174,7 @@ struct SceneUpdateState {
     std::vector<uint32_t> indices;                   /* 3 x nTriangles */
     std::vector<uint32_t> wRecPrim, recPrim;         /* the primitive of every Wald record of wtris / tris (0xFFFFFFFF: a leaf's never-hit placeholder): the side table that lets a collapsed triangle come back */
     std::vector<uint32_t> hadRecord;                 /* one bit per triangle: it got a Wald record (degenerate triangles are dropped by makeLeaf: a refit cannot give them one) */
+    std::vector<uint8_t> triClass;                   /* the shade class of every triangle (tagShadeClasses): phip_scene_rebuild writes it into the records of its new tree */
     std::vector<uint32_t> wLevels;                   /* HostBVH::wLevels */
     std::vector<int32_t> leafRefs;                   /* the references of the packed leaf table's leaves, in its order */
     struct EmitterMesh { uint32_t emitter, firstTri, nTris, firstVertex, endVertex; };      /* area emitters: their triangles and the vertex range those use */
@@ -183,6 +185,12 @@ struct SceneUpdateState {
     bool onDevice = false;
     DevBuf<uint32_t> dIndices, dWRecPrim, dRecPrim, dHadRecord, dCounters; DevBuf<int32_t> dLeafRefs;
     DevBuf<float> dPositions, dNormals, dNodeBox, dSahTerm, dPartials; DevBuf<detail::RefitConsts> dConsts;
+    /* phip_scene_rebuild (host_rebuild.h): from the first rebuild on the host vectors wRecPrim, hadRecord and wLevels above are what they were for -- the source of the
+       first upload and the counts -- and no more: wRecPrim keeps its size up to date, not its content.  The scratch of the pipeline, kept between calls: */
+    struct RebuildScratch {
+        DevBuf<uint32_t> keys, tris, sortedKeys, sortedTris, range, parent, arrived; DevBuf<int32_t> child, items, slotRef; DevBuf<float> box;
+        DevBuf<unsigned long long> scanIn, scanOut; DevBuf<unsigned char> temp; DevBuf<uint8_t> triClass;
+    } rb;
 };
 
 struct phip_scene {
@@ -335,6 +343,21 @@ static void environmentSphereOf(const float *sceneMin, const float *sceneMax, ui
     D.envRadius = std::max(PT_EPSILON, radius * 1.5f);
 }
 
+/* What follows from the counts of the 8-wide tree, stated once for the creation (chooseTraversal, chooseDevicePaths) and for phip_scene_rebuild, whose tree has other counts:
+   whether its depth fits the traversal stacks (one group per level) ... */
+static bool wideDepthFits(uint32_t wMaxDepth) { return (int) wMaxDepth + 2 <= WIDE_STACK_LDS + SPILL_DEPTH / 2; }
+/* ... the top of the tree the ray kernels stage in LDS (its nodes are in breadth-first order), and the kernels that walk it from memory beside the wavefront's: fusedWide
+   (round 6: k_mega on a tree that does not fit LDS, k_wide_wave.h -- every scene on the 8-wide tree whose emitter table fits LDS and that needs none of the feature sets k_mega
+   is not compiled with: bitmap textures, an environment emitter) and wideTrace (k_shade_trace_w).  Reads the DevScene's constants (sceneConstants) and the tree's statistics */
+static void wideTreePaths(phip_scene *sc, DevScene &D) {
+    const HostBVH &bvh = sc->bvh;
+    D.wideNodeCache = std::min<uint32_t>(bvh.nWNodes, WIDE_NODE_CACHE_MAX);
+    const bool addressable = bvh.nWTris < WP_TRI_MAX;
+    sc->fusedWide = (sc->wideOnly && !sc->hasTextures && D.envEmitter < 0 && sc->triShadeStride == TRISHADE_FLOAT4S && D.emitterTabSize <= EMITTER_LDS_FLOATS && addressable)
+                  ? (D.nMaterials <= MATERIAL_LDS_MAX ? 4 : 5) : 0;
+    sc->wideTrace = sc->wideOnly && addressable;
+}
+
 /* One phip_scene_create: what the stages of buildScene hand to each other.  Every stage up to chooseDevicePaths works on host arrays and calls no HIP
    function; uploadScene is the only one that allocates or copies scene buffers. */
 struct SceneBuild {
@@ -348,6 +371,7 @@ struct SceneBuild {
     std::vector<float4> envTexels; DevMipLevels envLevels; std::vector<float> envCdfRows, envCdfCols, envRowWeights;
     std::vector<float4> flat;                                       /* packed leaf table (flatMode != 0) */
     bool recordsInLds = false, fitsLdsBase = false;                 /* ldsPlan -> flatLeafTable, chooseDevicePaths */
+    std::vector<uint8_t> triClass;                                  /* tagShadeClasses -> keepForUpdate */
 
     SceneBuild(phip_scene *sc, const phip_scene_desc &d) : sc(sc), sd(*sc->devs[0]), d(d), D(sd.dev) { memset(&D, 0, sizeof(D)); }
 
@@ -523,7 +547,7 @@ struct SceneBuild {
        of the two sides of a two-sided surface; k_rays_w passes it on in the hit record and k_shade deals its lanes by it (k_pool.h) */
     void tagShadeClasses() {
         auto classOf = [&](uint32_t leaf) { const int t = mats[leaf].type; return t == PHIP_BSDF_ROUGHCONDUCTOR ? 1u : (t == PHIP_BSDF_DIELECTRIC ? 2u : 0u); };
-        std::vector<uint8_t> cls(d.n_triangles);
+        std::vector<uint8_t> &cls = triClass; cls.assign(d.n_triangles, 0);
         for (uint32_t i = 0; i < d.n_triangles; ++i) {
             const float4 *r = ts.data() + (size_t) stride * i;          /* front and back material: shadingRecords */
             const uint32_t a = classOf(pm_to_bits(r[0].w)), b = classOf(pm_to_bits(r[1].w));
@@ -550,7 +574,7 @@ struct SceneBuild {
         /* ... and, round 6, EVERY scene has the wide tree on the device: the ray kernels of the wavefront path (k_rays_w) and phip_trace (k_raycast_w) walk nothing else.
            The LDS-resident scenes keep their records in the binary tree's leaf order and the packed leaf table for k_mega / k_shade_trace beside it */
         /* the stack of the wide tree: one group per level */
-        if ((int) sc->bvh.wMaxDepth + 2 > WIDE_STACK_LDS + SPILL_DEPTH / 2) throw std::runtime_error("wide BVH too deep for the traversal stack");
+        if (!wideDepthFits(sc->bvh.wMaxDepth)) throw std::runtime_error("wide BVH too deep for the traversal stack");
     }
 
     /* packed emitter table (dv_scene.h: EmitterTab) */
@@ -684,7 +708,6 @@ struct SceneBuild {
            emitter, which k_shade_trace serves on the same table: k_shade_trace.h.  A scene that is ONE leaf has no leaf list, bvh.h: the ray kernels serve it) */
         recordsInLds = !sc->wideOnly && !bvh.leaves.empty() && bvh.tris.size() / 12 <= TRI_CACHE_MAX;
         D.triCache = recordsInLds ? (uint32_t) (bvh.tris.size() / 12) : 0u;
-        D.wideNodeCache = std::min<uint32_t>(bvh.nWNodes, WIDE_NODE_CACHE_MAX);
         D.preclip = 1u;                          /* k_rays_w traverses rays the shading kernels have clipped (k_clip.h) */
         /* the fused kernel's LDS plan (k_mega.h): the leaf table, every Wald and shading record, the emitter table and the materials in LDS (phip_mega.hip); leaf BSDF
            models: any (round 5) */
@@ -742,10 +765,7 @@ struct SceneBuild {
         sc->fitsLds = fitsLdsBase;                              /* (implies the packed leaf table: recordsInLds) */
         /* round 6: the fused kernel on a tree that does not fit LDS (k_wide_wave.h) -- every scene on the 8-wide tree whose emitter table fits LDS and that needs none of the
            feature sets k_mega is not compiled with (bitmap textures, an environment emitter) */
-        sc->fusedWide = (sc->wideOnly && !sc->hasTextures && envEmitter < 0 && stride == TRISHADE_FLOAT4S && tab.size() <= EMITTER_LDS_FLOATS
-                         && sc->bvh.wtris.size() / 12 < WP_TRI_MAX)
-                      ? (mats.size() <= MATERIAL_LDS_MAX ? 4 : 5) : 0;
-        sc->wideTrace = sc->wideOnly && sc->bvh.wtris.size() / 12 < WP_TRI_MAX;
+        wideTreePaths(sc, D);
         const bool traceable = D.flatMode >= 2 && tab.size() <= EMITTER_LDS_FLOATS && mats.size() <= MATERIAL_LDS_MAX;
         sc->flatTrace = !sc->fitsLds && traceable; sc->flatTraceToo = sc->fitsLds && traceable;
         /* k_mega deals the Wald tests of the packed table over the wave through LDS buffers at the front of its dynamic LDS
@@ -775,7 +795,7 @@ struct SceneBuild {
         };
         prims(bvh.wtris, U.wRecPrim);
         if (!sc->wideOnly) prims(bvh.tris, U.recPrim);
-        U.wLevels = bvh.wLevels;
+        U.wLevels = bvh.wLevels; U.triClass = triClass;
         if (!flat.empty()) for (const HostBVH::LeafBox &leaf : bvh.leaves) U.leafRefs.push_back(leaf.ref);
         for (uint32_t i = 0; i < d.n_emitters; ++i) {
             if (ems[i].shape == 0xFFFFFFFFu) continue;

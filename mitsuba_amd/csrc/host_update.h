@@ -6,10 +6,14 @@
  * refitted boxes are conservative, so every entry point gives the bits it gives on a scene created from the new arrays.
  * Order: validate (the check kernel's three counters and the emitter meshes' areas are read BEFORE anything is written: on an error the scene is what it was),
  * then shading records, scene box, Wald records, the wide tree level by level from the deepest, the packed leaf table, then the host stages.
+ * phip_scene_rebuild is the same call with one more step (rebuild = true; scenes on the 8-wide tree only): behind the scene box a new topology is built on the
+ * device (host_rebuild.h), the Wald and refit passes run on IT, and everything the call writes goes to fresh buffers that are swapped in at the end -- the
+ * depth of the new tree is known only then, and a refusal has to leave the scene unchanged.
  * Host code only; included by phip.hip alone, after host_scene.h.  The caller holds the scene's render lock.
  */
 #pragma once
 #include "host_scene.h"
+#include "host_rebuild.h"
 
 /* the creation's side tables on the device, the scratch of the passes: made by a scene's first update */
 static void updateDeviceTables(phip_scene *sc) {
@@ -30,14 +34,15 @@ static bool onSceneDevice(const void *p, int device) {
     return attr.type == hipMemoryTypeDevice && attr.device == device;
 }
 
-static int updateScene(phip_scene *sc, const phip_update_desc &u, phip_update_info *info) {
+static int updateScene(phip_scene *sc, const phip_update_desc &u, phip_update_info *info, bool rebuild = false) {
     const auto t0 = std::chrono::steady_clock::now();
+    const std::string who = rebuild ? "phip_scene_rebuild: " : "phip_scene_update: ";
     SceneUpdateState &U = sc->upd;
     SceneDev &sd = *sc->devs[0];
     DevScene &D = sd.dev;
-    if (u.normals && !U.hasNormals) return setErr(PHIP_ERR_INVALID, "phip_scene_update: normals for a scene that was created without normals");
+    if (u.normals && !U.hasNormals) return setErr(PHIP_ERR_INVALID, who + "normals for a scene that was created without normals");
     const phip_camera cam = u.camera ? *u.camera : sc->descCopy.camera;
-    for (int i = 0; i < 16; ++i) if (!std::isfinite(cam.to_world[i])) return setErr(PHIP_ERR_INVALID, "phip_scene_update: non-finite camera transform");
+    for (int i = 0; i < 16; ++i) if (!std::isfinite(cam.to_world[i])) return setErr(PHIP_ERR_INVALID, who + "non-finite camera transform");
     HIP_TRY(hipSetDevice(sd.device));
     HIP_TRY(hipDeviceSynchronize());          /* (a render on a caller's stream has been waited for by its call; this costs nothing then) */
     const bool newVertices = (u.positions || u.normals) && U.nTriangles > 0;
@@ -46,7 +51,7 @@ static int updateScene(phip_scene *sc, const phip_update_desc &u, phip_update_in
         updateDeviceTables(sc);
         if (u.device_pointers) {
             if ((u.positions && !onSceneDevice(u.positions, sd.device)) || (u.normals && !onSceneDevice(u.normals, sd.device)))
-                return setErr(PHIP_ERR_INVALID, "phip_scene_update: device_pointers = 1, but positions / normals are not device memory of the scene's device");
+                return setErr(PHIP_ERR_INVALID, who + "device_pointers = 1, but positions / normals are not device memory of the scene's device");
             HIP_TRY(hipStreamSynchronize((hipStream_t) u.stream));           /* ordered after the caller's producer */
             A.positions = u.positions; A.normals = u.normals;
         } else {
@@ -77,8 +82,8 @@ static int updateScene(phip_scene *sc, const phip_update_desc &u, phip_update_in
         HIP_TRY(hipEventRecord(e1, 0));
         HIP_TRY(hipMemcpy(counters, U.dCounters.p, sizeof(counters), hipMemcpyDeviceToHost));
         HIP_TRY(hipGetLastError());
-        if (counters[0]) return setErr(PHIP_ERR_INVALID, "phip_scene_update: " + std::to_string(counters[0]) + " vertices with a non-finite position or normal");
-        if (counters[1]) return setErr(PHIP_ERR_UNSUPPORTED, "phip_scene_update: " + std::to_string(counters[1]) + " triangles that were degenerate when the scene was created are not "
+        if (counters[0]) return setErr(PHIP_ERR_INVALID, who + std::to_string(counters[0]) + " vertices with a non-finite position or normal");
+        if (counters[1] && !rebuild) return setErr(PHIP_ERR_UNSUPPORTED, who + std::to_string(counters[1]) + " triangles that were degenerate when the scene was created are not "
                                        "degenerate now: they have no Wald record, and a refit cannot give them one (create the scene again)");
     } else HIP_TRY(hipEventRecord(e1, 0));
     if (u.positions && U.nTriangles > 0 && !U.emitterMeshes.empty()) {
@@ -91,22 +96,31 @@ static int updateScene(phip_scene *sc, const phip_update_desc &u, phip_update_in
         }
         try {
             for (size_t i = 0; i < U.emitterMeshes.size(); ++i) invArea[i] = areaCdfOf(hostPos, U.indices.data(), U.emitterMeshes[i].firstTri, U.emitterMeshes[i].nTris, cdfs[i]);
-        } catch (const std::exception &e) { return setErr(PHIP_ERR_INVALID, std::string("phip_scene_update: ") + e.what()); }
+        } catch (const std::exception &e) { return setErr(PHIP_ERR_INVALID, who + e.what()); }
     }
 
-    /* ---- mutate ---- */
+    /* ---- mutate (a rebuild: into `fresh`, the scene's own buffers are read only until the commit below) ---- */
     HIP_TRY(hipEventRecord(e2, 0));
+    RebuildFresh fresh;
+    float4 *wtris = sd.wtris.p; const uint32_t *wRecPrim = U.dWRecPrim.p; uint32_t nWRecs = (uint32_t) U.wRecPrim.size();
+    const std::vector<uint32_t> *levels = &U.wLevels;
     if (U.nTriangles > 0) {
+        if (rebuild && newVertices) { fresh.triShade.cloneFrom(sd.triShade); A.triShade = fresh.triShade.p; }
         if (newVertices) hipLaunchKernelGGL(K.shade, dim3(triBlocks), dim3(UPD_BLOCK), 0, 0, A);
         const unsigned boxBlocks = std::min(256u, triBlocks);
         hipLaunchKernelGGL(K.box, dim3(boxBlocks), dim3(UPD_BLOCK), 0, 0, A);
         hipLaunchKernelGGL(K.boxFinal, dim3(1), dim3(UPD_BLOCK), 0, 0, A, boxBlocks);
-        if (u.positions) {
-            if (!U.wRecPrim.empty()) hipLaunchKernelGGL(K.wald, dim3((unsigned) ((U.wRecPrim.size() + UPD_BLOCK - 1) / UPD_BLOCK)), dim3(UPD_BLOCK), 0, 0, A, sd.wtris.p, (const uint32_t *) U.dWRecPrim.p, (uint32_t) U.wRecPrim.size());
+        if (rebuild) {
+            const int rc = rebuildTopology(sc, A, fresh);
+            if (rc != PHIP_OK) return rc;
+            wtris = fresh.wtris.p; wRecPrim = fresh.wRecPrim.p; nWRecs = fresh.nRecs; levels = &fresh.wLevels;
+        }
+        if (u.positions || rebuild) {
+            if (nWRecs) hipLaunchKernelGGL(K.wald, dim3((nWRecs + UPD_BLOCK - 1) / UPD_BLOCK), dim3(UPD_BLOCK), 0, 0, A, wtris, wRecPrim, nWRecs);
             if (!U.recPrim.empty()) hipLaunchKernelGGL(K.wald, dim3((unsigned) ((U.recPrim.size() + UPD_BLOCK - 1) / UPD_BLOCK)), dim3(UPD_BLOCK), 0, 0, A, sd.tris.p, (const uint32_t *) U.dRecPrim.p, (uint32_t) U.recPrim.size());
         }
-        for (size_t l = U.wLevels.size(); l-- > 1; ) {          /* level l - 1 = nodes wLevels[l - 1] .. wLevels[l]: the deepest first */
-            const uint32_t first = U.wLevels[l - 1], count = U.wLevels[l] - first;
+        for (size_t l = levels->size(); l-- > 1; ) {          /* level l - 1 = nodes wLevels[l - 1] .. wLevels[l]: the deepest first */
+            const uint32_t first = (*levels)[l - 1], count = (*levels)[l] - first;
             if (count) hipLaunchKernelGGL(K.refitLevel, dim3((count + UPD_BLOCK - 1) / UPD_BLOCK), dim3(UPD_BLOCK), 0, 0, A, first, count);
         }
         if (A.nFlatLeaves) hipLaunchKernelGGL(K.leafTable, dim3(1), dim3(64), 0, 0, A);
@@ -117,8 +131,9 @@ static int updateScene(phip_scene *sc, const phip_update_desc &u, phip_update_in
     if (U.nTriangles > 0) {
         detail::RefitConsts C;
         HIP_TRY(hipMemcpy(&C, U.dConsts.p, sizeof(C), hipMemcpyDeviceToHost));
-        std::vector<float> terms(bvh.nWNodes);
-        HIP_TRY(hipMemcpy(terms.data(), U.dSahTerm.p, terms.size() * sizeof(float), hipMemcpyDeviceToHost));
+        std::vector<float> terms(rebuild ? fresh.nNodes : bvh.nWNodes);
+        HIP_TRY(hipMemcpy(terms.data(), A.sahTerm, terms.size() * sizeof(float), hipMemcpyDeviceToHost));
+        if (rebuild) rebuildCommit(sc, fresh, newVertices);          /* (nothing below fails but the runtime) */
         double cost = 0; for (float t : terms) cost += t;
         bvh.wSahCost = (float) (cost + 1.0);
         for (int a = 0; a < 3; ++a) {
@@ -149,6 +164,7 @@ static int updateScene(phip_scene *sc, const phip_update_desc &u, phip_update_in
     if (D.envEmitter >= 0) environmentSphereOf(bvh.sceneMin, bvh.sceneMax, U.nTriangles, cam, D);
     setupCamera(cam, sc->descCopy.film, D.cam);
     if (newVertices && u.positions) U.nDegenerate = counters[2];
+    if (rebuild) U.nDegenerate = 0;          /* the new tree has no record for a degenerate triangle, as a creation's */
     /* replicas on other devices are copies of what the scene was: dropped, ensureReplicas copies again before the next multi-device render */
     if (sc->devs.size() > 1) sc->devs.resize(1);
     HIP_TRY(hipSetDevice(sd.device));

@@ -15,7 +15,7 @@
  *       iteration that shades a slot's vertex and traces its shadow ray and its next ray on the packed leaf table in LDS (k_shade_trace.h); scenes of that
  *       kind whose tree lives in L2: k_shade_trace_w, the same iteration on the 8-wide tree in memory (k_shade_trace_w.h)
  *
- * libphip.so is 35 objects of five sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
+ * libphip.so is 36 objects of six sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
  * at plan time (host_render.h -- shadeUnit: the one table over the feature sets; megaKernelOf -> FusedPlan::kernel in planFused, shadeKernelOf / shadeTraceWideKernelOf ->
  * WavefrontPlan::vertex / vertexWide in selectVertexKernel), asks the runtime for the residency of the persistent ones (residentBlocksPerCU) and launches them.
  * Kernels and where they live:
@@ -36,6 +36,7 @@
  *                 k_film (wider filters, small blocks): ImageBlock::put, include/mitsuba/render/imageblock.h:124-204;
  *                 k_reduce_stats, k_export_samples                                                                [this unit]
  *   k_update.h    the refit of phip_scene_update: check, shading and Wald records, scene box, the 8-wide tree level by level, the leaf table   [phip_update.hip]
+ *   k_rebuild.h   the new topology of phip_scene_rebuild: Morton keys, the binary radix tree, its collapse to the 8-wide layout level by level      [phip_rebuild.hip]
  *
  * This file: the C ABI -- error state, the guard that maps what an entry point's body throws to its error code, the entry of both render functions, the film's way
  * to the host and the extern "C" entry points.  The rest of the host side is three headers by concern, each including the ones before it:
@@ -43,7 +44,8 @@
  *                  camera set-up), replication of the scene to further GPUs through SceneDev's one list of buffers
  *   host_render.h  the choice of each render's kernels and the render loop of one device
  *   host_multi.h   the multi-device orchestration (one host thread + stream per GPU, ncclReduce of the films over RCCL/xGMI)
- *   host_update.h  phip_scene_update: new vertices and camera on the tree as built (the kernels: k_update.h in phip_update.hip)
+ *   host_update.h  phip_scene_update: new vertices and camera on the tree as built (the kernels: k_update.h in phip_update.hip); with host_rebuild.h, which it
+ *                  includes, phip_scene_rebuild: the same on a new tree built on the device (k_rebuild.h in phip_rebuild.hip)
  * Not MFMA work: irregular traversal and gathers.  The product never includes, links or calls anything under oracle/.
  */
 #include "phip_common.h"
@@ -106,7 +108,7 @@ static int renderImpl(phip_scene *sc, const phip_render_params *p, float *dOut, 
 struct ErrorCodes { int invalid, other; };
 static const ErrorCodes CREATE_ERRORS = { PHIP_ERR_UNSUPPORTED, PHIP_ERR_INVALID };     /* phip_scene_create: a scene the back end does not serve / a malformed one */
 static const ErrorCodes RENDER_ERRORS = { PHIP_ERR_INVALID, PHIP_ERR_DEVICE };          /* phip_render, phip_render_device: a bad argument / the runtime */
-static const ErrorCodes DEVICE_ERRORS = { PHIP_ERR_DEVICE, PHIP_ERR_DEVICE };           /* phip_scene_replicate, phip_scene_update, phip_film_to_host, phip_trace: their bodies check arguments themselves */
+static const ErrorCodes DEVICE_ERRORS = { PHIP_ERR_DEVICE, PHIP_ERR_DEVICE };           /* phip_scene_replicate, phip_scene_update, phip_scene_rebuild, phip_film_to_host, phip_trace: their bodies check arguments themselves */
 template <typename Body> static int guarded(const ErrorCodes &codes, Body body) {
     try {
         return body();
@@ -173,6 +175,19 @@ int phip_scene_update(phip_scene *scene, const phip_update_desc *u, phip_update_
     return guarded(DEVICE_ERRORS, [&]() -> int {
         std::lock_guard<std::mutex> lock(scene->renderLock);          /* serialises with renders */
         return updateScene(scene, *u, out_info);
+    });
+}
+
+int phip_scene_rebuild(phip_scene *scene, const phip_update_desc *u, phip_update_info *out_info) {
+    if (!scene) return setErr(PHIP_ERR_INVALID, "NULL argument");
+    if (out_info) memset(out_info, 0, sizeof(*out_info));
+    int n = phip_device_count();
+    if (n <= 0) return n == 0 ? setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback") : PHIP_ERR_DEVICE;
+    return guarded(DEVICE_ERRORS, [&]() -> int {
+        std::lock_guard<std::mutex> lock(scene->renderLock);
+        phip_update_desc none; memset(&none, 0, sizeof(none));          /* update == NULL: the scene's current vertices and camera */
+        /* a scene of at most 64 Wald records keeps its packed leaf table and the tree of its creation: the update serves it */
+        return updateScene(scene, u ? *u : none, out_info, scene->wideOnly);
     });
 }
 

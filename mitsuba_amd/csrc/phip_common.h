@@ -2,7 +2,7 @@
  * phip_common.h -- what every translation unit of libphip.so starts with: HIP, the C ABI, the device scene layout and
  * shading functions (dv_scene.h), the path-pool layout (k_pool.h), the error macro.
  *
- * libphip.so is built from five sources (35 objects) so that they compile in parallel:
+ * libphip.so is built from six sources (36 objects) so that they compile in parallel:
  *   phip.hip          the C ABI + traversal and film kernels, with the host side it includes by concern: host_scene.h (scene build, replicas), host_render.h (kernel
  *                     selection, one device's render loop), host_multi.h (multi-device orchestration, RCCL): 1 object
  *   phip_shade.hip    k_shade / k_shade_direct / k_shade_trace instantiations behind the look-ups phipShade*KernelF<n> -- compiled per feature set (-DSHADE_FEAT=0..3, 8
@@ -11,7 +11,9 @@
  *   phip_mega.hip     k_mega instantiations behind phipMegaKernel (-DMEGA_PART=0: scenes in LDS) / phipMegaKernelWide (-DMEGA_PART=1: the 8-wide tree in memory) /
  *                     phipMegaKernelDirect (-DMEGA_PART=2: `direct`): 3 objects
  *   phip_update.hip   the kernels of phip_scene_update (k_update.h) behind phipUpdateKernels: 1 object
- * The other units hold kernels and the look-ups that return them, nothing else: every launch and every query of the runtime is in phip.hip and its host headers.
+ *   phip_rebuild.hip  the kernels of phip_scene_rebuild (k_rebuild.h) behind phipRebuildKernels, and its two rocPRIM calls (sort, scan): 1 object
+ * The other units hold kernels and the look-ups that return them, nothing else: every launch and every query of the runtime is in phip.hip and its host headers
+ * (but for the launches inside rocPRIM's sort and scan, which phip_rebuild.hip wraps).
  * No device function is called across units (everything on the device side is inline in headers), so no -fgpu-rdc.
  */
 #pragma once
@@ -72,3 +74,13 @@ struct UpdateKernels {
     void (*refitLevel)(UpdateArgs, uint32_t, uint32_t), (*leafTable)(UpdateArgs);
 };
 UpdateKernels phipUpdateKernels();
+/* the kernels of phip_scene_rebuild (phip_rebuild.hip, k_rebuild.h); RebuildArgs is theirs.  The sort of the (key, triangle) pairs and the scan over a level are rocPRIM's:
+   temp == NULL returns the size of the temporary storage in tempBytes and runs nothing */
+struct RebuildArgs;
+struct RebuildKernels {
+    void (*keys)(RebuildArgs), (*inner)(RebuildArgs), (*boxes)(RebuildArgs);
+    void (*collapse)(RebuildArgs, uint32_t, uint32_t), (*emit)(RebuildArgs, uint32_t, uint32_t, uint32_t, uint32_t), (*shadeClass)(RebuildArgs, uint32_t);
+};
+RebuildKernels phipRebuildKernels();
+hipError_t phipRebuildSortPairs(void *temp, size_t &tempBytes, const uint32_t *keysIn, uint32_t *keysOut, const uint32_t *trisIn, uint32_t *trisOut, uint32_t n, hipStream_t stream);
+hipError_t phipRebuildScan(void *temp, size_t &tempBytes, const unsigned long long *in, unsigned long long *out, uint32_t n, hipStream_t stream);

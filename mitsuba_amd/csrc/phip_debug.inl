@@ -304,6 +304,101 @@ int phip_debug_host_refit_trace_wide(const float *positions_a, const float *posi
     } catch (const std::exception &e) { return setErr(PHIP_ERR_INVALID, e.what()); }
 }
 
+/* phip_scene_rebuild ON THE HOST, sibling of the hook above with the same arguments: shading records of positions_a, then for positions_b and positions_c in turn (or for
+   positions_a itself when neither is given) the pipeline of host_rebuild.h by the __host__ __device__ functions its kernels run (rebuild_hd.h), in their order -- keys,
+   the sort (std::stable_sort), the binary radix tree, its boxes bottom-up with the arrival flags, the collapse level by level with a serial scan -- and the refit of
+   refit_hd.h on the new topology; the rays are traced on the CPU twin of the wide traversal.  info->n_leaves = leaf slots; *out_n_degenerate = triangles without a record.
+   PHIP_ERR_UNSUPPORTED for a tree the traversal stacks do not hold, as phip_scene_rebuild gives it */
+int phip_debug_host_rebuild_trace_wide(const float *positions_a, const float *positions_b, const float *positions_c, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles,
+                                       const float *camera3, const phip_ray *rays, size_t n_rays, phip_hit *hits, phip_accel_info *info,
+                                       uint32_t *out_nodes, float *out_records, uint32_t *out_rec_prim, uint32_t *out_n_degenerate) {
+    try {
+        for (uint32_t i = 0; i < 3 * n_triangles; ++i) if (indices[i] >= n_vertices) return setErr(PHIP_ERR_INVALID, "index out of range");
+        const uint32_t n = n_triangles;
+        std::vector<float4> ts((size_t) TRISHADE_FLOAT4S * std::max(n, 1u), make_float4(0, 0, 0, 0));
+        for (uint32_t i = 0; i < n; ++i) detail::refitShadeRecord(positions_a, nullptr, indices, i, ts.data() + (size_t) TRISHADE_FLOAT4S * i);
+        const float noCamera[3] = { 0, 0, 0 };
+        detail::RefitConsts K; memset(&K, 0, sizeof(K));
+        std::vector<uint32_t> wnodes, recPrim, levels; std::vector<float4> wtris; std::vector<float> nodeBox;
+        uint32_t nNodes = 0, m = 0, leafSlots = 0; float sah = 1.0f;
+        const auto t0 = std::chrono::steady_clock::now();
+        for (const float *pos : { positions_b, positions_c, (positions_b || positions_c) ? nullptr : positions_a }) {
+            if (!pos) continue;
+            for (uint32_t i = 0; i < n; ++i) detail::refitShadeRecord(pos, nullptr, indices, i, ts.data() + (size_t) TRISHADE_FLOAT4S * i);      /* k_upd_shade */
+            float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
+            for (uint32_t i = 0; i < n; ++i) detail::growByTriangle(ts.data(), TRISHADE_FLOAT4S, i, mn, mx);                                     /* k_upd_box */
+            detail::refitConstsOf(mn, mx, camera3 ? camera3 : noCamera, K);
+            std::vector<std::pair<uint32_t, uint32_t>> pairs(n);                                                                                 /* k_rb_keys */
+            m = 0;
+            for (uint32_t i = 0; i < n; ++i) { pairs[i] = { detail::rebuildKey(ts.data(), TRISHADE_FLOAT4S, i, K), i }; m += pairs[i].first != REBUILD_NO_KEY; }
+            std::stable_sort(pairs.begin(), pairs.end(), [](const std::pair<uint32_t, uint32_t> &a, const std::pair<uint32_t, uint32_t> &b) { return a.first < b.first; });
+            std::vector<uint32_t> keys(n), tris(n);
+            for (uint32_t i = 0; i < n; ++i) { keys[i] = pairs[i].first; tris[i] = pairs[i].second; }
+            const uint32_t maxNodes = std::max(m, 1u);
+            std::vector<int32_t> child(2 * (size_t) maxNodes), items(maxNodes), slotRef(8 * (size_t) maxNodes);
+            std::vector<uint32_t> range(2 * (size_t) maxNodes), parent(2 * (size_t) maxNodes, REBUILD_NO_NODE), arrived(maxNodes, 0u);
+            std::vector<float> box(12 * (size_t) maxNodes);
+            detail::RebuildTree T; T.keys = keys.data(); T.tris = tris.data(); T.nValid = m; T.child = child.data(); T.range = range.data(); T.parent = parent.data();
+            T.box = box.data(); T.arrived = arrived.data();
+            for (uint32_t i = 0; i + 1 < m; ++i) detail::rebuildInnerNode(T, i);                                                                 /* k_rb_inner */
+            for (uint32_t p = 0; p < m; ++p) {                                                                                                   /* k_rb_boxes */
+                float bmn[3], bmx[3];
+                detail::rebuildLeafBox(T, ts.data(), TRISHADE_FLOAT4S, p, bmn, bmx);
+                uint32_t cur = m - 1u + p;
+                for (;;) {
+                    const uint32_t par = parent[cur];
+                    if (par == REBUILD_NO_NODE) break;
+                    const uint32_t before = arrived[par]++;
+                    if (!detail::rebuildClimbStep(T, cur, par, before, bmn, bmx)) break;
+                }
+            }
+            wnodes.assign(20 * (size_t) maxNodes, 0u); recPrim.assign(maxNodes, 0xFFFFFFFFu); levels.assign(1, 0u); leafSlots = 0;
+            uint32_t nRecs = 0;
+            if (m == 0) { nNodes = 1; levels.push_back(1u); }
+            else {
+                items[0] = m == 1 ? ~(int32_t) 0 : 0;
+                uint32_t first = 0, count = 1;
+                while (count) {
+                    if (!wideDepthFits((uint32_t) levels.size())) return setErr(PHIP_ERR_UNSUPPORTED, "the new tree is deeper than the traversal stacks allow");
+                    const uint32_t nextFirst = first + count;
+                    std::vector<unsigned long long> scan(count + 1, 0ull);
+                    for (uint32_t i = 0; i < count; ++i) {                                                                                       /* k_rb_collapse, the scan */
+                        uint32_t nInner, nR;
+                        detail::rebuildCollapseNode(T, items[first + i], slotRef.data() + 8 * (size_t) (first + i), nInner, nR);
+                        scan[i + 1] = scan[i] + ((unsigned long long) nInner | ((unsigned long long) nR << 32));
+                    }
+                    if ((size_t) nextFirst + (uint32_t) scan[count] > maxNodes || (size_t) nRecs + (uint32_t) (scan[count] >> 32) > m) throw std::runtime_error("a level of the collapse does not fit the tree's bounds");
+                    for (uint32_t i = 0; i < count; ++i)                                                                                         /* k_rb_emit */
+                        leafSlots += detail::rebuildEmitNode(T, slotRef.data() + 8 * (size_t) (first + i), nextFirst + (uint32_t) scan[i], nRecs + (uint32_t) (scan[i] >> 32),
+                                                             (uint4 *) wnodes.data() + 5 * (size_t) (first + i), recPrim.data(), items.data());
+                    levels.push_back(nextFirst);
+                    first = nextFirst; nRecs += (uint32_t) (scan[count] >> 32); count = (uint32_t) scan[count];
+                }
+                nNodes = first;
+                if (nRecs != m) throw std::runtime_error("the collapse lost records");
+            }
+            wtris.assign(3 * (size_t) maxNodes, make_float4(0, 0, 0, 0)); nodeBox.assign(6 * (size_t) maxNodes, 0.0f);
+            for (uint32_t r = 0; r < m; ++r) detail::refitWaldRecord(ts.data(), TRISHADE_FLOAT4S, recPrim[r], wtris.data() + 3 * (size_t) r);   /* k_upd_wald */
+            double cost = 0;
+            for (size_t l = levels.size(); l-- > 1; )                                                                                            /* k_upd_refit_level */
+                for (uint32_t idx = levels[l - 1]; idx < levels[l]; ++idx)
+                    cost += detail::refitWideNode((uint4 *) wnodes.data() + 5 * (size_t) idx, idx, ts.data(), TRISHADE_FLOAT4S, recPrim.data(), K, nodeBox.data());
+            sah = (float) (cost + 1.0);
+        }
+        if (info) {
+            memset(info, 0, sizeof(*info));
+            info->n_nodes = nNodes; info->max_depth = (uint32_t) levels.size() - 1u; info->n_triangle_refs = m; info->n_leaves = leafSlots; info->node_bytes = 80; info->triangle_bytes = 48;
+            info->sah_cost = sah; info->build_ms = (float) std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        if (out_nodes) memcpy(out_nodes, wnodes.data(), (size_t) nNodes * 80);
+        if (out_records && m) memcpy(out_records, wtris.data(), (size_t) m * 48);
+        if (out_rec_prim && m) memcpy(out_rec_prim, recPrim.data(), (size_t) m * 4);
+        if (out_n_degenerate) *out_n_degenerate = n - m;
+        hostTraceRays(K.sceneMin, K.sceneMax, wtris.data(), m, (const uint4 *) wnodes.data(), nNodes, 1, rays, n_rays, hits, nullptr, 0);
+        return PHIP_OK;
+    } catch (const std::exception &e) { return setErr(PHIP_ERR_INVALID, e.what()); }
+}
+
 } // extern "C"
 
 /* device execution of the phip_fmath.h functions (bitwise host/device agreement test) */

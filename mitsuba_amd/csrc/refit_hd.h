@@ -101,6 +101,27 @@ RHD void wideQuantise(const WideGrid &g, const float *mn, const float *mx, uint8
     }
 }
 
+/* the slots of a wide node's n <= 8 children (buildWide explains the layout): a child goes to the slot whose octant direction ((s & 1 ? + : -), (s & 2 ? + : -),
+   (s & 4 ? + : -)) best matches its offset from the node's centre -- greedy on the dot product: of all (child, free slot) pairs the best one, n times; the first
+   pair wins a tie.  The host builder and the collapse of phip_scene_rebuild (rebuild_hd.h) both call it */
+RHD void wideAssignSlots(const float (*cmn)[3], const float (*cmx)[3], int n, const float *nbMn, const float *nbMx, int *slotOf) {
+    const float cen[3] = { 0.5f * (nbMn[0] + nbMx[0]), 0.5f * (nbMn[1] + nbMx[1]), 0.5f * (nbMn[2] + nbMx[2]) };
+    bool slotUsed[8] = { false, false, false, false, false, false, false, false }, childDone[8] = { false, false, false, false, false, false, false, false };
+    for (int k = 0; k < n; ++k) {
+        float bestV = -INFINITY; int bc = -1, bs = -1;
+        for (int c = 0; c < n; ++c) {
+            if (childDone[c]) continue;
+            const float d[3] = { 0.5f * (cmn[c][0] + cmx[c][0]) - cen[0], 0.5f * (cmn[c][1] + cmx[c][1]) - cen[1], 0.5f * (cmn[c][2] + cmx[c][2]) - cen[2] };
+            for (int sl = 0; sl < 8; ++sl) {
+                if (slotUsed[sl]) continue;
+                const float v = ((sl & 1) ? d[0] : -d[0]) + ((sl & 2) ? d[1] : -d[1]) + ((sl & 4) ? d[2] : -d[2]);
+                if (v > bestV) { bestV = v; bc = c; bs = sl; }
+            }
+        }
+        childDone[bc] = true; slotUsed[bs] = true; slotOf[bc] = bs;
+    }
+}
+
 /* centre / half extent of a packed leaf (host_scene.h: packLeafTable explains the terms): `ext` = the largest extent of the tight box, `camMax` = the camera's largest coordinate */
 RHD void leafCentreHalf(const float *lo, const float *hi, float ext, float camMax, float *c, float *h) {
     for (int a = 0; a < 3; ++a) {

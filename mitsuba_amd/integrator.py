@@ -91,6 +91,15 @@ class Scene:
         positions, normals: numpy arrays (host memory), or float32 contiguous torch tensors on the scene's device, whose data_ptr() the library reads in place
         (`stream`: the stream their producer ran on -- a torch.cuda.Stream or a raw handle; the update is ordered after it); shape n_vertices x 3 of the scene as
         created.  camera: a phip_camera.  Returns the phip_update_info (update_ms, kernel_ms, sah_cost, n_degenerate); PhipError on a refusal, the scene unchanged."""
+        return self._new_vertices("phip_scene_update", positions, normals, camera, stream)
+
+    def rebuild(self, positions=None, normals=None, camera=None, stream=None):
+        """Scene.update with a new topology of the acceleration structure, built on the device from the positions where they are (phip_scene_rebuild): the remedy for
+        a tree that refits have made slow (compare the sah_cost an update returns with accel_info().sah_cost of the creation).  Same arguments, same return value; with
+        no arguments the tree is rebuilt on the scene's current vertices.  accel_info() may report other node, leaf and record counts afterwards."""
+        return self._new_vertices("phip_scene_rebuild", positions, normals, camera, stream)
+
+    def _new_vertices(self, entry, positions, normals, camera, stream):
         n = self.desc.n_vertices
         u = A.phip_update_desc()
         keep, on_device = [], []
@@ -120,9 +129,9 @@ class Scene:
         if camera is not None:
             u.camera = C.pointer(camera)
         info = A.phip_update_info()
-        rc = self._L.phip_scene_update(self._h, C.byref(u), C.byref(info))
+        rc = getattr(self._L, entry)(self._h, C.byref(u), C.byref(info))
         if rc != 0:
-            raise _ffi.PhipError(rc, "phip_scene_update")
+            raise _ffi.PhipError(rc, entry)
         if camera is not None:
             self.desc.camera = camera
         return info
