@@ -21,6 +21,7 @@
  *   phip_render_params.progress  <- ProgressReporter::update / RenderQueue::signalWorkEnd
  *                                                                      src/librender/renderproc.cpp:146-154
  *   phip_trace          <- ShapeKDTree::rayIntersect(ray, its) / (ray) src/librender/skdtree.cpp:112-142,207-226
+ *   phip_trace_device   <- the same on device memory, with the record of fillIntersectionRecord, include/mitsuba/render/skdtree.h:343-428
  *   phip_cancel         <- SamplingIntegrator::cancel                  src/librender/integrator.cpp:90-93
  *   phip_develop        <- HDRFilm::develop weight normalisation       src/libcore/fmtconv.cpp:979-991
  *
@@ -393,6 +394,34 @@ int  phip_get_samples(phip_scene *scene, float *out_rgba, size_t n_samples);
 int  phip_trace(phip_scene *scene, const phip_ray *rays, size_t n,
                 phip_hit *hits, uint8_t *occluded, phip_stats *out_stats);
 
+/* The surface at a hit: what fillIntersectionRecord (include/mitsuba/render/skdtree.h:343-428) gives the integrators, for callers that use the scene's tree
+   for something else than its integrators (a depth sensor, visibility queries, their own feature buffers).  64 bytes. */
+typedef struct phip_surface {
+    float p[3];  float t;               /* the hit point as shading computes it (the barycentric sum of the vertices, not o + t d), the ray distance */
+    float ng[3]; uint32_t prim;         /* geometric normal (flipped towards the shading normal on meshes with vertex normals, as the record has it);
+                                           PHIP_NO_HIT: a miss, every other field 0 */
+    float ns[3]; uint32_t flags;        /* shading normal (the shading frame's n); PHIP_SURFACE_BACK: the ray arrived on the back (wi.z <= 0, wi as skdtree.h:427) */
+    float uv[2];                        /* texture coordinates; (u, v) of the hit on a mesh without them (skdtree.h:404) */
+    uint32_t material;                  /* the leaf BSDF on the side of arrival: the shape's material, or the nested id a `twosided` adapter shows that side */
+    int32_t  emitter;                   /* id into emitters[] of the area emitter the triangle belongs to, or -1 */
+} phip_surface;
+#define PHIP_SURFACE_BACK 1u
+
+/* phip_trace on DEVICE memory, ordered on the caller's stream, with the surface records: the ray cast of a loop that stays on the GPU (a torch producer writes
+   the rays, phip_scene_update / phip_scene_rebuild move the scene, the hits stay in tensors).  Every pointer is device memory of the scene's device and -- d_occluded
+   excepted -- 16-byte aligned; a host pointer, another device's pointer or a misaligned one is PHIP_ERR_INVALID.  d_hits, d_occluded and d_surfaces may each be NULL;
+   d_surfaces needs d_hits (PHIP_ERR_INVALID without).  n == 0 returns PHIP_OK and touches nothing; n is at most 2^32 - 256 rays per call (PHIP_ERR_INVALID beyond).
+   `stream` is the hipStream_t the caller's producer ran on, or NULL: the work is ordered after it; completion is synchronous on return, as for phip_render_device.
+   The hits are phip_trace's on the same rays, bit for bit (the closest hit does not depend on the structure or the order of the tests); out_stats fills the fields
+   phip_trace fills (the node-visit and triangle-test counters are those of this kernel's order of work; closest_rays / shadow_rays are counted by the kernel),
+   render_ms, and in shade_kernel_ms the HIP-event time of the surface records' kernel.
+   Rays are not validated and must be finite: they are clipped by the arithmetic phip_trace clips them with, so a non-finite ray gets what it gets there.
+   The call takes the scene's render lock.  Its buffers -- the stack overflow region of the persistent grid, the work counters, the per-wave statistics -- are the
+   scene's and are sized by the grid, not by n: after the first call no call allocates, and there is no chunking. */
+int  phip_trace_device(phip_scene *scene, const phip_ray *d_rays, size_t n,
+                       phip_hit *d_hits, uint8_t *d_occluded, phip_surface *d_surfaces,
+                       void *stream, phip_stats *out_stats);
+
 /* Replicates the device-resident scene (geometry, acceleration structure, materials, textures) from the scene's device
    to each listed device (device-to-device copies over xGMI), so that a later multi-device render starts immediately. */
 int  phip_scene_replicate(phip_scene *scene, const int32_t *devices, int32_t n_devices);
@@ -473,7 +502,7 @@ int  phip_scene_accel_info(const phip_scene *scene, phip_accel_info *out);
 /* Utilities for callers that fill a phip_scene_desc without Mitsuba at hand (the test harness, bench.py): the table of the reference's default `gaussian` reconstruction
  * filter with the given standard deviation -- (radius, PHIP_FILTER_RESOLUTION + 1 values), rfilter.cpp:38-57 + gaussian.cpp:34-57; the Mitsuba shim copies the scene's own
  * filter instead -- and sizeof of the ABI's structs by index (0 phip_material, 1 phip_shape, 2 phip_emitter, 3 phip_camera, 4 phip_film, 5 phip_scene_desc,
- * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info, 11 phip_update_desc, 12 phip_update_info), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
+ * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info, 11 phip_update_desc, 12 phip_update_info, 13 phip_surface), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
 void   phip_gaussian_filter(float stddev, float *radius, float *table);
 size_t phip_abi_sizeof(int which);
 

@@ -144,6 +144,14 @@ class phip_hit(C.Structure):
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("prim", C.c_uint32)]
 
 
+class phip_surface(C.Structure):
+    _fields_ = [("p", C.c_float * 3), ("t", C.c_float), ("ng", C.c_float * 3), ("prim", C.c_uint32),
+                ("ns", C.c_float * 3), ("flags", C.c_uint32), ("uv", C.c_float * 2), ("material", C.c_uint32), ("emitter", C.c_int32)]
+
+
+PHIP_SURFACE_BACK = 1
+
+
 class phip_accel_info(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("n_triangle_refs", C.c_uint32),
                 ("max_depth", C.c_uint32), ("node_bytes", C.c_uint32), ("triangle_bytes", C.c_uint32),

@@ -184,6 +184,27 @@ DV void fillIntersection(const DevScene &S, const V3 &rayD, uint32_t prim, float
     its.t = t; its.prim = prim;
 }
 
+/* The surface record of a ray cast (phip_surface, include/phip.h) from a hit (t, u, v, prim) and the ray's direction: fillIntersection, and what a caller
+   outside the integrators needs beside it -- the (u, v) fallback of a mesh without texture coordinates (skdtree.h:404), the side of arrival (wi.z <= 0 is the
+   back) and the leaf BSDF of that side (bsdfResolve's rule: a `twosided` adapter shows its second nested model to wi.z < 0).  k_surfaces (k_raycast.h) and its
+   host twin (phip_debug.inl) evaluate this one statement. */
+DV void fillSurface(const DevScene &S, const V3 &rayD, float t, float cu, float cv, uint32_t prim, phip_surface &out) {
+    if (prim == PHIP_NO_HIT) {
+        out.p[0] = out.p[1] = out.p[2] = out.t = 0.0f; out.ng[0] = out.ng[1] = out.ng[2] = 0.0f; out.prim = PHIP_NO_HIT;
+        out.ns[0] = out.ns[1] = out.ns[2] = 0.0f; out.flags = 0u; out.uv[0] = out.uv[1] = 0.0f; out.material = 0u; out.emitter = 0;
+        return;
+    }
+    Isect its;
+    fillIntersection(S, rayD, prim, cu, cv, t, its);
+    const bool texcoords = (its.flags & TS_TEXCOORDS) != 0;
+    const bool flip = (its.flags & TS_TWOSIDED) && its.wi.z < 0;
+    out.p[0] = its.p.x; out.p[1] = its.p.y; out.p[2] = its.p.z; out.t = t;
+    out.ng[0] = its.geoN.x; out.ng[1] = its.geoN.y; out.ng[2] = its.geoN.z; out.prim = prim;
+    out.ns[0] = its.sh.n.x; out.ns[1] = its.sh.n.y; out.ns[2] = its.sh.n.z; out.flags = its.wi.z <= 0 ? PHIP_SURFACE_BACK : 0u;
+    out.uv[0] = texcoords ? its.uv.x : cu; out.uv[1] = texcoords ? its.uv.y : cv;
+    out.material = flip ? its.back : its.front; out.emitter = its.emitter;
+}
+
 /* Intersection::computePartials, intersection.cpp:5-76 (rxOrigin = ryOrigin = rayO: pinhole camera) */
 DV bool solveLinearSystem2x2(const float a[2][2], const float b[2], float x[2]) {   /* util.cpp:527-539 */
     const float det = a[0][0] * a[1][1] - a[0][1] * a[1][0];

@@ -135,7 +135,9 @@ struct SceneDev {
     DevBuf<uint32_t> rinvPrimes, rinvOffsets; DevBuf<uint16_t> rinvPerm; uint64_t rinvKey = 0;   /* PHIP_SAMPLER_HALTON / _HAMMERSLEY: primes + permutations */
     uint32_t rinvInvPerm2 = 0x4u, rinvInvPerm3 = 0x24u;                                                                         /* inverse permutations of bases 2 and 3, two bits per digit */
     DevBuf<unsigned long long> dynCounter, stat, invalid, megaNext;
-    DevBuf<unsigned int> drawCounters;                                                       /* k_rays_w: 2 x RAY_SHARDS sharded work counters */
+    DevBuf<unsigned int> drawCounters;                                                       /* k_rays_w, k_raycast_p: 2 x RAY_SHARDS sharded work counters */
+    /* phip_trace_device (host_raycast.h): the persistent ray server's kernels, LDS plan and resident grid, resolved for a tree whose node cache is `nodeCache` */
+    struct RaycastPlan { RaycastKernels k = { nullptr, nullptr }; uint32_t nodeCache = 0; size_t lds = 0; unsigned blocks = 0; } raycast;
     DevBuf<float> film, patchImg;                                                            /* patchImg: k_film_splat's 16 x 16 patch images (k_film.h) */
     uint32_t lastSpp = 0, nLocalTiles = 0; unsigned long long localPixels = 0;
     int tileKey[3] = { -1, -1, -1 };

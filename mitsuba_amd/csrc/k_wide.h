@@ -1,6 +1,7 @@
 /*
  * k_wide.h -- traversal of the compressed 8-wide BVH (bvh.h: buildWide) for the big scenes: k_rays_w (persistent waves with
- * refill; closest-hit and any-hit rays of an iteration in one launch) and k_raycast_w (phip_trace).  Included by phip.hip.
+ * refill; closest-hit and any-hit rays of an iteration in one launch) and k_raycast_w (phip_trace).  Included by phip.hip -- and, for the persistent loop and
+ * its draw counters alone (WIDE_SERVER_ONLY), by phip_raycast.hip, whose k_raycast_p feeds the loop from a caller's ray array (k_raycast.h).
  *
  * Why a second structure: the BVH4 ray kernel of the 250k-triangle scenes was measured (round 2, SQ counters) at 34 % VALU
  * issue with 64 % of its wave cycles waiting -- every lane of a wave fetches its own node, i.e. 64 different cache lines per
@@ -152,8 +153,11 @@ enum { WW_RAYS = 0, WW_STEPS, WW_SH_RAYS, WW_SH_STEPS, WW_COUNT };     /* 64-bit
  *     triangle index (winsTie), whatever the order; the lane whose key stands in the slot after the step writes (u, v) beside it;
  *     any hit: LDS min of the group bit (the sequential loop stops at the first hit in bit order: the work counter stays what it was);
  *   - the slot is the ray's result: (t, u, v, prim) leave the registers, the owner only pulls its new maxt after a round.
- * The rays' step sequences are unchanged (all records of a group, then the next node), hence so are results and counters. */
-__device__ __forceinline__ void persistentTraverseWide(const DevScene &S, WideStackT<WIDE_BLOCK> &stack, ShadowSourceDyn &ss, TraceSourceDyn &ts,
+ * The rays' step sequences are unchanged (all records of a group, then the next node), hence so are results and counters.
+ * The loop is generic over its two sources -- any-hit rays first, then closest-hit rays: more / assign / load / commit.  k_rays_w feeds it from the pool (above),
+ * k_raycast_p from a caller's ray array (k_raycast.h). */
+template <typename AnyHitSource, typename ClosestHitSource>
+__device__ __forceinline__ void persistentTraverseWide(const DevScene &S, WideStackT<WIDE_BLOCK> &stack, AnyHitSource &ss, ClosestHitSource &ts,
                                                        unsigned long long *wc /* LDS: WC_COUNT counters of this wave */, unsigned char *dealLds /* WD_WAVE_BYTES of this wave */) {
     lds_w64 *slot = (lds_w64 *) dealLds; lds_u2 *uvs = (lds_u2 *) (dealLds + 64u * 8u); lds_w16 *list = (lds_w16 *) (dealLds + 2u * 64u * 8u);
     const uint32_t lane = __lane_id();
@@ -286,6 +290,7 @@ __device__ __forceinline__ void persistentTraverseWide(const DevScene &S, WideSt
     }
 }
 
+#ifndef WIDE_SERVER_ONLY      /* (phip_raycast.hip takes the loop and the draw counters, not this unit's kernels) */
 __global__ __launch_bounds__(WIDE_BLOCK, WIDE_WAVES) void k_rays_w(DevScene S, PathPool P, float4 *L, unsigned int *drawCounters /* 2 * RAY_SHARDS lines, zeroed */) {
     __shared__ unsigned long long wcnt[WIDE_BLOCK / 64][WW_COUNT];
     const uint32_t wave = WIDE_UNIFORM(threadIdx.x >> 6), waveId = blockIdx.x * (WIDE_BLOCK / 64) + wave;
@@ -339,3 +344,4 @@ __global__ __launch_bounds__(BLOCK) void k_raycast_w(DevScene S, const phip_ray 
     waveStat(P, ST_SH_NODE, waveId, shNodeVisits);
     waveStat(P, ST_SH_TRI, waveId, shTriTests);
 }
+#endif

@@ -15,7 +15,7 @@
  *       iteration that shades a slot's vertex and traces its shadow ray and its next ray on the packed leaf table in LDS (k_shade_trace.h); scenes of that
  *       kind whose tree lives in L2: k_shade_trace_w, the same iteration on the 8-wide tree in memory (k_shade_trace_w.h)
  *
- * libphip.so is 36 objects of six sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
+ * libphip.so is 37 objects of seven sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
  * at plan time (host_render.h -- shadeUnit: the one table over the feature sets; megaKernelOf -> FusedPlan::kernel in planFused, shadeKernelOf / shadeTraceWideKernelOf ->
  * WavefrontPlan::vertex / vertexWide in selectVertexKernel), asks the runtime for the residency of the persistent ones (residentBlocksPerCU) and launches them.
  * Kernels and where they live:
@@ -37,6 +37,7 @@
  *                 k_reduce_stats, k_export_samples                                                                [this unit]
  *   k_update.h    the refit of phip_scene_update: check, shading and Wald records, scene box, the 8-wide tree level by level, the leaf table   [phip_update.hip]
  *   k_rebuild.h   the new topology of phip_scene_rebuild: Morton keys, the binary radix tree, its collapse to the 8-wide layout level by level      [phip_rebuild.hip]
+ *   k_raycast.h   phip_trace_device: k_raycast_p (k_wide.h's persistent loop on a caller's ray array), k_surfaces (the record at every hit)            [phip_raycast.hip]
  *
  * This file: the C ABI -- error state, the guard that maps what an entry point's body throws to its error code, the entry of both render functions, the film's way
  * to the host and the extern "C" entry points.  The rest of the host side is three headers by concern, each including the ones before it:
@@ -46,6 +47,7 @@
  *   host_multi.h   the multi-device orchestration (one host thread + stream per GPU, ncclReduce of the films over RCCL/xGMI)
  *   host_update.h  phip_scene_update: new vertices and camera on the tree as built (the kernels: k_update.h in phip_update.hip); with host_rebuild.h, which it
  *                  includes, phip_scene_rebuild: the same on a new tree built on the device (k_rebuild.h in phip_rebuild.hip)
+ *   host_raycast.h phip_trace_device: the persistent ray server's plan and launch on the caller's stream, the surface records behind it (k_raycast.h in phip_raycast.hip)
  * Not MFMA work: irregular traversal and gathers.  The product never includes, links or calls anything under oracle/.
  */
 #include "phip_common.h"
@@ -76,6 +78,7 @@ static int setErr(int code, const std::string &msg) { g_err = msg; return code; 
 #include "host_render.h"
 #include "host_multi.h"
 #include "host_update.h"
+#include "host_raycast.h"
 
 /* Entry of both render functions: validation, the scene's render lock, single- or multi-device dispatch, the sticky
    cancellation flag (consumed by the call that observed it). */
@@ -108,7 +111,7 @@ static int renderImpl(phip_scene *sc, const phip_render_params *p, float *dOut, 
 struct ErrorCodes { int invalid, other; };
 static const ErrorCodes CREATE_ERRORS = { PHIP_ERR_UNSUPPORTED, PHIP_ERR_INVALID };     /* phip_scene_create: a scene the back end does not serve / a malformed one */
 static const ErrorCodes RENDER_ERRORS = { PHIP_ERR_INVALID, PHIP_ERR_DEVICE };          /* phip_render, phip_render_device: a bad argument / the runtime */
-static const ErrorCodes DEVICE_ERRORS = { PHIP_ERR_DEVICE, PHIP_ERR_DEVICE };           /* phip_scene_replicate, phip_scene_update, phip_scene_rebuild, phip_film_to_host, phip_trace: their bodies check arguments themselves */
+static const ErrorCodes DEVICE_ERRORS = { PHIP_ERR_DEVICE, PHIP_ERR_DEVICE };           /* phip_scene_replicate, phip_scene_update, phip_scene_rebuild, phip_film_to_host, phip_trace, phip_trace_device: their bodies check arguments themselves */
 template <typename Body> static int guarded(const ErrorCodes &codes, Body body) {
     try {
         return body();
@@ -361,6 +364,17 @@ int phip_trace(phip_scene *scene, const phip_ray *rays, size_t n, phip_hit *hits
     });
 }
 
+int phip_trace_device(phip_scene *scene, const phip_ray *d_rays, size_t n, phip_hit *d_hits, uint8_t *d_occluded, phip_surface *d_surfaces, void *stream, phip_stats *out_stats) {
+    if (!scene || (!d_rays && n)) return setErr(PHIP_ERR_INVALID, "NULL argument");
+    int nDev = phip_device_count();
+    if (nDev <= 0) return nDev == 0 ? setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback") : PHIP_ERR_DEVICE;
+    return guarded(DEVICE_ERRORS, [&]() -> int {
+        HIP_TRY(hipSetDevice(scene->devs[0]->device));
+        std::lock_guard<std::mutex> lock(scene->renderLock);
+        return traceDevice(scene, d_rays, n, d_hits, d_occluded, d_surfaces, (hipStream_t) stream, out_stats);
+    });
+}
+
 void phip_cancel(phip_scene *scene) { if (scene && scene->cancelFlag) __atomic_store_n(scene->cancelFlag, 1, __ATOMIC_RELAXED); }
 
 void phip_develop(const float *rgbaw, size_t n_pixels, float *out_rgb) {
@@ -416,6 +430,7 @@ size_t phip_abi_sizeof(int which) {
         case 10: return sizeof(phip_accel_info);
         case 11: return sizeof(phip_update_desc);
         case 12: return sizeof(phip_update_info);
+        case 13: return sizeof(phip_surface);
         default: return 0;
     }
 }

@@ -2,7 +2,7 @@
  * phip_common.h -- what every translation unit of libphip.so starts with: HIP, the C ABI, the device scene layout and
  * shading functions (dv_scene.h), the path-pool layout (k_pool.h), the error macro.
  *
- * libphip.so is built from six sources (36 objects) so that they compile in parallel:
+ * libphip.so is built from seven sources (37 objects) so that they compile in parallel:
  *   phip.hip          the C ABI + traversal and film kernels, with the host side it includes by concern: host_scene.h (scene build, replicas), host_render.h (kernel
  *                     selection, one device's render loop), host_multi.h (multi-device orchestration, RCCL): 1 object
  *   phip_shade.hip    k_shade / k_shade_direct / k_shade_trace instantiations behind the look-ups phipShade*KernelF<n> -- compiled per feature set (-DSHADE_FEAT=0..3, 8
@@ -12,6 +12,7 @@
  *                     phipMegaKernelDirect (-DMEGA_PART=2: `direct`): 3 objects
  *   phip_update.hip   the kernels of phip_scene_update (k_update.h) behind phipUpdateKernels: 1 object
  *   phip_rebuild.hip  the kernels of phip_scene_rebuild (k_rebuild.h) behind phipRebuildKernels, and its two rocPRIM calls (sort, scan): 1 object
+ *   phip_raycast.hip  the kernels of phip_trace_device (k_raycast.h) behind phipRaycastKernels: 1 object
  * The other units hold kernels and the look-ups that return them, nothing else: every launch and every query of the runtime is in phip.hip and its host headers
  * (but for the launches inside rocPRIM's sort and scan, which phip_rebuild.hip wraps).
  * No device function is called across units (everything on the device side is inline in headers), so no -fgpu-rdc.
@@ -84,3 +85,9 @@ struct RebuildKernels {
 RebuildKernels phipRebuildKernels();
 hipError_t phipRebuildSortPairs(void *temp, size_t &tempBytes, const uint32_t *keysIn, uint32_t *keysOut, const uint32_t *trisIn, uint32_t *trisOut, uint32_t n, hipStream_t stream);
 hipError_t phipRebuildScan(void *temp, size_t &tempBytes, const unsigned long long *in, unsigned long long *out, uint32_t n, hipStream_t stream);
+/* the kernels of phip_trace_device (phip_raycast.hip, k_raycast.h): rays, hits and surface records as the 16-byte words they are made of */
+struct RaycastKernels {
+    void (*cast)(DevScene, const float4 *, uint32_t, float4 *, uint8_t *, PathPool, unsigned int *);
+    void (*surfaces)(DevScene, const float4 *, const float4 *, uint32_t, float4 *);
+};
+RaycastKernels phipRaycastKernels();

@@ -445,6 +445,27 @@ extern "C" int phip_debug_host_mip_eval(const phip_texture *t, size_t n, const f
     } catch (const std::exception &e) { return setErr(PHIP_ERR_INVALID, e.what()); }
 }
 
+/* The surface records of phip_trace_device on the host: the shading records come from the stages phip_scene_create runs before it builds the tree (validation, shapes,
+   textures' maxima, materials, shadingRecords -- none of them calls HIP), the records from fillSurface (dv_scene.h), which k_surfaces evaluates on the device.
+   hits: (t, u, v, prim) of every ray, from any ray cast of the scene. */
+extern "C" int phip_debug_host_surfaces(const phip_scene_desc *desc, const phip_ray *rays, const phip_hit *hits, size_t n, phip_surface *out) {
+    if (!desc || ((!rays || !hits || !out) && n)) return setErr(PHIP_ERR_INVALID, "NULL argument");
+    try {
+        phip_scene sc;
+        SceneBuild B(&sc, *desc);
+        B.validateDesc();
+        B.flattenShapes(); B.packTextures(); B.materials();
+        B.shadingRecords();
+        DevScene S; memset(&S, 0, sizeof(S));
+        S.triShade = B.ts.data(); S.triShadeStride = B.stride; S.nTriangles = desc->n_triangles;
+        for (size_t i = 0; i < n; ++i) {
+            if (hits[i].prim != PHIP_NO_HIT && hits[i].prim >= desc->n_triangles) return setErr(PHIP_ERR_INVALID, "hit primitive out of range");
+            fillSurface(S, V3(rays[i].d[0], rays[i].d[1], rays[i].d[2]), hits[i].t, hits[i].u, hits[i].v, hits[i].prim, out[i]);
+        }
+        return PHIP_OK;
+    } catch (const std::exception &e) { return setErr(PHIP_ERR_INVALID, e.what()); }
+}
+
 extern "C" int phip_debug_fmath(int on_device, int op, size_t n, const float *a, const float *b, float *out) {
     if (!on_device) {
         for (size_t i = 0; i < n; ++i) {

@@ -79,6 +79,28 @@ class Scene:
             raise _ffi.PhipError(rc, "phip_trace")
         return hits, occ, st
 
+    def rayIntersectDevice(self, rays, closest=True, shadow=False, surfaces=False, stream=None):
+        """rayIntersect on device memory (phip_trace_device): rays is a contiguous float32 torch tensor of shape (n, 8) = o, mint, d, maxt on the scene's device, read in
+        place; `stream` is the stream its producer ran on (a torch.cuda.Stream or a raw handle), the cast is ordered after it.  Returns (hits, occluded, surfaces, stats):
+        torch tensors on the same device -- (n, 4) float32 (t, u, v, bits of prim), (n,) uint8, (n, 16) float32 (the words of phip_surface) -- or None where not asked for.
+        stats.trace_kernel_ms is the ray kernel's HIP-event time, stats.shade_kernel_ms that of the surface records' kernel.
+        The rays must be finite.  ValueError for a tensor of another dtype, layout or device; PhipError for what the library refuses (surfaces without closest)."""
+        import torch
+        if not hasattr(rays, "data_ptr") or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError("rays: expected a contiguous float32 tensor of shape (n, 8)")
+        if not rays.is_cuda or (rays.device.index or 0) != self.device:
+            raise ValueError("rays: the tensor is not on the scene's device")
+        n = rays.shape[0]
+        hits = torch.empty((n, 4), dtype=torch.float32, device=rays.device) if closest else None
+        occ = torch.empty((n,), dtype=torch.uint8, device=rays.device) if shadow else None
+        surf = torch.empty((n, 16), dtype=torch.float32, device=rays.device) if surfaces else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        st = A.phip_stats()
+        rc = self._L.phip_trace_device(self._h, ptr(rays), n, ptr(hits), ptr(occ), ptr(surf), getattr(stream, "cuda_stream", stream), C.byref(st))
+        if rc != 0:
+            raise _ffi.PhipError(rc, "phip_trace_device")
+        return hits, occ, surf, st
+
     def replicate(self, devices):
         """Copies the device scene to further GPUs ahead of a multi-device render (phip_scene_replicate)."""
         arr = (C.c_int32 * len(devices))(*devices)
