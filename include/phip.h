@@ -422,6 +422,42 @@ int  phip_trace_device(phip_scene *scene, const phip_ray *d_rays, size_t n,
                        phip_hit *d_hits, uint8_t *d_occluded, phip_surface *d_surfaces,
                        void *stream, phip_stats *out_stats);
 
+/* Path-traced radiance along a caller's rays in DEVICE memory: SamplingIntegrator::Li(ray, rRec) (include/mitsuba/render/integrator.h) as an entry point, for callers
+   whose sensor is their own code -- an orthographic, thin-lens or spherical camera, an irradiance meter, a light-probe or lightmap bake written as torch code over
+   this call.  phip_render_device serves the one sensor the library knows, the `perspective` pinhole through the film.
+     Samples.  For ray i and k in [0, spp) one evaluation of the integrator's Li starts with the caller's ray -- its o, d, mint and maxt --, clipped to the scene with
+       the arithmetic the camera ray is clipped with.
+     Stream.  The random numbers are the PHIP_SAMPLER_CTR stream of (pixel = the ray's stream key, sample = sample_offset + k, seed), consumed exactly as phip_render
+       consumes them for a camera sample; the two numbers of the pixel jitter are drawn and not used.  The key of ray i is d_stream[i], or first_stream + i.
+     Read from params: spp, max_depth, rr_depth, strict_normals, hide_emitters, seed, sample_offset, sample_total, stream, device (n_devices = 1: devices[0]),
+       integrator, PHIP_FLAG_KERNEL_TIMING.  Ignored: what concerns the film -- shards, block size, the progress callback (its totals are the film's),
+       PHIP_FLAG_ENVMAP_BILINEAR_BACKGROUND, the flags that choose a fused kernel.  Refused, PHIP_ERR_INVALID: PHIP_FLAG_SAMPLE_BUFFER, PHIP_FLAG_ACCUMULATE.
+     Differentials.  The caller's ray has none: a bitmap texture at the first vertex and a directly visible environment map are read the way later vertices read
+       them, level 0 and bilinear.  This is the one difference from a camera ray; on a scene without textures and without an envmap there is none, and sample k of a
+       ray equals sample k of the pixel whose camera ray it is and whose index (y * crop_width + x) is its key, bit for bit (PHIP_FLAG_SAMPLE_BUFFER, phip_get_samples).
+     Output.  d_out[i].rgb is the float64 sum of the spp float32 sample values, in ascending k, divided by spp and rounded once to float32; d_out[i].alpha the same mean
+       of the samples' alpha, 1 where the caller's ray hit and 0 where it did not.  A non-finite or negative sample is counted in invalid_samples and contributes
+       zero, as the film would reject it.
+     Served: PHIP_INTEGRATOR_PATH and PHIP_INTEGRATOR_VOLPATH_SIMPLE with PHIP_SAMPLER_CTR.  PHIP_ERR_UNSUPPORTED: PHIP_INTEGRATOR_DIRECT and the other samplers, whose
+       streams are addressed by film coordinates.  PHIP_ERR_INVALID: n_devices > 1, a host pointer, another device's pointer, a misaligned pointer, d_rays or d_out
+       NULL, n > 2^32 - 256, and what phip_render refuses of the parameters above.  n == 0 returns PHIP_OK and touches nothing.  Rays are not validated and must be finite.
+     Ordering and locking, as for phip_trace_device: the work is ordered after params->stream, completion is synchronous on return, the call takes the scene's render
+       lock; phip_cancel ends it with PHIP_ERR_CANCELLED and d_out unspecified.
+     Stats: samples, the ray and vertex counters, invalid_samples, iterations, render_ms, and under PHIP_FLAG_KERNEL_TIMING trace / shade_kernel_ms and, in
+       film_kernel_ms, the time of the kernel that writes d_out.
+   There is no fused path: the call runs the wavefront kernels, as a render with PHIP_FLAG_NO_FUSED does.  Its buffers are the scene's and are kept between calls; a
+   call whose spp does not fit one pass (PHIP_MAX_PASS_SAMPLES, as for renders) splits spp over passes and keeps 32 bytes per ray of running sums, so that buffer, like
+   the 16 bytes per sample of a pass, grows with n. */
+typedef struct phip_radiance_desc {
+    const phip_ray *d_rays;      /* n rays, device memory of the scene's device, 16-byte aligned; finite, not validated */
+    size_t          n;
+    const uint32_t *d_stream;    /* NULL, or n stream keys: ray i draws the counter stream of "pixel" d_stream[i]; NULL = first_stream + i */
+    uint32_t        first_stream;
+    uint32_t        reserved;
+    float          *d_out;       /* n x (R, G, B, alpha) float32, device, 16-byte aligned */
+} phip_radiance_desc;
+int  phip_radiance_device(phip_scene *scene, const phip_render_params *params, const phip_radiance_desc *desc, phip_stats *out_stats /* may be NULL */);
+
 /* Replicates the device-resident scene (geometry, acceleration structure, materials, textures) from the scene's device
    to each listed device (device-to-device copies over xGMI), so that a later multi-device render starts immediately. */
 int  phip_scene_replicate(phip_scene *scene, const int32_t *devices, int32_t n_devices);
@@ -502,7 +538,7 @@ int  phip_scene_accel_info(const phip_scene *scene, phip_accel_info *out);
 /* Utilities for callers that fill a phip_scene_desc without Mitsuba at hand (the test harness, bench.py): the table of the reference's default `gaussian` reconstruction
  * filter with the given standard deviation -- (radius, PHIP_FILTER_RESOLUTION + 1 values), rfilter.cpp:38-57 + gaussian.cpp:34-57; the Mitsuba shim copies the scene's own
  * filter instead -- and sizeof of the ABI's structs by index (0 phip_material, 1 phip_shape, 2 phip_emitter, 3 phip_camera, 4 phip_film, 5 phip_scene_desc,
- * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info, 11 phip_update_desc, 12 phip_update_info, 13 phip_surface), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
+ * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info, 11 phip_update_desc, 12 phip_update_info, 13 phip_surface, 15 phip_radiance_desc; 14 is unassigned and answers 0: tests/test_raycast_device_host.py pins phip_abi_sizeof(14) == 0 as "one past the last struct" and stays as it is, so the new struct skips that index), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
 void   phip_gaussian_filter(float stddev, float *radius, float *table);
 size_t phip_abi_sizeof(int which);
 

@@ -152,6 +152,10 @@ class phip_surface(C.Structure):
 PHIP_SURFACE_BACK = 1
 
 
+class phip_radiance_desc(C.Structure):
+    _fields_ = [("d_rays", C.c_void_p), ("n", C.c_size_t), ("d_stream", C.c_void_p), ("first_stream", C.c_uint32), ("reserved", C.c_uint32), ("d_out", C.c_void_p)]
+
+
 class phip_accel_info(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("n_triangle_refs", C.c_uint32),
                 ("max_depth", C.c_uint32), ("node_bytes", C.c_uint32), ("triangle_bytes", C.c_uint32),

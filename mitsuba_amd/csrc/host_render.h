@@ -15,11 +15,14 @@ struct ShadeUnit {
     ShadeKernel (*direct)(int materialMask);
     ShadeKernel (*trace)(bool strictNormals, int materialMask);
     ShadeTraceWideKernel (*traceWide)(bool strictNormals, int materialMask);
+    ShadeRaysKernel (*rays[2])(int materialMask, int tables);   /* k_shade_r without / with strictNormals (phip_radiance_device: the counter stream only, so nullptr with FEAT bit 3) */
 };
 /* The one place that maps a feature set to its objects */
 static const ShadeUnit &shadeUnit(int feat) {
-#define SHADE_UNIT(n) { { phipShadeKernelS0F##n, phipShadeKernelS1F##n }, phipShadeDirectKernelF##n, phipShadeTraceKernelF##n, phipShadeTraceWideKernelF##n }
-    static const ShadeUnit units[6] = { SHADE_UNIT(0), SHADE_UNIT(1), SHADE_UNIT(2), SHADE_UNIT(3), SHADE_UNIT(8), SHADE_UNIT(11) };
+#define SHADE_UNIT(n, r0, r1) { { phipShadeKernelS0F##n, phipShadeKernelS1F##n }, phipShadeDirectKernelF##n, phipShadeTraceKernelF##n, phipShadeTraceWideKernelF##n, { r0, r1 } }
+#define SHADE_UNIT_R(n) SHADE_UNIT(n, phipShadeRaysKernelS0F##n, phipShadeRaysKernelS1F##n)
+    static const ShadeUnit units[6] = { SHADE_UNIT_R(0), SHADE_UNIT_R(1), SHADE_UNIT_R(2), SHADE_UNIT_R(3), SHADE_UNIT(8, nullptr, nullptr), SHADE_UNIT(11, nullptr, nullptr) };
+#undef SHADE_UNIT_R
 #undef SHADE_UNIT
     switch (feat & 11) {
         case 0: return units[0];
@@ -191,6 +194,7 @@ struct WavefrontPlan {
     /* the vertex kernel of the iterations, its grid and dynamic LDS (selectVertexKernel): k_shade, k_shade_direct or k_shade_trace with a thread per slot, or -- with
        wideTrace -- k_shade_trace_w, a persistent grid that stages traceNodeCache nodes */
     ShadeKernel vertex = nullptr; ShadeTraceWideKernel vertexWide = nullptr;
+    ShadeRaysKernel vertexRays = nullptr; RaySamples rays = { nullptr, nullptr, 0u, 0u };     /* phip_radiance_device: k_shade_r in k_shade's place, and the caller's ray array (host_radiance.h) */
     dim3 vertexGrid = dim3(1); size_t vertexLds = 0; uint32_t traceNodeCache = 0;
     uint32_t capacity = 0, nWaves = 0, nBlocks = 0;
     int feat = 0;                           /* FEAT of the shading kernels: 1 environment emitter, 2 bitmap textures, 8 the QMC samplers */
@@ -258,22 +262,21 @@ static void shardTiles(RenderJob &J, int shardIndex, int shardCount) {
     sd.tileKey[0] = bs; sd.tileKey[1] = shardIndex; sd.tileKey[2] = shardCount;
 }
 
-/* passes: bound the per-sample buffer (16 B per sample id; 24 B with the jitter the sequence samplers keep for the film pass) */
-static void planPasses(RenderJob &J) {
+/* passes: bound the per-sample buffer (16 B per sample id; 24 B with the jitter the sequence samplers keep for the film pass).  idsPerSpp: the sample ids one sample
+   per pixel takes -- the pixels of this device's blocks, or the rays of phip_radiance_device */
+static void planPasses(RenderJob &J, unsigned long long idsPerSpp) {
     SceneDev &sd = J.sd; const phip_render_params *p = J.p;
     J.keepJitter = (p->sampler == PHIP_SAMPLER_SOBOL || p->sampler == PHIP_SAMPLER_HALTON || p->sampler == PHIP_SAMPLER_HAMMERSLEY);
     const unsigned long long maxIdsPerPass = (1ull << 32) - 1;                 /* sample ids are 32-bit in the slot state */
     unsigned long long budgetIds = (24ull << 30) / (J.keepJitter ? 24 : 16);  /* 24 GiB of sample buffer */
     if (const char *e = getenv("PHIP_MAX_PASS_SAMPLES")) budgetIds = std::max(1ull, strtoull(e, nullptr, 10));   /* test hook: force several passes */
-    J.idsPerSpp = (unsigned long long) sd.nLocalTiles * ((unsigned long long) J.bs * J.bs);
+    J.idsPerSpp = idsPerSpp;
     J.sppPerPass = (uint32_t) p->spp;
     if (J.idsPerSpp > 0) {
         unsigned long long cap = std::min(maxIdsPerPass, budgetIds) / J.idsPerSpp;
         if (cap < 1) cap = 1;
         J.sppPerPass = (uint32_t) std::min<unsigned long long>(cap, (unsigned long long) p->spp);
     }
-    if (J.keepSamples) { sd.sampleOut.alloc((size_t) J.W * J.H * (size_t) p->spp); HIP_TRY(hipMemsetAsync(sd.sampleOut.p, 0, sd.sampleOut.n * sizeof(float4), J.stream)); }
-    sd.haveSamples = J.keepSamples; sd.lastSpp = (uint32_t) p->spp;
     const unsigned long long idsFirstPass = J.idsPerSpp * J.sppPerPass;
     if (sd.L.n < idsFirstPass) sd.L.alloc((size_t) idsFirstPass);
     if (J.keepJitter && sd.jitter.n < idsFirstPass) sd.jitter.alloc((size_t) idsFirstPass);
@@ -672,7 +675,8 @@ static bool wavefrontPass(RenderJob &J) {
         rc.countAlive = check ? 1 : 0;
         rc.draining = drainingSeen ? 1u : 0u;
         if (J.timing) J.evShade.record(stream);
-        if (wf.vertexWide) hipLaunchKernelGGL(wf.vertexWide, wf.vertexGrid, dim3(BLOCK), wf.vertexLds, stream, J.D, J.P, rc, sd.L.p, wf.traceNodeCache);
+        if (wf.vertexRays) hipLaunchKernelGGL(wf.vertexRays, wf.vertexGrid, dim3(BLOCK), wf.vertexLds, stream, J.D, J.P, rc, sd.L.p, wf.rays);
+        else if (wf.vertexWide) hipLaunchKernelGGL(wf.vertexWide, wf.vertexGrid, dim3(BLOCK), wf.vertexLds, stream, J.D, J.P, rc, sd.L.p, wf.traceNodeCache);
         else hipLaunchKernelGGL(wf.vertex, wf.vertexGrid, dim3(BLOCK), wf.vertexLds, stream, J.D, J.P, rc, sd.L.p);
         if (J.timing) J.evShade.record(stream);
         if (!wf.shadeTrace) launchRayKernels(J);        /* (k_shade_trace traced both rays of the iteration itself: k_shade_trace.h) */
@@ -770,7 +774,9 @@ static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params
     shardTiles(J, shardIndex, shardCount);
     J.stream = (p->n_devices <= 1) ? (hipStream_t) p->stream : nullptr;    /* a caller's stream belongs to one device */
     if (!J.stream) { if (!sd.stream) HIP_TRY(hipStreamCreate(&sd.stream)); J.stream = sd.stream; }
-    planPasses(J);
+    planPasses(J, (unsigned long long) sd.nLocalTiles * ((unsigned long long) J.bs * J.bs));
+    if (J.keepSamples) { sd.sampleOut.alloc((size_t) J.W * J.H * (size_t) p->spp); HIP_TRY(hipMemsetAsync(sd.sampleOut.p, 0, sd.sampleOut.n * sizeof(float4), J.stream)); }
+    sd.haveSamples = J.keepSamples; sd.lastSpp = (uint32_t) p->spp;
     if (p->sampler == PHIP_SAMPLER_SOBOL) uploadSobolTables(J);
     if (J.rinv) uploadRinvTables(J);
     planFused(J);

@@ -138,7 +138,11 @@ struct SceneDev {
     DevBuf<unsigned int> drawCounters;                                                       /* k_rays_w, k_raycast_p: 2 x RAY_SHARDS sharded work counters */
     /* phip_trace_device (host_raycast.h): the persistent ray server's kernels, LDS plan and resident grid, resolved for a tree whose node cache is `nodeCache` */
     struct RaycastPlan { RaycastKernels k = { nullptr, nullptr }; uint32_t nodeCache = 0; size_t lds = 0; unsigned blocks = 0; } raycast;
-    DevBuf<float> film, patchImg;                                                            /* patchImg: k_film_splat's 16 x 16 patch images (k_film.h) */
+    /* phip_radiance_device (host_radiance.h): k_shade_r without / with strictNormals and k_radiance_out, resolved at the scene's first call; the running float64 sums of
+       a call that takes several passes, two double2 per ray -- the one buffer of that call that grows with its ray count */
+    struct RadiancePlan { ShadeRaysKernel vertex[2] = { nullptr, nullptr }; RadianceOutKernel out = nullptr; } radiance;
+    DevBuf<double2> radianceAcc;
+    DevBuf<float> film, patchImg;                                                           /* patchImg: k_film_splat's 16 x 16 patch images (k_film.h) */
     uint32_t lastSpp = 0, nLocalTiles = 0; unsigned long long localPixels = 0;
     int tileKey[3] = { -1, -1, -1 };
     bool haveSamples = false;

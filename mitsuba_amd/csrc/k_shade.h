@@ -40,7 +40,9 @@ __device__ __forceinline__ V2 cameraSample(const DevScene &S, const RenderConst 
 }
 
 /* The common tail of the shading kernels: the block's shadow-queue entries are compacted, slots whose sample ended start
- * the next camera sample in the same lane, blocks without work retire, per-wave statistics are recorded. */
+ * the next camera sample in the same lane, blocks without work retire, per-wave statistics are recorded.
+ * k_shade_r.h holds a COPY of this function, shadeEpilogueRays (the caller's ray array as the source of samples; why a copy: there): a change to the shadow compaction,
+ * the dynamic tail or the retirement is made in both -- tests/test_radiance_device_host.py compares the two texts outside the copy's lines marked "rays". */
 template <bool QMC>
 __device__ __forceinline__ void shadeEpilogue(const DevScene &S, const PathPool &P, const RenderConst &rc, uint32_t *waveCnt,
                                               const uint32_t slot, const bool inRange, uint4 info, const bool alive, bool needNew,
@@ -201,13 +203,14 @@ struct LRegister {
    next ray; v.state is updated whenever the path goes on.  A shadow-queue entry is returned in sh when pushShadow.
    FEAT: bit 0 = the scene has an environment emitter (constant / envmap), bit 1 = it has bitmap textures, bit 2 (k_shade only) = the
    emitter table and the materials are known to fit LDS (the kernel then reads them with ds_read instead of flat loads), bit 4 (k_shade only) =
-   the emitter table fits LDS, the materials stay in memory; MM: leaf BSDF models
+   the emitter table fits LDS, the materials stay in memory, bit 5 (k_shade_r only) = the sample's first ray is a caller's and has no differentials: its vertex reads
+   bitmap textures and a directly visible environment map as the later vertices do (level 0, bilinear); MM: leaf BSDF models
    present in the scene; STRICT: strictNormals (a compile-time switch: without it the geometric normal is dead after
    fillIntersection and the diffuse-only instantiation fits 80 VGPRs = 6 waves per SIMD) */
 template <int MM, bool STRICT, int FEAT, typename LAcc>
 __device__ __forceinline__ bool shadeVertex(const DevScene &S, const EmitterTab &T, const DevMaterial *materials, const RenderConst &rc,
                                             PathVertex &v, const LAcc &acc, bool &newRay, bool &pushShadow, ShadowEntry &sh, uint32_t &vertices) {
-    constexpr bool ENV = (FEAT & 1) != 0, TEX = (FEAT & 2) != 0, QMC = (FEAT & 8) != 0;
+    constexpr bool ENV = (FEAT & 1) != 0, TEX = (FEAT & 2) != 0, QMC = (FEAT & 8) != 0, NODIFF = (FEAT & 32) != 0;
     const uint32_t prim = pm_to_bits(v.hit.w);
     const V3 rayD(v.rayD.x, v.rayD.y, v.rayD.z);
     V3 thr(v.thr.x, v.thr.y, v.thr.z);
@@ -261,7 +264,7 @@ __device__ __forceinline__ bool shadeVertex(const DevScene &S, const EmitterTab 
             if (flags & F_FIRST) {
                 if (!rc.hideEmitters) {                                                    /* throughput is 1; alpha stays 0 */
                     V3 bg = value;
-                    if (rc.envFiltered) {
+                    if (!NODIFF && rc.envFiltered) {
                         /* the camera ray is the one ray with differentials: filtered lookup, envmap.cpp:395-407.
                            Its sample position is recomputed from the counter stream (a rare branch) */
                         const uint32_t px = v.pixel % (uint32_t) S.film.width, py = v.pixel / (uint32_t) S.film.width;
@@ -322,7 +325,7 @@ __device__ __forceinline__ bool shadeVertex(const DevScene &S, const EmitterTab 
             if (!VP) flags &= ~F_EMITTED;           /* rRec.type = ERadianceNoEmission (volpath_simple: the previous vertex decided, see below) */
             russianRoulette();
         }
-        const bool firstVertex = (flags & F_FIRST) != 0;
+        const bool firstVertex = !NODIFF && (flags & F_FIRST) != 0;
         flags &= ~F_FIRST;
 
         /* ---- head of the loop for this vertex, path.cpp:135-165 ---- */
@@ -565,6 +568,7 @@ __device__ __forceinline__ void dealSlotsByClass(unsigned char *xbuf /* SHADE_DE
     inRange = slot < P.capacity;
 }
 
+/* (k_shade_r.h holds a copy of this kernel's body with shadeEpilogueRays at its end: a change here is made there too; the same test compares the two) */
 template <int MM, bool STRICT, int FEAT> __global__ __launch_bounds__(BLOCK, MM == 0 ? SHADE_WAVES_LEAN : ((FEAT & 3) == 0 ? SHADE_WAVES_PLAIN : SHADE_WAVES)) void k_shade(DevScene S, PathPool P, RenderConst rc, float4 *L) {
     __shared__ uint32_t waveCnt[BLOCK / 64];
     __shared__ __align__(16) float ldsEm[EMITTER_LDS_FLOATS];

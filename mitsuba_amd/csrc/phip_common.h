@@ -2,7 +2,7 @@
  * phip_common.h -- what every translation unit of libphip.so starts with: HIP, the C ABI, the device scene layout and
  * shading functions (dv_scene.h), the path-pool layout (k_pool.h), the error macro.
  *
- * libphip.so is built from seven sources (37 objects) so that they compile in parallel:
+ * libphip.so is built from eight sources (45 objects) so that they compile in parallel:
  *   phip.hip          the C ABI + traversal and film kernels, with the host side it includes by concern: host_scene.h (scene build, replicas), host_render.h (kernel
  *                     selection, one device's render loop), host_multi.h (multi-device orchestration, RCCL): 1 object
  *   phip_shade.hip    k_shade / k_shade_direct / k_shade_trace instantiations behind the look-ups phipShade*KernelF<n> -- compiled per feature set (-DSHADE_FEAT=0..3, 8
@@ -13,6 +13,8 @@
  *   phip_update.hip   the kernels of phip_scene_update (k_update.h) behind phipUpdateKernels: 1 object
  *   phip_rebuild.hip  the kernels of phip_scene_rebuild (k_rebuild.h) behind phipRebuildKernels, and its two rocPRIM calls (sort, scan): 1 object
  *   phip_raycast.hip  the kernels of phip_trace_device (k_raycast.h) behind phipRaycastKernels: 1 object
+ *   phip_shade_r.hip  the kernels of phip_radiance_device (k_shade_r.h) behind phipShadeRaysKernelS<s>F<n> and phipRadianceOutKernel -- per feature set (-DSHADE_FEAT=0..3) and
+ *                     strictNormals (-DSHADE_PART=0 / 1): 8 objects
  * The other units hold kernels and the look-ups that return them, nothing else: every launch and every query of the runtime is in phip.hip and its host headers
  * (but for the launches inside rocPRIM's sort and scan, which phip_rebuild.hip wraps).
  * No device function is called across units (everything on the device side is inline in headers), so no -fgpu-rdc.
@@ -91,3 +93,15 @@ struct RaycastKernels {
     void (*surfaces)(DevScene, const float4 *, const float4 *, uint32_t, float4 *);
 };
 RaycastKernels phipRaycastKernels();
+/* the kernels of phip_radiance_device (phip_shade_r.hip, k_shade_r.h).  Per feature set n = 0..3 and strictNormals = 0 / 1 (compiled with -DSHADE_FEAT=n -DSHADE_PART=0 / 1):
+   k_shade_r<materials, strictNormals, FEAT> by the leaf BSDF models present and k_shade's table set; RaySamples, the ray array it draws its samples from, is an argument
+   of these kernels alone.  k_radiance_out: (L, acc, n, sppPass, spp, first, last, out, invalid) */
+struct RaySamples;
+typedef void (*ShadeRaysKernel)(DevScene, PathPool, RenderConst, float4 *, RaySamples);
+typedef void (*RadianceOutKernel)(const float4 *, double2 *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float4 *, unsigned long long *);
+#define PHIP_DECLARE_RADIANCE_KERNELS(n)                                                \
+    ShadeRaysKernel phipShadeRaysKernelS0F##n(int materialMask, int tables);            \
+    ShadeRaysKernel phipShadeRaysKernelS1F##n(int materialMask, int tables);
+PHIP_DECLARE_RADIANCE_KERNELS(0) PHIP_DECLARE_RADIANCE_KERNELS(1) PHIP_DECLARE_RADIANCE_KERNELS(2) PHIP_DECLARE_RADIANCE_KERNELS(3)
+#undef PHIP_DECLARE_RADIANCE_KERNELS
+RadianceOutKernel phipRadianceOutKernel();

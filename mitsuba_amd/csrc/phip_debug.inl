@@ -639,3 +639,11 @@ extern "C" int phip_debug_rccl_selftest(int n_devices, size_t n_floats) {
         return n;
     } catch (const std::exception &e) { return setErr(PHIP_ERR_DEVICE, e.what()); }
 }
+
+/* phip_radiance_device's checks of its arguments that need no device (host_radiance.h: radianceArgsError), for a machine without one: the code the entry point would
+   return for them, PHIP_OK when it would go on to the scene and the pointers' attributes; the message in phip_last_error */
+extern "C" int phip_debug_host_radiance_args(const phip_render_params *params, const phip_radiance_desc *desc) {
+    int code = PHIP_OK;
+    if (const char *bad = radianceArgsError(params, desc, code)) return setErr(code, std::string("phip_radiance_device: ") + bad);
+    return PHIP_OK;
+}

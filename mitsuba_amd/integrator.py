@@ -279,6 +279,29 @@ class PathHIP:
         """Renders this shard's blocks into device memory (e.g. a torch tensor) for an RCCL reduce."""
         return self._call("phip_render_device", scene, self.params(scene, spp, seed, shard_index, shard_count, flags, stream, **extra), C.c_void_p(d_out_ptr))
 
+    def radiance(self, scene, rays, spp, seed=0, stream_ids=None, first_stream=0, flags=0, stream=None, **extra):
+        """SamplingIntegrator::Li along the caller's rays (phip_radiance_device): rays is a contiguous float32 torch tensor of shape (n, 8) = o, mint, d, maxt on the
+        scene's device, read in place; the result is an (n, 4) float32 tensor of (R, G, B, alpha) on the same device, the mean of spp samples per ray.  Ray i draws
+        the counter stream of "pixel" stream_ids[i] (a contiguous int32 / uint32 tensor of n keys on the same device) or first_stream + i; extra: sample_offset,
+        sample_total.  `stream` is the stream the rays' producer ran on (a torch.cuda.Stream or a raw handle).  The call's statistics are kept in self.stats.
+        ValueError for a tensor of another dtype, layout or device; PhipError for what the library refuses; None if the call was cancelled."""
+        import torch
+        if not hasattr(rays, "data_ptr") or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError("rays: expected a contiguous float32 tensor of shape (n, 8)")
+        if not rays.is_cuda or (rays.device.index or 0) != scene.device:
+            raise ValueError("rays: the tensor is not on the scene's device")
+        n = rays.shape[0]
+        if stream_ids is not None:
+            if not hasattr(stream_ids, "data_ptr") or stream_ids.dtype not in (torch.int32, torch.uint32) or not stream_ids.is_contiguous() or tuple(stream_ids.shape) != (n,):
+                raise ValueError("stream_ids: expected a contiguous int32 or uint32 tensor of shape (n,)")
+            if stream_ids.device != rays.device:
+                raise ValueError("stream_ids: the tensor is not on the rays' device")
+        out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        p = self.params(scene, spp, seed, flags=flags, stream=getattr(stream, "cuda_stream", stream), **extra)
+        d = A.phip_radiance_desc(d_rays=rays.data_ptr() if n else None, n=n, d_stream=stream_ids.data_ptr() if stream_ids is not None and n else None,
+                                 first_stream=first_stream, reserved=0, d_out=out.data_ptr() if n else None)
+        return out if self._call("phip_radiance_device", scene, p, C.byref(d)) else None
+
     def samples(self, scene, spp):
         """Per-sample (R,G,B,alpha) of the last render made with PHIP_FLAG_SAMPLE_BUFFER: [y][x][sample]."""
         out = np.zeros((scene.height, scene.width, spp, 4), np.float32)
