@@ -447,16 +447,65 @@ int  phip_trace_device(phip_scene *scene, const phip_ray *d_rays, size_t n,
        film_kernel_ms, the time of the kernel that writes d_out.
    There is no fused path: the call runs the wavefront kernels, as a render with PHIP_FLAG_NO_FUSED does.  Its buffers are the scene's and are kept between calls; a
    call whose spp does not fit one pass (PHIP_MAX_PASS_SAMPLES, as for renders) splits spp over passes and keeps 32 bytes per ray of running sums, so that buffer, like
-   the 16 bytes per sample of a pass, grows with n. */
+   the 16 bytes per sample of a pass, grows with n.
+     Pairs (stream_layout = PHIP_RADIANCE_STREAM_PAIRS).  d_stream holds n pairs (key, sample) instead of n keys: sample k of ray i draws the stream of
+       (pixel = key, sample = sample + k), so the rays of one call need not share a sample index -- the camera samples of a whole render, as
+       phip_camera_rays_device writes them (d_rays, d_keys), are ONE call at spp = 1 instead of one call per sample.  d_stream must then not be NULL and is 8-byte
+       aligned, and params->sample_offset must be 0 (the index is the pair's): PHIP_ERR_INVALID otherwise, and for a layout other than 0 and 1. */
 typedef struct phip_radiance_desc {
     const phip_ray *d_rays;      /* n rays, device memory of the scene's device, 16-byte aligned; finite, not validated */
     size_t          n;
-    const uint32_t *d_stream;    /* NULL, or n stream keys: ray i draws the counter stream of "pixel" d_stream[i]; NULL = first_stream + i */
+    const uint32_t *d_stream;    /* NULL, or n stream keys: ray i draws the counter stream of "pixel" d_stream[i]; NULL = first_stream + i.  stream_layout 1: n pairs (key, sample) */
     uint32_t        first_stream;
-    uint32_t        reserved;
+    uint32_t        stream_layout; /* 0: d_stream holds keys; PHIP_RADIANCE_STREAM_PAIRS: pairs (was `reserved`, always 0: same layout) */
     float          *d_out;       /* n x (R, G, B, alpha) float32, device, 16-byte aligned */
 } phip_radiance_desc;
+#define PHIP_RADIANCE_STREAM_PAIRS 1u
 int  phip_radiance_device(phip_scene *scene, const phip_render_params *params, const phip_radiance_desc *desc, phip_stats *out_stats /* may be NULL */);
+
+/* The sensor as an entry point: the camera samples phip_render traces, written to DEVICE memory -- for callers that trace or shade them themselves
+   (phip_trace_device, phip_radiance_device) and put the results on the film with phip_film_device.  PHIP_SAMPLER_CTR only (PHIP_ERR_UNSUPPORTED for the others,
+   whose streams are addressed by film coordinates).
+     Samples.  Pixel i of the list (d_pixels[i], or i itself when d_pixels is NULL: every pixel of the crop window, row-major) and k in [0, spp): entry i * spp + k
+       is sample sample_offset + k of that pixel.  Its position on the film is (float32(x) + jx, float32(y) + jy) in crop coordinates, (jx, jy) the first two numbers
+       of block 0 of the counter stream of (pixel, sample, seed); its ray is the `perspective` camera's through that position, as the render generates it before it
+       clips it to the scene (phip_trace_device and phip_radiance_device clip a caller's ray with the same arithmetic).
+     Read from params: spp, sample_offset, seed, sampler, stream, device (n_devices = 1: devices[0]).
+     PHIP_ERR_INVALID: n_devices > 1, spp <= 0, a negative sample_offset, d_rays NULL, a host pointer, another device's pointer, a misaligned pointer, more than
+       2^32 - 256 samples, an entry of d_pixels that is not below crop_w * crop_h (the list is checked on the device before anything is written: after a refusal
+       the output buffers are untouched).  An empty list (d_pixels set, m == 0) returns PHIP_OK and touches nothing.
+     Ordering and locking, as for phip_trace_device: the work is ordered after params->stream, completion is synchronous on return, the call takes the scene's
+       render lock. */
+typedef struct phip_camera_rays_desc {
+    const uint32_t *d_pixels;   /* NULL: every pixel of the crop window, row-major; else m crop-pixel indices (y * crop_width + x), each < crop_w * crop_h */
+    size_t          m;          /* number of pixels (ignored when d_pixels is NULL) */
+    phip_ray       *d_rays;     /* m * spp rays, entry (i * spp + k): pixel i, sample sample_offset + k; 16-byte aligned */
+    uint32_t       *d_keys;     /* NULL, or m * spp pairs (stream key = the pixel index, sample index = sample_offset + k); 8-byte aligned */
+    float          *d_positions;/* NULL, or m * spp pairs: the sample's position on the film in crop coordinates, float32(x) + jitter; 8-byte aligned */
+} phip_camera_rays_desc;
+int  phip_camera_rays_device(phip_scene *scene, const phip_render_params *params, const phip_camera_rays_desc *desc);
+
+/* ImageBlock::put (include/mitsuba/render/imageblock.h:124-204) on a caller's per-sample values: d_out is the film phip_render_device would leave if sample
+   sample_offset + k of crop pixel (x, y) had carried d_values[y][x][k] -- the sample positions are derived again from the counter stream (not passed in), the
+   render blocks' bitmaps, their border, the clipped footprints and the filter table's look-up are the render's.  With phip_camera_rays_device and phip_trace_device
+   this is a filtered normal, depth or albedo buffer; with phip_radiance_device or the caller's own integrator, a render in parts.  PHIP_SAMPLER_CTR only.
+     Read from params: spp, sample_offset, seed, block_size, sampler, stream, device (n_devices = 1: devices[0]), PHIP_FLAG_ACCUMULATE (the sums are added to what
+       d_out holds), PHIP_FLAG_KERNEL_TIMING.
+     Validity.  flags = 0: a sample of which a value is not finite or negative is rejected whole and counted in invalid_samples, as the film rejects it;
+       PHIP_FILM_SIGNED: only a non-finite one is (normals, signed fields).
+     Deterministic: one lane per film pixel gathers the samples that reach it in a fixed order -- no float atomics, any filter radius, any spp, and no pass limit
+       (the buffer is the caller's).
+     PHIP_ERR_INVALID: shard_count > 1, n_devices > 1, spp <= 0, a negative sample_offset, a block size phip_render refuses, d_values or d_out NULL, not device
+       memory of the scene's device or not 16-byte aligned, an unknown flag.  Nothing is written after a refusal.
+     Stats: samples, invalid_samples, render_ms and -- under PHIP_FLAG_KERNEL_TIMING -- film_kernel_ms.  Ordering and locking as above. */
+typedef struct phip_film_desc {
+    const float *d_values;   /* crop_h * crop_w * spp x 4 float32, order [y][x][k] (phip_camera_rays_device's order with d_pixels NULL); 16-byte aligned */
+    float       *d_out;      /* crop_h * crop_w x 5: the four filtered sums and the weight, phip_render_device's layout; 16-byte aligned */
+    uint32_t     flags;      /* PHIP_FILM_SIGNED: reject only non-finite samples; 0: the film's own check (non-finite or negative) */
+    uint32_t     reserved;
+} phip_film_desc;
+#define PHIP_FILM_SIGNED 1u
+int  phip_film_device(phip_scene *scene, const phip_render_params *params, const phip_film_desc *desc, phip_stats *out_stats /* may be NULL */);
 
 /* Replicates the device-resident scene (geometry, acceleration structure, materials, textures) from the scene's device
    to each listed device (device-to-device copies over xGMI), so that a later multi-device render starts immediately. */
@@ -538,7 +587,7 @@ int  phip_scene_accel_info(const phip_scene *scene, phip_accel_info *out);
 /* Utilities for callers that fill a phip_scene_desc without Mitsuba at hand (the test harness, bench.py): the table of the reference's default `gaussian` reconstruction
  * filter with the given standard deviation -- (radius, PHIP_FILTER_RESOLUTION + 1 values), rfilter.cpp:38-57 + gaussian.cpp:34-57; the Mitsuba shim copies the scene's own
  * filter instead -- and sizeof of the ABI's structs by index (0 phip_material, 1 phip_shape, 2 phip_emitter, 3 phip_camera, 4 phip_film, 5 phip_scene_desc,
- * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info, 11 phip_update_desc, 12 phip_update_info, 13 phip_surface, 15 phip_radiance_desc; 14 is unassigned and answers 0: tests/test_raycast_device_host.py pins phip_abi_sizeof(14) == 0 as "one past the last struct" and stays as it is, so the new struct skips that index), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
+ * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info, 11 phip_update_desc, 12 phip_update_info, 13 phip_surface, 15 phip_radiance_desc; 14 is unassigned and answers 0: tests/test_raycast_device_host.py pins phip_abi_sizeof(14) == 0 as "one past the last struct" and stays as it is, so the new struct skips that index; 16 is unassigned likewise: tests/test_radiance_device_host.py pins it; 17 phip_camera_rays_desc, 18 phip_film_desc), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
 void   phip_gaussian_filter(float stddev, float *radius, float *table);
 size_t phip_abi_sizeof(int which);
 

@@ -156,6 +156,20 @@ class phip_radiance_desc(C.Structure):
     _fields_ = [("d_rays", C.c_void_p), ("n", C.c_size_t), ("d_stream", C.c_void_p), ("first_stream", C.c_uint32), ("reserved", C.c_uint32), ("d_out", C.c_void_p)]
 
 
+PHIP_RADIANCE_STREAM_PAIRS = 1       # phip_radiance_desc.stream_layout (the mirror keeps the field's earlier name, `reserved`): d_stream holds (key, sample) pairs
+
+
+class phip_camera_rays_desc(C.Structure):
+    _fields_ = [("d_pixels", C.c_void_p), ("m", C.c_size_t), ("d_rays", C.c_void_p), ("d_keys", C.c_void_p), ("d_positions", C.c_void_p)]
+
+
+class phip_film_desc(C.Structure):
+    _fields_ = [("d_values", C.c_void_p), ("d_out", C.c_void_p), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+PHIP_FILM_SIGNED = 1
+
+
 class phip_accel_info(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("n_triangle_refs", C.c_uint32),
                 ("max_depth", C.c_uint32), ("node_bytes", C.c_uint32), ("triangle_bytes", C.c_uint32),

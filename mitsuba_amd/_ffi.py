@@ -53,6 +53,8 @@ UNITS += [("phip_shade_r.hip", ["-DSHADE_FEAT=%d" % f, "-DSHADE_PART=%d" % q], "
 # phip_raycast.hip (the persistent ray server and the surface records of phip_trace_device, k_raycast.h): one small object, in front of the two units that
 # tests/test_scene_rebuild_host.py expects at the end of the list
 UNITS += [("phip_raycast.hip", [], "phip_raycast.o")]
+# phip_camera_film.hip (the camera samples of phip_camera_rays_device and the gather of phip_film_device, k_camera_film.h): one small object, inserted likewise
+UNITS += [("phip_camera_film.hip", [], "phip_camera_film.o")]
 # phip_update.hip (the refit kernels of phip_scene_update, k_update.h): one small object, appended likewise
 UNITS += [("phip_update.hip", [], "phip_update.o")]
 # phip_rebuild.hip (the device build of phip_scene_rebuild, k_rebuild.h, with rocPRIM's sort and scan): one object, appended likewise
@@ -140,6 +142,8 @@ def _build_locked(sid, out_lib, verbose):
             return 13.0
         if name.startswith("phip_raycast"):
             return 5.0
+        if name.startswith("phip_camera_film"):
+            return 3.0
         if name.startswith("phip_radiance"):
             return feat_cost.get(int(re.match(r"phip_radiance(\d)", name).group(1)), 20.0)
         return 31.0 if name.startswith("phip_mega") else 14.0
@@ -178,8 +182,8 @@ TEST_VARIANTS = {"fault": "-DMEGA_MB_FAULT=1",       # waves of fused launches r
                  "cap32": "-DWP_CAP=32u",            # 32-entry task stacks: nearly every push of a big scene spills to memory
                  "overflow": "-DWP_CAP=64u -DWP_SPILL_CAP=64u"}      # 128-entry task stacks, half of them spilled: the tree-in-memory scenes outgrow them -- the wave stops, the pass is re-rendered
 # sources whose objects a variant takes from the product build: its flags do not concern them (the task stacks are k_mega's and k_shade_trace_w's)
-VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip", "cap32": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip",
-                 "overflow": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip"}
+VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip", "cap32": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip",
+                 "overflow": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip"}
 
 
 def build_test_variant(tag):
@@ -223,6 +227,8 @@ def lib():
     L.phip_trace.argtypes = [C.c_void_p, C.POINTER(A.phip_ray), C.c_size_t, C.POINTER(A.phip_hit), u8p, C.POINTER(A.phip_stats)]
     L.phip_trace_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(A.phip_stats)]
     L.phip_radiance_device.argtypes = [C.c_void_p, C.POINTER(A.phip_render_params), C.POINTER(A.phip_radiance_desc), C.POINTER(A.phip_stats)]
+    L.phip_camera_rays_device.argtypes = [C.c_void_p, C.POINTER(A.phip_render_params), C.POINTER(A.phip_camera_rays_desc)]
+    L.phip_film_device.argtypes = [C.c_void_p, C.POINTER(A.phip_render_params), C.POINTER(A.phip_film_desc), C.POINTER(A.phip_stats)]
     L.phip_cancel.argtypes = [C.c_void_p]
     L.phip_scene_replicate.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
     L.phip_scene_update.argtypes = [C.c_void_p, C.POINTER(A.phip_update_desc), C.POINTER(A.phip_update_info)]
@@ -283,6 +289,8 @@ def debug_lib():
     L.phip_debug_host_rebuild_trace_wide.argtypes = L.phip_debug_host_refit_trace_wide.argtypes
     L.phip_debug_host_surfaces.argtypes = [C.POINTER(A.phip_scene_desc), C.POINTER(A.phip_ray), C.POINTER(A.phip_hit), C.c_size_t, C.POINTER(A.phip_surface)]
     L.phip_debug_host_radiance_args.argtypes = [C.POINTER(A.phip_render_params), C.POINTER(A.phip_radiance_desc)]
+    L.phip_debug_host_camera_rays_args.argtypes = [C.POINTER(A.phip_render_params), C.POINTER(A.phip_camera_rays_desc)]
+    L.phip_debug_host_film_args.argtypes = [C.POINTER(A.phip_render_params), C.POINTER(A.phip_film_desc)]
     L.phip_debug_fmath.argtypes = [C.c_int, C.c_int, C.c_size_t, fp, fp, fp]
     L.phip_debug_selected_kernel.argtypes = [C.c_int] * 7; L.phip_debug_selected_kernel.restype = C.c_char_p
     _debug = L

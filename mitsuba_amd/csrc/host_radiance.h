@@ -26,6 +26,12 @@ static const char *radianceArgsError(const phip_render_params *p, const phip_rad
         if (((uintptr_t) r->d_rays & 15u) || ((uintptr_t) r->d_out & 15u)) return "d_rays and d_out must be 16-byte aligned";
         if ((uintptr_t) r->d_stream & 3u) return "d_stream must be 4-byte aligned";
     }
+    if (r->stream_layout > PHIP_RADIANCE_STREAM_PAIRS) return "unknown stream_layout";
+    if (r->stream_layout == PHIP_RADIANCE_STREAM_PAIRS) {
+        if (p->sample_offset != 0) return "PHIP_RADIANCE_STREAM_PAIRS: the sample index is the pair's, sample_offset must be 0";
+        if (r->n && !r->d_stream) return "PHIP_RADIANCE_STREAM_PAIRS: d_stream must not be NULL";
+        if (r->n && ((uintptr_t) r->d_stream & 7u)) return "PHIP_RADIANCE_STREAM_PAIRS: d_stream must be 8-byte aligned";
+    }
     code = PHIP_ERR_UNSUPPORTED;
     if (p->integrator == PHIP_INTEGRATOR_DIRECT) return "PHIP_INTEGRATOR_DIRECT is not served: its sample arrays are addressed by film coordinates";
     if (p->sampler != PHIP_SAMPLER_CTR) return "PHIP_SAMPLER_CTR only: the other samplers' streams are addressed by film coordinates";
@@ -66,6 +72,7 @@ static int radianceDevice(phip_scene *sc, const phip_render_params *p, const phi
     setupWavefront(J, J.idsPerSpp * J.sppPerPass);
     J.wf.vertexRays = radianceVertexKernel(J);
     J.wf.rays.rays = (const float4 *) r->d_rays; J.wf.rays.stream = r->d_stream; J.wf.rays.firstStream = r->first_stream; J.wf.rays.n = (uint32_t) n;
+    J.wf.rays.pairs = r->stream_layout == PHIP_RADIANCE_STREAM_PAIRS ? 1u : 0u;
     callConstants(J);
     J.rc.envFiltered = 0;
     const bool onePass = J.sppPerPass >= (uint32_t) q.spp;

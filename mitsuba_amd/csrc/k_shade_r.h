@@ -11,10 +11,11 @@
  */
 #pragma once
 
-/* the sample source of k_shade_r: n rays of (o, mint | d, maxt), their stream keys (NULL: firstStream + ray index) */
+/* the sample source of k_shade_r: n rays of (o, mint | d, maxt), their stream keys (NULL: firstStream + ray index) -- or, with `pairs` (phip_radiance_desc::stream_layout
+   = PHIP_RADIANCE_STREAM_PAIRS), n pairs (key, sample): the ray's own sample index, on top of which the call's k counts (one 8-byte load in place of the 4-byte one) */
 struct RaySamples {
     static constexpr bool RAYS = true;
-    const float4 *rays; const uint32_t *stream; uint32_t firstStream, n;
+    const float4 *rays; const uint32_t *stream; uint32_t firstStream, n, pairs;
     /* the sample of id `id` (< rc.totalIds = n * rc.sppPass, so ray < n): its stream key, sample index and ray */
     __device__ __forceinline__ void sample(const RenderConst &rc, unsigned long long id, uint32_t &key, uint32_t &k, V3 &o, V3 &d, float &mint, float &maxt) const {
         const uint32_t r = (uint32_t) id;                           /* ids of a pass are < 2^32 */
@@ -24,7 +25,8 @@ struct RaySamples {
         k += rc.sppFirst;
         const float4 ro = rays[2 * (size_t) ray], rd = rays[2 * (size_t) ray + 1];
         o = V3(ro.x, ro.y, ro.z); d = V3(rd.x, rd.y, rd.z); mint = ro.w; maxt = rd.w;
-        key = stream ? stream[ray] : firstStream + ray;
+        if (pairs) { const uint2 ks = ((const uint2 *) stream)[ray]; key = ks.x; k += ks.y; }       /* (block-uniform: a kernel argument) */
+        else key = stream ? stream[ray] : firstStream + ray;
     }
 };
 

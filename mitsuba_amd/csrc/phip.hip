@@ -15,7 +15,7 @@
  *       iteration that shades a slot's vertex and traces its shadow ray and its next ray on the packed leaf table in LDS (k_shade_trace.h); scenes of that
  *       kind whose tree lives in L2: k_shade_trace_w, the same iteration on the 8-wide tree in memory (k_shade_trace_w.h)
  *
- * libphip.so is 45 objects of eight sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
+ * libphip.so is 46 objects of nine sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
  * at plan time (host_render.h -- shadeUnit: the one table over the feature sets; megaKernelOf -> FusedPlan::kernel in planFused, shadeKernelOf / shadeTraceWideKernelOf ->
  * WavefrontPlan::vertex / vertexWide in selectVertexKernel), asks the runtime for the residency of the persistent ones (residentBlocksPerCU) and launches them.
  * Kernels and where they live:
@@ -39,6 +39,8 @@
  *   k_rebuild.h   the new topology of phip_scene_rebuild: Morton keys, the binary radix tree, its collapse to the 8-wide layout level by level      [phip_rebuild.hip]
  *   k_raycast.h   phip_trace_device: k_raycast_p (k_wide.h's persistent loop on a caller's ray array), k_surfaces (the record at every hit)            [phip_raycast.hip]
  *   k_shade_r.h   phip_radiance_device: k_shade_r (k_shade with a caller's ray array as its source of samples), k_radiance_out (the mean of a ray's samples)  [phip_shade_r.hip]
+ *   k_camera_film.h  phip_camera_rays_device / phip_film_device: k_camera_rays (the camera samples of the counter stream), k_film_values (k_film's gather on a
+ *                 caller's per-sample values)                                                                                                              [phip_camera_film.hip]
  *
  * This file: the C ABI -- error state, the guard that maps what an entry point's body throws to its error code, the entry of both render functions, the film's way
  * to the host and the extern "C" entry points.  The rest of the host side is three headers by concern, each including the ones before it:
@@ -51,6 +53,8 @@
  *   host_raycast.h phip_trace_device: the persistent ray server's plan and launch on the caller's stream, the surface records behind it (k_raycast.h in phip_raycast.hip)
  *   host_radiance.h phip_radiance_device: a render job without a film over the caller's rays -- the passes and the pass loop of host_render.h, k_shade_r for k_shade,
  *                  k_radiance_out for the film pass (k_shade_r.h in phip_shade_r.hip)
+ *   host_camera_film.h phip_camera_rays_device and phip_film_device: the camera samples out, per-sample values onto a film -- validation before any launch
+ *                  (k_camera_film.h in phip_camera_film.hip)
  * Not MFMA work: irregular traversal and gathers.  The product never includes, links or calls anything under oracle/.
  */
 #include "phip_common.h"
@@ -84,6 +88,7 @@ static int setErr(int code, const std::string &msg) { g_err = msg; return code; 
 #include "host_update.h"
 #include "host_raycast.h"
 #include "host_radiance.h"
+#include "host_camera_film.h"
 
 /* Entry of both render functions: validation, the scene's render lock, single- or multi-device dispatch, the sticky
    cancellation flag (consumed by the call that observed it). */
@@ -395,6 +400,34 @@ int phip_radiance_device(phip_scene *scene, const phip_render_params *params, co
     });
 }
 
+int phip_camera_rays_device(phip_scene *scene, const phip_render_params *params, const phip_camera_rays_desc *desc) {
+    int code = PHIP_OK;
+    if (const char *bad = cameraRaysArgsError(params, desc, code)) return setErr(code, std::string("phip_camera_rays_device: ") + bad);
+    if (!scene) return setErr(PHIP_ERR_INVALID, "NULL argument");
+    if (desc->d_pixels && desc->m == 0) return PHIP_OK;
+    int nDev = phip_device_count();
+    if (nDev <= 0) return nDev == 0 ? setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback") : PHIP_ERR_DEVICE;
+    return guarded(RENDER_ERRORS, [&]() -> int {
+        HIP_TRY(hipSetDevice(scene->devs[0]->device));
+        std::lock_guard<std::mutex> lock(scene->renderLock);
+        return cameraRaysDevice(scene, params, desc);
+    });
+}
+
+int phip_film_device(phip_scene *scene, const phip_render_params *params, const phip_film_desc *desc, phip_stats *out_stats) {
+    int code = PHIP_OK;
+    if (const char *bad = filmArgsError(params, desc, code)) return setErr(code, std::string("phip_film_device: ") + bad);
+    if (!scene) return setErr(PHIP_ERR_INVALID, "NULL argument");
+    if (out_stats) memset(out_stats, 0, sizeof(*out_stats));
+    int nDev = phip_device_count();
+    if (nDev <= 0) return nDev == 0 ? setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback") : PHIP_ERR_DEVICE;
+    return guarded(RENDER_ERRORS, [&]() -> int {
+        HIP_TRY(hipSetDevice(scene->devs[0]->device));
+        std::lock_guard<std::mutex> lock(scene->renderLock);
+        return filmDevice(scene, params, desc, out_stats);
+    });
+}
+
 void phip_cancel(phip_scene *scene) { if (scene && scene->cancelFlag) __atomic_store_n(scene->cancelFlag, 1, __ATOMIC_RELAXED); }
 
 void phip_develop(const float *rgbaw, size_t n_pixels, float *out_rgb) {
@@ -452,6 +485,8 @@ size_t phip_abi_sizeof(int which) {
         case 12: return sizeof(phip_update_info);
         case 13: return sizeof(phip_surface);
         case 15: return sizeof(phip_radiance_desc);      /* (14 stays unassigned: see include/phip.h) */
+        case 17: return sizeof(phip_camera_rays_desc);   /* (16 likewise) */
+        case 18: return sizeof(phip_film_desc);
         default: return 0;
     }
 }

@@ -2,7 +2,7 @@
  * phip_common.h -- what every translation unit of libphip.so starts with: HIP, the C ABI, the device scene layout and
  * shading functions (dv_scene.h), the path-pool layout (k_pool.h), the error macro.
  *
- * libphip.so is built from eight sources (45 objects) so that they compile in parallel:
+ * libphip.so is built from nine sources (46 objects) so that they compile in parallel:
  *   phip.hip          the C ABI + traversal and film kernels, with the host side it includes by concern: host_scene.h (scene build, replicas), host_render.h (kernel
  *                     selection, one device's render loop), host_multi.h (multi-device orchestration, RCCL): 1 object
  *   phip_shade.hip    k_shade / k_shade_direct / k_shade_trace instantiations behind the look-ups phipShade*KernelF<n> -- compiled per feature set (-DSHADE_FEAT=0..3, 8
@@ -15,6 +15,7 @@
  *   phip_raycast.hip  the kernels of phip_trace_device (k_raycast.h) behind phipRaycastKernels: 1 object
  *   phip_shade_r.hip  the kernels of phip_radiance_device (k_shade_r.h) behind phipShadeRaysKernelS<s>F<n> and phipRadianceOutKernel -- per feature set (-DSHADE_FEAT=0..3) and
  *                     strictNormals (-DSHADE_PART=0 / 1): 8 objects
+ *   phip_camera_film.hip  the kernels of phip_camera_rays_device and phip_film_device (k_camera_film.h) behind phipCameraFilmKernels: 1 object
  * The other units hold kernels and the look-ups that return them, nothing else: every launch and every query of the runtime is in phip.hip and its host headers
  * (but for the launches inside rocPRIM's sort and scan, which phip_rebuild.hip wraps).
  * No device function is called across units (everything on the device side is inline in headers), so no -fgpu-rdc.
@@ -105,3 +106,11 @@ typedef void (*RadianceOutKernel)(const float4 *, double2 *, uint32_t, uint32_t,
 PHIP_DECLARE_RADIANCE_KERNELS(0) PHIP_DECLARE_RADIANCE_KERNELS(1) PHIP_DECLARE_RADIANCE_KERNELS(2) PHIP_DECLARE_RADIANCE_KERNELS(3)
 #undef PHIP_DECLARE_RADIANCE_KERNELS
 RadianceOutKernel phipRadianceOutKernel();
+/* the kernels of phip_camera_rays_device and phip_film_device (phip_camera_film.hip, k_camera_film.h): the check of a pixel list, the camera samples, and
+   ImageBlock::put on a caller's values without / with PHIP_FILM_SIGNED */
+struct CameraFilmKernels {
+    void (*pixelsCheck)(const uint32_t *, uint32_t, uint32_t, unsigned long long *);
+    void (*rays)(DevScene, RenderConst, const uint32_t *, uint32_t, float4 *, uint2 *, float2 *);
+    void (*film[2])(DevScene, RenderConst, const float4 *, float *, int, unsigned long long *);
+};
+CameraFilmKernels phipCameraFilmKernels();

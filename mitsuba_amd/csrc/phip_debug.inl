@@ -647,3 +647,15 @@ extern "C" int phip_debug_host_radiance_args(const phip_render_params *params, c
     if (const char *bad = radianceArgsError(params, desc, code)) return setErr(code, std::string("phip_radiance_device: ") + bad);
     return PHIP_OK;
 }
+
+/* ... and those of phip_camera_rays_device and phip_film_device (host_camera_film.h: cameraRaysArgsError, filmArgsError) */
+extern "C" int phip_debug_host_camera_rays_args(const phip_render_params *params, const phip_camera_rays_desc *desc) {
+    int code = PHIP_OK;
+    if (const char *bad = cameraRaysArgsError(params, desc, code)) return setErr(code, std::string("phip_camera_rays_device: ") + bad);
+    return PHIP_OK;
+}
+extern "C" int phip_debug_host_film_args(const phip_render_params *params, const phip_film_desc *desc) {
+    int code = PHIP_OK;
+    if (const char *bad = filmArgsError(params, desc, code)) return setErr(code, std::string("phip_film_device: ") + bad);
+    return PHIP_OK;
+}

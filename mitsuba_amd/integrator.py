@@ -101,6 +101,63 @@ class Scene:
             raise _ffi.PhipError(rc, "phip_trace_device")
         return hits, occ, surf, st
 
+    def _sensor_params(self, spp, seed, sample_offset, block_size, flags, stream):
+        return A.default_render_params(spp=spp, seed=seed, sample_offset=sample_offset, block_size=block_size or self.block_size, device=self.device, flags=flags,
+                                       stream=getattr(stream, "cuda_stream", stream))
+
+    def camera_rays(self, spp, seed=0, sample_offset=0, pixels=None, keys=True, positions=False, stream=None):
+        """The camera samples a render traces, on the device (phip_camera_rays_device): for every pixel of the crop window in row-major order -- or for the pixels
+        of `pixels`, a contiguous int32 / uint32 tensor of crop-pixel indices (y * width + x) on the scene's device -- and k in [0, spp), sample sample_offset + k
+        of the counter stream.  Returns (rays, keys, positions): torch tensors on the scene's device with one row per sample, pixel-major -- (n, 8) float32 = o, mint,
+        d, maxt as rayIntersectDevice and PathHIP.radiance read them; (n, 2) int32 (pixel, sample), the `pairs` of PathHIP.radiance; (n, 2) float32, the sample's
+        position on the film in crop coordinates -- or None where not asked for.  ValueError for a tensor of another dtype, layout or device; PhipError for what
+        the library refuses (an index outside the crop window: nothing is written)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if pixels is not None:
+            if not hasattr(pixels, "data_ptr") or pixels.dtype not in (torch.int32, torch.uint32) or not pixels.is_contiguous() or pixels.dim() != 1:
+                raise ValueError("pixels: expected a contiguous int32 or uint32 tensor of shape (m,)")
+            if not pixels.is_cuda or (pixels.device.index or 0) != self.device:
+                raise ValueError("pixels: the tensor is not on the scene's device")
+        m = self.width * self.height if pixels is None else pixels.shape[0]
+        n = m * spp
+        rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        k = torch.empty((n, 2), dtype=torch.int32, device=dev) if keys else None
+        pos = torch.empty((n, 2), dtype=torch.float32, device=dev) if positions else None
+        if n == 0:                                  # an empty list: nothing to ask the library for
+            return rays, k, pos
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        d = A.phip_camera_rays_desc(d_pixels=ptr(pixels), m=m, d_rays=ptr(rays), d_keys=ptr(k), d_positions=ptr(pos))
+        rc = self._L.phip_camera_rays_device(self._h, C.byref(self._sensor_params(spp, seed, sample_offset, None, 0, stream)), C.byref(d))
+        if rc != 0:
+            raise _ffi.PhipError(rc, "phip_camera_rays_device")
+        return rays, k, pos
+
+    def film(self, values, spp, seed=0, sample_offset=0, signed=False, out=None, accumulate=False, block_size=None, flags=0, stream=None):
+        """ImageBlock::put on the caller's per-sample values (phip_film_device): values is a contiguous float32 torch tensor of height * width * spp x 4 entries in
+        [y][x][k] order (camera_rays' order) on the scene's device; the result is the (height, width, 5) float32 film -- four filtered sums and the weight -- a
+        render would leave had its samples carried these values, at the samples' own positions.  signed: reject only non-finite samples (normals, signed
+        fields), not negative ones.  out: the film tensor to write (accumulate=True: to add to).  Returns (film, stats)."""
+        import torch
+        n = self.width * self.height * spp
+        if not hasattr(values, "data_ptr") or values.dtype != torch.float32 or not values.is_contiguous() or values.numel() != 4 * n or values.shape[-1] != 4:
+            raise ValueError("values: expected a contiguous float32 tensor of height * width * spp x 4 values")
+        if not values.is_cuda or (values.device.index or 0) != self.device:
+            raise ValueError("values: the tensor is not on the scene's device")
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate needs the film to add to (out=)")
+            out = torch.empty((self.height, self.width, 5), dtype=torch.float32, device=values.device)
+        elif not hasattr(out, "data_ptr") or out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (self.height, self.width, 5) or out.device != values.device:
+            raise ValueError("out: expected a contiguous float32 tensor of shape (height, width, 5) on the values' device")
+        d = A.phip_film_desc(d_values=values.data_ptr(), d_out=out.data_ptr(), flags=A.PHIP_FILM_SIGNED if signed else 0, reserved=0)
+        st = A.phip_stats()
+        p = self._sensor_params(spp, seed, sample_offset, block_size, flags | (A.PHIP_FLAG_ACCUMULATE if accumulate else 0), stream)
+        rc = self._L.phip_film_device(self._h, C.byref(p), C.byref(d), C.byref(st))
+        if rc != 0:
+            raise _ffi.PhipError(rc, "phip_film_device")
+        return out, st
+
     def replicate(self, devices):
         """Copies the device scene to further GPUs ahead of a multi-device render (phip_scene_replicate)."""
         arr = (C.c_int32 * len(devices))(*devices)
@@ -279,11 +336,13 @@ class PathHIP:
         """Renders this shard's blocks into device memory (e.g. a torch tensor) for an RCCL reduce."""
         return self._call("phip_render_device", scene, self.params(scene, spp, seed, shard_index, shard_count, flags, stream, **extra), C.c_void_p(d_out_ptr))
 
-    def radiance(self, scene, rays, spp, seed=0, stream_ids=None, first_stream=0, flags=0, stream=None, **extra):
+    def radiance(self, scene, rays, spp, seed=0, stream_ids=None, first_stream=0, flags=0, stream=None, pairs=None, **extra):
         """SamplingIntegrator::Li along the caller's rays (phip_radiance_device): rays is a contiguous float32 torch tensor of shape (n, 8) = o, mint, d, maxt on the
         scene's device, read in place; the result is an (n, 4) float32 tensor of (R, G, B, alpha) on the same device, the mean of spp samples per ray.  Ray i draws
         the counter stream of "pixel" stream_ids[i] (a contiguous int32 / uint32 tensor of n keys on the same device) or first_stream + i; extra: sample_offset,
-        sample_total.  `stream` is the stream the rays' producer ran on (a torch.cuda.Stream or a raw handle).  The call's statistics are kept in self.stats.
+        sample_total.  pairs (in place of stream_ids): a contiguous int32 / uint32 tensor of shape (n, 2) of (key, sample) -- Scene.camera_rays' keys --, sample k of
+        ray i then draws the stream of (key, sample + k), and sample_offset must be 0: the camera samples of a whole render are one call at spp = 1.
+        `stream` is the stream the rays' producer ran on (a torch.cuda.Stream or a raw handle).  The call's statistics are kept in self.stats.
         ValueError for a tensor of another dtype, layout or device; PhipError for what the library refuses; None if the call was cancelled."""
         import torch
         if not hasattr(rays, "data_ptr") or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
@@ -296,10 +355,18 @@ class PathHIP:
                 raise ValueError("stream_ids: expected a contiguous int32 or uint32 tensor of shape (n,)")
             if stream_ids.device != rays.device:
                 raise ValueError("stream_ids: the tensor is not on the rays' device")
+        if pairs is not None:
+            if stream_ids is not None:
+                raise ValueError("pairs and stream_ids are two layouts of one argument: pass one of them")
+            if not hasattr(pairs, "data_ptr") or pairs.dtype not in (torch.int32, torch.uint32) or not pairs.is_contiguous() or tuple(pairs.shape) != (n, 2):
+                raise ValueError("pairs: expected a contiguous int32 or uint32 tensor of shape (n, 2)")
+            if pairs.device != rays.device:
+                raise ValueError("pairs: the tensor is not on the rays' device")
+            stream_ids = pairs
         out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
         p = self.params(scene, spp, seed, flags=flags, stream=getattr(stream, "cuda_stream", stream), **extra)
         d = A.phip_radiance_desc(d_rays=rays.data_ptr() if n else None, n=n, d_stream=stream_ids.data_ptr() if stream_ids is not None and n else None,
-                                 first_stream=first_stream, reserved=0, d_out=out.data_ptr() if n else None)
+                                 first_stream=first_stream, reserved=A.PHIP_RADIANCE_STREAM_PAIRS if pairs is not None else 0, d_out=out.data_ptr() if n else None)
         return out if self._call("phip_radiance_device", scene, p, C.byref(d)) else None
 
     def samples(self, scene, spp):

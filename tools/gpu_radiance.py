@@ -2,7 +2,7 @@
 """phip_radiance_device on the procedural atrium's own primary rays against phip_render_device with PHIP_FLAG_NO_FUSED on the same samples, in one process on one
 GPU.  One JSON line is appended to profiles/radiance_device.jsonl (DESIGN.md 3.15 quotes it).
 
-    python tools/gpu_radiance.py [--mode radiance|render|both] [--out profiles/radiance_device.jsonl] [--width 1920] [--height 1080] [--spp 4] [--reps 5] [--warmup 2]
+    python tools/gpu_radiance.py [--mode radiance|render|both|parts] [--out profiles/radiance_device.jsonl] [--width 1920] [--height 1080] [--spp 4] [--reps 5] [--warmup 2]
                                  [--rays-file rays.npy] [--make-rays]
 
 The rays are the camera rays of samples 0 .. spp - 1 of every pixel, made on the host by the twins of the device's stream and camera (phip_debug_host_ctr_block,
@@ -14,7 +14,12 @@ repetitions after --warmup -- wall clock, and the HIP-event times of the vertex 
                              repetition's figure is the sum over its spp calls, which are spp passes with a pool of a quarter of the ids each)
   radiance_device            one call with spp samples per ray on the camera rays of sample 0: the same streams, but the spp samples of a pixel share their first
                              segment, so their first hits are more coherent than the render's (a caller's usual call: a ray and its spp)
---mode render runs at a commit that has no phip_radiance_device."""
+--mode render runs at a commit that has no phip_radiance_device.
+--mode parts needs no ray file: the camera samples are made on the device by phip_camera_rays_device (the same bits, tests/test_gpu_camera_film.py).
+Its lines, beside render_device_no_fused and radiance_device_per_sample measured again in the same process on the device-made rays:
+  camera_rays_device         phip_camera_rays_device making the width x height x spp samples with their keys (wall clock only: one kernel and a synchronisation)
+  radiance_device_pairs      ONE call of phip_radiance_device at spp = 1 with PHIP_RADIANCE_STREAM_PAIRS on those samples: the render's samples, one pool
+  film_device                phip_film_device putting that call's output on the film: its kernel's HIP-event time stands beside the render's film_kernel_ms"""
 import argparse
 import ctypes as C
 import json
@@ -73,7 +78,7 @@ def measure(calls, integ, reps, warmup):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", default="both", choices=("radiance", "render", "both"))
+    ap.add_argument("--mode", default="both", choices=("radiance", "render", "both", "parts"))
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "radiance_device.jsonl"))
     ap.add_argument("--width", type=int, default=1920); ap.add_argument("--height", type=int, default=1080); ap.add_argument("--spp", type=int, default=4)
     ap.add_argument("--reps", type=int, default=5); ap.add_argument("--warmup", type=int, default=2)
@@ -88,7 +93,7 @@ def main():
     integ = I.PathHIP()
     build = _ffi.lib().phip_build_id().decode()
     line = dict(scene="atrium", triangles=int(desc.n_triangles), width=w, height=h, spp=args.spp, reps=args.reps, warmup=args.warmup, build=build, device=torch.cuda.get_device_name(0))
-    if args.mode in ("render", "both"):
+    if args.mode in ("render", "both", "parts"):
         film = torch.empty((h, w, 5), dtype=torch.float32, device="cuda")
         flags = A.PHIP_FLAG_NO_FUSED | A.PHIP_FLAG_KERNEL_TIMING
         line["render_device_no_fused"] = measure([lambda: integ.render_device(gs, film.data_ptr(), args.spp, flags=flags)], integ, args.reps, args.warmup)
@@ -99,6 +104,26 @@ def main():
         per_sample = [(lambda k=k: integ.radiance(gs, t[k], 1, flags=A.PHIP_FLAG_KERNEL_TIMING, sample_offset=k, sample_total=args.spp)) for k in range(args.spp)]
         line["radiance_device_per_sample"] = measure(per_sample, integ, args.reps, args.warmup)
         line["radiance_device"] = measure([lambda: integ.radiance(gs, t[0], args.spp, flags=A.PHIP_FLAG_KERNEL_TIMING)], integ, args.reps, args.warmup)
+    if args.mode == "parts":
+        T = A.PHIP_FLAG_KERNEL_TIMING
+        made = {}
+        def make():
+            made["rays"], made["keys"], _ = gs.camera_rays(args.spp)
+            integ.stats = A.phip_stats()                    # (the call has no statistics: wall clock only)
+        line["camera_rays_device"] = measure([make], integ, args.reps, args.warmup)
+        rays, keys = made["rays"], made["keys"]
+        t = [rays.view(h * w, args.spp, 8)[:, k].contiguous() for k in range(args.spp)]
+        per_sample = [(lambda k=k: integ.radiance(gs, t[k], 1, flags=T, sample_offset=k, sample_total=args.spp)) for k in range(args.spp)]
+        line["radiance_device_per_sample"] = measure(per_sample, integ, args.reps, args.warmup)
+        del t
+        got = {}
+        def pairs():
+            got["L"] = integ.radiance(gs, rays, 1, flags=T, pairs=keys, sample_total=args.spp)
+        line["radiance_device_pairs"] = measure([pairs], integ, args.reps, args.warmup)
+        out_film = torch.empty((h, w, 5), dtype=torch.float32, device="cuda")
+        def put():
+            _, integ.stats = gs.film(got["L"], args.spp, out=out_film, flags=T)
+        line["film_device"] = measure([put], integ, args.reps, args.warmup)
     print(json.dumps(line))
     with open(args.out, "a") as out:
         out.write(json.dumps(line) + "\n")
