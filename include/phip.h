@@ -557,6 +557,43 @@ int  phip_scene_update(phip_scene *scene, const phip_update_desc *update, phip_u
    gain -- is served by phip_scene_update itself, with that call's refusals (the degenerate-at-creation triangle included) and its unchanged counts. */
 int  phip_scene_rebuild(phip_scene *scene, const phip_update_desc *update /* may be NULL */, phip_update_info *out_info /* may be NULL */);
 
+/* New materials, emitter radiances and sampling weights, texture contents and sampling settings and / or a new environment map for the scene as created: what a
+   surface or a light LOOKS like, in place (dimming a lamp, turning a wall to glass, an animated sky, a video texture) -- without the host builder, without
+   uploading the geometry again.  After the call every entry point behaves exactly as if the scene had been created from the original descriptor with these
+   materials, emitters, textures and environment map -- on top of whatever phip_scene_update and phip_scene_rebuild have done to vertices and camera so far:
+   per-sample radiance, film, the counters samples / closest_rays / shadow_rays / path_vertices / invalid_samples and phip_surface.material are the same bits.
+   What stays fixed: every count, the shape -> material and shape -> emitter assignment, emitter types, texture and environment-map sizes and level counts, the
+   film, the tree (phip_scene_accel_info does not change but for nothing).  Material TYPES may change, what `twosided` adapters nest included: the set of leaf
+   BSDF models may then be another one, and renders resolve other kernels from then on (material_mask_changed).
+   The call takes the scene's render lock (it serialises with renders), validates before it writes -- on any error the scene is unchanged: the environment map's
+   tables are built in fresh buffers and swapped in at the end, everything else is written after the last check -- and drops the replicas on other devices, which the
+   next multi-device render copies again.  A NULL desc, or one with all four pointers NULL, returns PHIP_OK and changes nothing.
+   Errors.  Every refusal is one the creation has, with the creation's message and PHIP_ERR_INVALID: a count that differs from the scene's, what phip_scene_create
+   refuses of a material array (an unknown BSDF type, a reflectance or a texture maximum -- the NEW texels' -- above 1, a `twosided` that nests a transmissive or a
+   later material, a texture id out of range, eta <= 0), an anisotropic BSDF on a shape without texture coordinates, an emitter whose type or shape is not the
+   creation's, a texture or environment map whose size or level count is not the creation's or that lacks a level pointer, a bad wrap mode or filter type, a black
+   or non-finite environment map, a singular to_world, an `envmap` for a scene without that emitter, device_pointers = 1 with memory that is not the scene's
+   device's.  An unsupported microfacet distribution is PHIP_ERR_UNSUPPORTED, as at creation.  PHIP_ERR_DEVICE without a GPU: there is no CPU fallback. */
+typedef struct phip_appearance_desc {
+    uint32_t n_materials, n_emitters, n_textures;   /* must equal the scene's counts when the matching pointer is set: PHIP_ERR_INVALID otherwise */
+    uint32_t device_pointers;      /* 0: every texel pointer below is host memory; 1: device memory of the scene's device */
+    const phip_material *materials;/* NULL = unchanged; else n_materials entries, host memory always */
+    const phip_emitter  *emitters; /* NULL = unchanged; else n_emitters entries, host memory always: radiance and sampling_weight are taken,
+                                      type and shape must be the creation's (PHIP_ERR_INVALID) */
+    const phip_texture  *textures; /* NULL = unchanged; else n_textures entries (host structs); an entry with width == 0 leaves that texture alone;
+                                      otherwise width, height and n_levels must be the creation's, every level pointer set, and texels, wrap modes,
+                                      filter type, max_anisotropy, uv scale / offset are replaced */
+    const phip_envmap   *envmap;   /* NULL = unchanged; else the scene must have a PHIP_EMITTER_ENVMAP emitter, width / height / n_levels the creation's;
+                                      texels, levels, scale and to_world are replaced */
+    void *stream;                  /* device_pointers = 1: the hipStream_t the producer ran on, or NULL; the call is ordered after it */
+} phip_appearance_desc;
+typedef struct phip_appearance_info {
+    double update_ms, kernel_ms;   /* host wall clock of the call; HIP-event time of its device work */
+    uint32_t material_mask_changed;/* 1: the set of leaf BSDF models changed, so renders resolve other kernels from now on */
+    uint32_t reserved;
+} phip_appearance_info;
+int phip_scene_update_appearance(phip_scene *scene, const phip_appearance_desc *desc, phip_appearance_info *out_info /* may be NULL */);
+
 /* Thread-safe and sticky, like Scheduler::cancel on a process (src/libcore/sched.cpp): a running phip_render returns
    PHIP_ERR_CANCELLED; a request that arrives before the render starts cancels that render.  The flag is consumed by the
    call that observes it. */

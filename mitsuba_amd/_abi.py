@@ -191,6 +191,19 @@ class phip_update_info(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class phip_appearance_desc(C.Structure):
+    _fields_ = [("n_materials", C.c_uint32), ("n_emitters", C.c_uint32), ("n_textures", C.c_uint32), ("device_pointers", C.c_uint32),
+                ("materials", C.POINTER(phip_material)), ("emitters", C.POINTER(phip_emitter)), ("textures", C.POINTER(phip_texture)),
+                ("envmap", C.POINTER(phip_envmap)), ("stream", C.c_void_p)]
+
+
+class phip_appearance_info(C.Structure):
+    _fields_ = [("update_ms", C.c_double), ("kernel_ms", C.c_double), ("material_mask_changed", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 def default_render_params(**kw):
     """MonteCarloIntegrator defaults (src/librender/integrator.cpp:190-225)."""
     p = phip_render_params()

@@ -55,6 +55,8 @@ UNITS += [("phip_shade_r.hip", ["-DSHADE_FEAT=%d" % f, "-DSHADE_PART=%d" % q], "
 UNITS += [("phip_raycast.hip", [], "phip_raycast.o")]
 # phip_camera_film.hip (the camera samples of phip_camera_rays_device and the gather of phip_film_device, k_camera_film.h): one small object, inserted likewise
 UNITS += [("phip_camera_film.hip", [], "phip_camera_film.o")]
+# phip_appearance.hip (the kernels of phip_scene_update_appearance, k_appearance.h): one small object, inserted likewise
+UNITS += [("phip_appearance.hip", [], "phip_appearance.o")]
 # phip_update.hip (the refit kernels of phip_scene_update, k_update.h): one small object, appended likewise
 UNITS += [("phip_update.hip", [], "phip_update.o")]
 # phip_rebuild.hip (the device build of phip_scene_rebuild, k_rebuild.h, with rocPRIM's sort and scan): one object, appended likewise
@@ -142,7 +144,7 @@ def _build_locked(sid, out_lib, verbose):
             return 13.0
         if name.startswith("phip_raycast"):
             return 5.0
-        if name.startswith("phip_camera_film"):
+        if name.startswith("phip_camera_film") or name.startswith("phip_appearance"):
             return 3.0
         if name.startswith("phip_radiance"):
             return feat_cost.get(int(re.match(r"phip_radiance(\d)", name).group(1)), 20.0)
@@ -182,8 +184,8 @@ TEST_VARIANTS = {"fault": "-DMEGA_MB_FAULT=1",       # waves of fused launches r
                  "cap32": "-DWP_CAP=32u",            # 32-entry task stacks: nearly every push of a big scene spills to memory
                  "overflow": "-DWP_CAP=64u -DWP_SPILL_CAP=64u"}      # 128-entry task stacks, half of them spilled: the tree-in-memory scenes outgrow them -- the wave stops, the pass is re-rendered
 # sources whose objects a variant takes from the product build: its flags do not concern them (the task stacks are k_mega's and k_shade_trace_w's)
-VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip", "cap32": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip",
-                 "overflow": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip"}
+VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip", "cap32": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip",
+                 "overflow": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip"}
 
 
 def build_test_variant(tag):
@@ -233,6 +235,7 @@ def lib():
     L.phip_scene_replicate.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
     L.phip_scene_update.argtypes = [C.c_void_p, C.POINTER(A.phip_update_desc), C.POINTER(A.phip_update_info)]
     L.phip_scene_rebuild.argtypes = [C.c_void_p, C.POINTER(A.phip_update_desc), C.POINTER(A.phip_update_info)]
+    L.phip_scene_update_appearance.argtypes = [C.c_void_p, C.POINTER(A.phip_appearance_desc), C.POINTER(A.phip_appearance_info)]
     L.phip_develop.argtypes = [fp, C.c_size_t, fp]
     L.phip_scene_accel_info.argtypes = [C.c_void_p, C.POINTER(A.phip_accel_info)]
     L.phip_gaussian_filter.argtypes = [C.c_float, fp, fp]
@@ -291,6 +294,8 @@ def debug_lib():
     L.phip_debug_host_radiance_args.argtypes = [C.POINTER(A.phip_render_params), C.POINTER(A.phip_radiance_desc)]
     L.phip_debug_host_camera_rays_args.argtypes = [C.POINTER(A.phip_render_params), C.POINTER(A.phip_camera_rays_desc)]
     L.phip_debug_host_film_args.argtypes = [C.POINTER(A.phip_render_params), C.POINTER(A.phip_film_desc)]
+    L.phip_debug_host_appearance_args.argtypes = [C.POINTER(A.phip_scene_desc), C.POINTER(A.phip_appearance_desc)]
+    L.phip_debug_host_envmap_cdf.argtypes = [C.POINTER(A.phip_envmap), fp, fp, fp, fp]
     L.phip_debug_fmath.argtypes = [C.c_int, C.c_int, C.c_size_t, fp, fp, fp]
     L.phip_debug_selected_kernel.argtypes = [C.c_int] * 7; L.phip_debug_selected_kernel.restype = C.c_char_p
     _debug = L

@@ -189,6 +189,14 @@ struct SceneUpdateState {
     std::vector<float> hostPositions;                /* device-pointer updates: the emitter meshes' vertex ranges, copied back */
     uint32_t nDegenerate = 0;
     bool onDevice = false;
+    /* phip_scene_update_appearance (host_appearance.h): what the creation knew of the scene's look and the call validates a new look against -- the shapes (material,
+       emitter, triangle range, normals / texture coordinates), the materials and emitters as last given, every texture's and the environment map's descriptor with
+       its level-0 maximum; on the device the triangle -> shape map and the per-shape table of the records pass, made by the first call */
+    struct Appearance {
+        std::vector<DevShape> shapes; std::vector<phip_material> materials; std::vector<phip_emitter> emitters;
+        std::vector<DevMipLevels> texDesc; std::vector<float> texMax; DevMipLevels envLevels; bool envIsMap = false;
+        DevBuf<uint32_t> dTriShape, dTexMax; DevBuf<detail::ShapeWords> dShapeWords; DevBuf<float> dScratch, dRowTerms, dRowSum;
+    } app;
     DevBuf<uint32_t> dIndices, dWRecPrim, dRecPrim, dHadRecord, dCounters; DevBuf<int32_t> dLeafRefs;
     DevBuf<float> dPositions, dNormals, dNodeBox, dSahTerm, dPartials; DevBuf<detail::RefitConsts> dConsts;
     /* phip_scene_rebuild (host_rebuild.h): from the first rebuild on the host vectors wRecPrim, hadRecord and wLevels above are what they were for -- the source of the
@@ -304,13 +312,76 @@ static void pyramidLevels(DevMipLevels &lv, int sx, int sy, uint32_t nLevels, in
 static void ewaWeightLut(float *lut) { for (int k = 0; k < 64; ++k) { const float r2 = (float) k / 63.0f; lut[k] = pm_expf(-2.0f * r2) - pm_expf(-2.0f); } }
 
 /* m_alphaU != m_alphaV as OBJECTS (one texture for both is isotropic, roughconductor.cpp:228-229); twosided.cpp:96-100 inherits the flag */
-static bool anisotropic(const phip_scene_desc &d, uint32_t m, int depth = 0) {
-    if (m >= d.n_materials || depth > 2) return false;
-    const phip_material &M = d.materials[m];
+static bool anisotropic(const phip_material *materials, uint32_t nMaterials, uint32_t m, int depth = 0) {
+    if (m >= nMaterials || depth > 2) return false;
+    const phip_material &M = materials[m];
     if (M.type == PHIP_BSDF_ROUGHCONDUCTOR)
         return (M.alpha_u_texture | M.alpha_v_texture) ? M.alpha_u_texture != M.alpha_v_texture : std::max(M.alpha_u, 1e-4f) != std::max(M.alpha_v, 1e-4f);
-    if (M.type == PHIP_BSDF_TWOSIDED) return anisotropic(d, M.nested[0], depth + 1) || anisotropic(d, M.nested[1], depth + 1);
+    if (M.type == PHIP_BSDF_TWOSIDED) return anisotropic(materials, nMaterials, M.nested[0], depth + 1) || anisotropic(materials, nMaterials, M.nested[1], depth + 1);
     return false;
+}
+/* TriMesh::computeUVTangents, trimesh.cpp:683-693: an anisotropic BSDF (roughconductor.cpp:196-200,230-231: the clamped
+   alphaU != alphaV) needs texture coordinates for its tangent frame -- an error there.  (DevShape::pad: the mesh has them) */
+static void requireTexcoordsOfAnisotropic(const phip_material *materials, uint32_t nMaterials, const std::vector<DevShape> &shapes) {
+    for (const DevShape &s : shapes)
+        if (!s.pad && anisotropic(materials, nMaterials, s.material))
+            throw std::runtime_error("computeUVTangents(): texture coordinates are required to generate tangent vectors (anisotropic BSDF on a shape without them)");
+}
+/* the leaf BSDF models present (MM_*): selects the instantiation of the shading kernels */
+static int materialMaskOf(const std::vector<DevMaterial> &mats) {
+    int mask = 0;
+    for (const DevMaterial &m : mats) {
+        if (m.type == PHIP_BSDF_ROUGHCONDUCTOR) mask |= MM_ROUGH;
+        if (m.type == PHIP_BSDF_DIELECTRIC) mask |= MM_DIELECTRIC;
+    }
+    return mask;
+}
+/* what the shading records of a shape's triangles say of its material: the leaf seen from either side (a `twosided` adapter's nested ids, or the material itself
+   twice), the material's flag bits (TS_MATERIAL_BITS), and the shade class of its Wald records -- 0 diffuse, 1 rough conductor, 2 dielectric, the heavier of the
+   two sides of a two-sided surface */
+static uint32_t shadeClassOf(const std::vector<DevMaterial> &mats, uint32_t front, uint32_t back) {
+    auto classOf = [&](uint32_t leaf) { const int t = mats[leaf].type; return t == PHIP_BSDF_ROUGHCONDUCTOR ? 1u : (t == PHIP_BSDF_DIELECTRIC ? 2u : 0u); };
+    const uint32_t a = classOf(front), b = classOf(back);
+    return (a == 1u || b == 1u) ? 1u : std::max(a, b);
+}
+static detail::ShapeWords shapeWordsOf(const std::vector<DevMaterial> &mats, uint32_t material) {
+    const DevMaterial &m = mats[material];
+    const bool twosided = m.type == PHIP_BSDF_TWOSIDED;
+    detail::ShapeWords w;
+    w.front = twosided ? m.nested0 : material; w.back = twosided ? m.nested1 : material;
+    w.flags = (twosided ? TS_TWOSIDED : 0u) | ((m.flags & MF_SMOOTH) ? TS_MF_SMOOTH : 0u) | ((m.flags & MF_TRANS_OR_BACK) ? TS_TRANS_OR_BACK : 0u);
+    w.cls = shadeClassOf(mats, w.front, w.back);
+    return w;
+}
+/* the emitter selection CDF (scene.cpp:375-381 + DiscreteDistribution::normalize): n + 1 entries; returns the normalization (0 for a sum that is not positive) */
+static float emitterCdfOf(const phip_emitter *emitters, uint32_t nEmitters, std::vector<float> &ecdf) {
+    ecdf.assign(1, 0.0f);
+    for (uint32_t i = 0; i < nEmitters; ++i) ecdf.push_back(ecdf.back() + emitters[i].sampling_weight);
+    float emNorm = 0;
+    if (nEmitters) {
+        const float sum = ecdf.back();
+        if (sum > 0) { emNorm = 1.0f / sum; for (size_t j = 1; j < ecdf.size(); ++j) ecdf[j] *= emNorm; ecdf.back() = 1.0f; }
+    }
+    return emNorm;
+}
+/* the sampling fields of a bitmap texture's descriptor (everything but the pyramid's sizes and offsets) */
+static void textureSampling(const phip_texture &t, DevMipLevels &lv) {
+    if (t.wrap_u > PHIP_WRAP_ONE || t.wrap_v > PHIP_WRAP_ONE || t.filter_type > PHIP_FILTER_EWA) throw std::runtime_error("bad texture wrap mode / filter type");
+    lv.bcu = t.wrap_u; lv.bcv = t.wrap_v; lv.filterType = t.filter_type; lv.maxAnisotropy = t.max_anisotropy;
+    lv.uvScale[0] = t.uv_scale[0]; lv.uvScale[1] = t.uv_scale[1]; lv.uvOffset[0] = t.uv_offset[0]; lv.uvOffset[1] = t.uv_offset[1];
+}
+/* the environment map's transforms, scale and normalization from its CDF's total (envmap.cpp:318-328), after the refusals of a map that cannot be sampled */
+static void envmapConstants(const phip_envmap &e, float rowSum, DevEnvMap &E) {
+    if (rowSum == 0) throw std::runtime_error("The environment map is completely black -- this is not allowed.");
+    if (!std::isfinite(rowSum)) throw std::runtime_error("The environment map contains an invalid floating point value (nan/inf) -- giving up.");
+    M4 tw, tl;
+    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) tw.m[i][j] = e.to_world[4 * i + j];
+    if (!m4invert(tw, tl)) throw std::runtime_error("envmap toWorld is singular");
+    const int w = (int) e.width, h = (int) e.height;
+    E.w = w; E.h = h; E.scale = e.scale;
+    E.normalization = 1.0f / (rowSum * (2 * PT_PI / w) * (PT_PI / h));
+    E.pixelSizeX = 2 * PT_PI / w; E.pixelSizeY = PT_PI / h;
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { E.toWorld[3 * i + j] = tw.m[i][j]; E.toLocal[3 * i + j] = tl.m[i][j]; }
 }
 
 /* TriMesh::prepareSamplingTable, trimesh.cpp:388-404 + DiscreteDistribution::normalize: the area CDF of a mesh's triangles (n + 1 entries); returns 1 / surface area */
@@ -362,6 +433,28 @@ static void wideTreePaths(phip_scene *sc, DevScene &D) {
     sc->fusedWide = (sc->wideOnly && !sc->hasTextures && D.envEmitter < 0 && sc->triShadeStride == TRISHADE_FLOAT4S && D.emitterTabSize <= EMITTER_LDS_FLOATS && addressable)
                   ? (D.nMaterials <= MATERIAL_LDS_MAX ? 4 : 5) : 0;
     sc->wideTrace = sc->wideOnly && addressable;
+}
+
+/* which device path serves the scene: fitsLds (k_mega on the LDS-resident tree), fusedWide (k_mega on the 8-wide tree), flatTrace (k_shade_trace), wideTrace (k_shade_trace_w);
+   the deal region at the front of k_mega's dynamic LDS, the lane deal of the shading kernels.
+   Reads the DevScene's counts (sceneConstants, flatLeafTable) and the material mask: phip_scene_update_appearance calls it again when the mask has changed */
+static void devicePathsOf(phip_scene *sc, DevScene &D, bool fitsLdsBase) {
+    const int mask = sc->materialMask;
+    sc->fitsLds = fitsLdsBase;                              /* (implies the packed leaf table: recordsInLds) */
+    /* round 6: the fused kernel on a tree that does not fit LDS (k_wide_wave.h) -- every scene on the 8-wide tree whose emitter table fits LDS and that needs none of the
+       feature sets k_mega is not compiled with (bitmap textures, an environment emitter) */
+    wideTreePaths(sc, D);
+    const bool traceable = D.flatMode >= 2 && D.emitterTabSize <= EMITTER_LDS_FLOATS && D.nMaterials <= MATERIAL_LDS_MAX;
+    sc->flatTrace = !sc->fitsLds && traceable; sc->flatTraceToo = sc->fitsLds && traceable;
+    /* k_mega deals the Wald tests of the packed table over the wave through LDS buffers at the front of its dynamic LDS
+       (k_traverse.h: traverseFlat2W); k_mega<MM_ALL> keeps its mailbox of copper vertices in MEGA_DEAL_DWORDS x BLOCK dwords of LDS that lie there too (k_mega.h) */
+    const uint32_t dealList = D.flatMode >= 2 ? (uint32_t) (((BLOCK / 64) * BAL_WAVE_BYTES + BLOCK * sizeof(uint32_t) - 1) / (BLOCK * sizeof(uint32_t))) : 0u;
+    const uint32_t mailbox = (sc->fitsLds && mask != 0) ? (uint32_t) MEGA_DEAL_DWORDS : 0u;
+    D.dealDwords = std::max(dealList, mailbox);
+    /* the lane deal of k_shade pays where the expensive model is rare: rough conductors (microfacet sampling: atrium, 8 % of the vertices,
+       k_shade -7 %); on a diffuse + dielectric mix the extra round trip costs more than the cheap Fresnel branch (glass room: +8 %).
+       k_shade_trace deals its lanes by BSDF model where there is more than one (the kernel traces its own rays and leaves the class in the hit word) */
+    D.shadeSort = ((mask & MM_ROUGH) || (traceable && mask != 0)) ? 1u : 0u;
 }
 
 /* One phip_scene_create: what the stages of buildScene hand to each other.  Every stage up to chooseDevicePaths works on host arrays and calls no HIP
@@ -434,8 +527,8 @@ struct SceneBuild {
         for (uint32_t i = 0; i < d.n_textures; ++i) {
             const phip_texture &t = d.textures[i];
             if (t.width == 0 || t.height == 0 || !t.levels[0]) throw std::runtime_error("texture without level 0");
-            if (t.wrap_u > PHIP_WRAP_ONE || t.wrap_v > PHIP_WRAP_ONE || t.filter_type > PHIP_FILTER_EWA) throw std::runtime_error("bad texture wrap mode / filter type");
             DevMipLevels &lv = texDesc[i]; memset(&lv, 0, sizeof(lv));
+            textureSampling(t, lv);
             pyramidLevels(lv, (int) t.width, (int) t.height, t.n_levels, PHIP_MIP_MAX_LEVELS, "texture");
             for (int l = 0; l < lv.nLevels; ++l) {
                 if (!t.levels[l]) throw std::runtime_error("texture: level pointer is NULL");
@@ -444,12 +537,10 @@ struct SceneBuild {
                 for (size_t k = 0; k < cnt; ++k) {
                     const float *c = t.levels[l] + 3 * k;
                     texTexels.push_back(make_float4(c[0], c[1], c[2], 0.0f));
-                    if (l == 0) texMax[i] = std::max(texMax[i], std::max(c[0], std::max(c[1], c[2])));
+                    if (l == 0) texMax[i] = detail::texelMaxStep(texMax[i], c[0], c[1], c[2]);
                 }
             }
             if (texTexels.size() >= (1ull << 32)) throw std::runtime_error("textures too large");
-            lv.bcu = t.wrap_u; lv.bcv = t.wrap_v; lv.filterType = t.filter_type; lv.maxAnisotropy = t.max_anisotropy;
-            lv.uvScale[0] = t.uv_scale[0]; lv.uvScale[1] = t.uv_scale[1]; lv.uvOffset[0] = t.uv_offset[0]; lv.uvOffset[1] = t.uv_offset[1];
             ewaWeightLut(lv.weightLut);
         }
         sc->hasTextures = d.n_textures > 0;
@@ -458,22 +549,13 @@ struct SceneBuild {
     /* DevMaterials, the leaf BSDF models present, the texture-coordinate requirement of anisotropic BSDFs */
     void materials() {
         mats = convertMaterials(d.materials, d.n_materials, &texMax);
-        /* TriMesh::computeUVTangents, trimesh.cpp:683-693: an anisotropic BSDF (roughconductor.cpp:196-200,230-231: the clamped
-           alphaU != alphaV) needs texture coordinates for its tangent frame -- an error there */
-        for (uint32_t i = 0; i < d.n_shapes; ++i)
-            if (!d.shapes[i].has_texcoords && anisotropic(d, d.shapes[i].material))
-                throw std::runtime_error("computeUVTangents(): texture coordinates are required to generate tangent vectors (anisotropic BSDF on a shape without them)");
-        sc->materialMask = 0;
-        for (const DevMaterial &m : mats) {
-            if (m.type == PHIP_BSDF_ROUGHCONDUCTOR) sc->materialMask |= MM_ROUGH;
-            if (m.type == PHIP_BSDF_DIELECTRIC) sc->materialMask |= MM_DIELECTRIC;
-        }
+        requireTexcoordsOfAnisotropic(d.materials, d.n_materials, shapes);
+        sc->materialMask = materialMaskOf(mats);
     }
 
     /* DevEmitters + selection pdf (scene.cpp:375-381), the single environment emitter */
     void emitterSelection() {
         ems.resize(d.n_emitters);
-        ecdf.assign(1, 0.0f);
         for (uint32_t i = 0; i < d.n_emitters; ++i) {
             const phip_emitter &e = d.emitters[i];
             if (e.type == PHIP_EMITTER_CONSTANT || e.type == PHIP_EMITTER_ENVMAP) {
@@ -485,12 +567,8 @@ struct SceneBuild {
             memset(&ems[i], 0, sizeof(DevEmitter));
             for (int k = 0; k < 3; ++k) ems[i].radiance[k] = e.radiance[k];
             ems[i].samplingWeight = e.sampling_weight; ems[i].shape = e.type == PHIP_EMITTER_AREA ? e.shape : 0xFFFFFFFFu;
-            ecdf.push_back(ecdf.back() + e.sampling_weight);
         }
-        if (d.n_emitters) {
-            const float sum = ecdf.back();
-            if (sum > 0) { emNorm = 1.0f / sum; for (size_t j = 1; j < ecdf.size(); ++j) ecdf[j] *= emNorm; ecdf.back() = 1.0f; }
-        }
+        emNorm = emitterCdfOf(d.emitters, d.n_emitters, ecdf);
     }
 
     /* acceleration structure (bvh.h) and the two limits of its encodings */
@@ -511,15 +589,14 @@ struct SceneBuild {
         ts.assign((size_t) stride * d.n_triangles, make_float4(0, 0, 0, 0));
         for (uint32_t i = 0; i < d.n_triangles; ++i) {
             const DevShape &sh = shapes[triShape[i]];
-            const DevMaterial &m = mats[sh.material];
             const uint32_t *ix = d.indices + 3 * (size_t) i;
             const V3 p0(d.positions[3 * ix[0]], d.positions[3 * ix[0] + 1], d.positions[3 * ix[0] + 2]);
             const V3 p1(d.positions[3 * ix[1]], d.positions[3 * ix[1] + 1], d.positions[3 * ix[1] + 2]);
             const V3 p2(d.positions[3 * ix[2]], d.positions[3 * ix[2] + 1], d.positions[3 * ix[2] + 2]);
-            const bool twosided = m.type == PHIP_BSDF_TWOSIDED, texcoords = sh.pad != 0;
-            const uint32_t front = twosided ? m.nested0 : sh.material, back = twosided ? m.nested1 : sh.material;     /* (tagShadeClasses reads them back from the record) */
-            uint32_t flags = (sh.hasNormals ? TS_VERTEX_NORMALS : 0u) | (twosided ? TS_TWOSIDED : 0u) | (texcoords ? TS_TEXCOORDS : 0u)
-                           | ((m.flags & MF_SMOOTH) ? TS_MF_SMOOTH : 0u) | ((m.flags & MF_TRANS_OR_BACK) ? TS_TRANS_OR_BACK : 0u);
+            const bool texcoords = sh.pad != 0;
+            const detail::ShapeWords mw = shapeWordsOf(mats, sh.material);
+            const uint32_t front = mw.front, back = mw.back;     /* (tagShadeClasses reads them back from the record) */
+            uint32_t flags = (sh.hasNormals ? TS_VERTEX_NORMALS : 0u) | (texcoords ? TS_TEXCOORDS : 0u) | mw.flags;
             float4 *r = ts.data() + (size_t) stride * i;
             V2 t0(0, 0), t1(0, 0), t2(0, 0);
             if (texcoords) {
@@ -552,12 +629,10 @@ struct SceneBuild {
     /* shade class of every triangle in the spare word of its Wald record(s): 0 diffuse, 1 rough conductor, 2 dielectric -- the heavier
        of the two sides of a two-sided surface; k_rays_w passes it on in the hit record and k_shade deals its lanes by it (k_pool.h) */
     void tagShadeClasses() {
-        auto classOf = [&](uint32_t leaf) { const int t = mats[leaf].type; return t == PHIP_BSDF_ROUGHCONDUCTOR ? 1u : (t == PHIP_BSDF_DIELECTRIC ? 2u : 0u); };
         std::vector<uint8_t> &cls = triClass; cls.assign(d.n_triangles, 0);
         for (uint32_t i = 0; i < d.n_triangles; ++i) {
             const float4 *r = ts.data() + (size_t) stride * i;          /* front and back material: shadingRecords */
-            const uint32_t a = classOf(pm_to_bits(r[0].w)), b = classOf(pm_to_bits(r[1].w));
-            cls[i] = (uint8_t) ((a == 1u || b == 1u) ? 1u : std::max(a, b));
+            cls[i] = (uint8_t) shadeClassOf(mats, pm_to_bits(r[0].w), pm_to_bits(r[1].w));
         }
         for (std::vector<float> *recs : { &sc->bvh.tris, &sc->bvh.wtris })
             for (size_t r = 0; r + 12 <= recs->size(); r += 12) {
@@ -652,38 +727,11 @@ struct SceneBuild {
         sc->envLevelCount = lv.nLevels;
         std::vector<float> &cdfCols = envCdfCols, &cdfRows = envCdfRows, &rowWeights = envRowWeights;
         cdfCols.resize((size_t) (w + 1) * h); cdfRows.resize((size_t) h + 1); rowWeights.resize((size_t) h);
-        size_t colPos = 0, rowPos = 0;
-        float rowSum = 0.0f;
-        cdfRows[rowPos++] = 0;
-        for (int y = 0; y < h; ++y) {
-            float colSum = 0;
-            cdfCols[colPos++] = 0;
-            for (int x = 0; x < w; ++x) {
-                const float4 &t = tex[(size_t) y * w + x];
-                colSum += rgbLuminance(V3(t.x, t.y, t.z));
-                cdfCols[colPos++] = colSum;
-            }
-            const float norm = 1.0f / colSum;
-            for (int x = 1; x < w; ++x) cdfCols[colPos - x - 1] *= norm;
-            cdfCols[colPos - 1] = 1.0f;
-            float sn, cs; pm_sincosf((y + 0.5f) * PT_PI / h, &sn, &cs);
-            rowWeights[y] = sn;
-            rowSum += colSum * sn;
-            cdfRows[rowPos++] = rowSum;
-        }
-        const float norm = 1.0f / rowSum;
-        for (int y = 1; y < h; ++y) cdfRows[rowPos - y - 1] *= norm;
-        cdfRows[rowPos - 1] = 1.0f;
-        if (rowSum == 0) throw std::runtime_error("The environment map is completely black -- this is not allowed.");
-        if (!std::isfinite(rowSum)) throw std::runtime_error("The environment map contains an invalid floating point value (nan/inf) -- giving up.");
-        M4 tw, tl;
-        for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) tw.m[i][j] = e.to_world[4 * i + j];
-        if (!m4invert(tw, tl)) throw std::runtime_error("envmap toWorld is singular");
-        DevEnvMap &E = D.env;
-        E.w = w; E.h = h; E.scale = e.scale;
-        E.normalization = 1.0f / (rowSum * (2 * PT_PI / w) * (PT_PI / h));
-        E.pixelSizeX = 2 * PT_PI / w; E.pixelSizeY = PT_PI / h;
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { E.toWorld[3 * i + j] = tw.m[i][j]; E.toLocal[3 * i + j] = tl.m[i][j]; }
+        /* the conditional and the marginal CDF: appearance_hd.h, which the kernels of phip_scene_update_appearance run too */
+        std::vector<float> rowTerms((size_t) h);
+        for (int y = 0; y < h; ++y) rowTerms[y] = detail::envmapRowCdf(tex.data() + (size_t) y * w, w, h, y, cdfCols.data() + (size_t) y * (w + 1), &rowWeights[y]);
+        const float rowSum = detail::envmapMarginalCdf(rowTerms.data(), h, cdfRows.data());
+        envmapConstants(e, rowSum, D.env);
     }
 
     /* the plain-data fields of the DevScene: counts, box, camera, film; the scalar copy of the descriptor */
@@ -764,26 +812,7 @@ struct SceneBuild {
         D.flatMode = flat.empty() ? 0u : (sc->bvh.tris.size() / 12 <= 32 ? 2u : 3u); D.nFlatLeaves = (uint32_t) (flat.size() / 2);
     }
 
-    /* which device path serves the scene: fitsLds (k_mega on the LDS-resident tree), fusedWide (k_mega on the 8-wide tree), flatTrace (k_shade_trace), wideTrace (k_shade_trace_w);
-       the deal region at the front of k_mega's dynamic LDS, the lane deal of the shading kernels */
-    void chooseDevicePaths() {
-        const int mask = sc->materialMask;
-        sc->fitsLds = fitsLdsBase;                              /* (implies the packed leaf table: recordsInLds) */
-        /* round 6: the fused kernel on a tree that does not fit LDS (k_wide_wave.h) -- every scene on the 8-wide tree whose emitter table fits LDS and that needs none of the
-           feature sets k_mega is not compiled with (bitmap textures, an environment emitter) */
-        wideTreePaths(sc, D);
-        const bool traceable = D.flatMode >= 2 && tab.size() <= EMITTER_LDS_FLOATS && mats.size() <= MATERIAL_LDS_MAX;
-        sc->flatTrace = !sc->fitsLds && traceable; sc->flatTraceToo = sc->fitsLds && traceable;
-        /* k_mega deals the Wald tests of the packed table over the wave through LDS buffers at the front of its dynamic LDS
-           (k_traverse.h: traverseFlat2W); k_mega<MM_ALL> keeps its mailbox of copper vertices in MEGA_DEAL_DWORDS x BLOCK dwords of LDS that lie there too (k_mega.h) */
-        const uint32_t dealList = D.flatMode >= 2 ? (uint32_t) (((BLOCK / 64) * BAL_WAVE_BYTES + BLOCK * sizeof(uint32_t) - 1) / (BLOCK * sizeof(uint32_t))) : 0u;
-        const uint32_t mailbox = (sc->fitsLds && mask != 0) ? (uint32_t) MEGA_DEAL_DWORDS : 0u;
-        D.dealDwords = std::max(dealList, mailbox);
-        /* the lane deal of k_shade pays where the expensive model is rare: rough conductors (microfacet sampling: atrium, 8 % of the vertices,
-           k_shade -7 %); on a diffuse + dielectric mix the extra round trip costs more than the cheap Fresnel branch (glass room: +8 %).
-           k_shade_trace deals its lanes by BSDF model where there is more than one (the kernel traces its own rays and leaves the class in the hit word) */
-        D.shadeSort = ((mask & MM_ROUGH) || (traceable && mask != 0)) ? 1u : 0u;
-    }
+    void chooseDevicePaths() { devicePathsOf(sc, D, fitsLdsBase); }
 
     /* the topology a later phip_scene_update keeps fixed (SceneUpdateState); before uploadScene releases the builder's arrays */
     void keepForUpdate() {
@@ -811,6 +840,13 @@ struct SceneBuild {
             U.emitterMeshes.push_back(m);
         }
         U.tab = tab; U.ecdfSize = ecdf.size();
+        keepAppearance();
+    }
+    /* ... and the look a later phip_scene_update_appearance starts from (SceneUpdateState::Appearance); host arrays only */
+    void keepAppearance() {
+        SceneUpdateState::Appearance &P = sc->upd.app;
+        P.shapes = shapes; P.texDesc = texDesc; P.texMax = texMax; P.envLevels = envLevels; P.envIsMap = envIsMap;
+        P.materials.assign(d.materials, d.materials + (d.materials ? d.n_materials : 0)); P.emitters.assign(d.emitters, d.emitters + (d.emitters ? d.n_emitters : 0));
     }
 
     /* every immutable scene buffer of the device (placeholders where a kernel argument must not be NULL), the DevScene's pointers, the per-device counters */

@@ -15,7 +15,7 @@
  *       iteration that shades a slot's vertex and traces its shadow ray and its next ray on the packed leaf table in LDS (k_shade_trace.h); scenes of that
  *       kind whose tree lives in L2: k_shade_trace_w, the same iteration on the 8-wide tree in memory (k_shade_trace_w.h)
  *
- * libphip.so is 46 objects of nine sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
+ * libphip.so is 47 objects of ten sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
  * at plan time (host_render.h -- shadeUnit: the one table over the feature sets; megaKernelOf -> FusedPlan::kernel in planFused, shadeKernelOf / shadeTraceWideKernelOf ->
  * WavefrontPlan::vertex / vertexWide in selectVertexKernel), asks the runtime for the residency of the persistent ones (residentBlocksPerCU) and launches them.
  * Kernels and where they live:
@@ -37,6 +37,8 @@
  *                 k_reduce_stats, k_export_samples                                                                [this unit]
  *   k_update.h    the refit of phip_scene_update: check, shading and Wald records, scene box, the 8-wide tree level by level, the leaf table   [phip_update.hip]
  *   k_rebuild.h   the new topology of phip_scene_rebuild: Morton keys, the binary radix tree, its collapse to the 8-wide layout level by level      [phip_rebuild.hip]
+ *   k_appearance.h  phip_scene_update_appearance: the texel maximum and conversion, the environment map's CDFs, the material words of the shading records, the shade
+ *                 classes of the Wald records (appearance_hd.h: the arithmetic the creation shares)                                                          [phip_appearance.hip]
  *   k_raycast.h   phip_trace_device: k_raycast_p (k_wide.h's persistent loop on a caller's ray array), k_surfaces (the record at every hit)            [phip_raycast.hip]
  *   k_shade_r.h   phip_radiance_device: k_shade_r (k_shade with a caller's ray array as its source of samples), k_radiance_out (the mean of a ray's samples)  [phip_shade_r.hip]
  *   k_camera_film.h  phip_camera_rays_device / phip_film_device: k_camera_rays (the camera samples of the counter stream), k_film_values (k_film's gather on a
@@ -50,6 +52,8 @@
  *   host_multi.h   the multi-device orchestration (one host thread + stream per GPU, ncclReduce of the films over RCCL/xGMI)
  *   host_update.h  phip_scene_update: new vertices and camera on the tree as built (the kernels: k_update.h in phip_update.hip); with host_rebuild.h, which it
  *                  includes, phip_scene_rebuild: the same on a new tree built on the device (k_rebuild.h in phip_rebuild.hip)
+ *   host_appearance.h phip_scene_update_appearance: new materials, emitters, textures and environment map on the scene as created -- the creation's material and
+ *                  emitter stages, then the records, texels and CDFs in place (the kernels: k_appearance.h in phip_appearance.hip)
  *   host_raycast.h phip_trace_device: the persistent ray server's plan and launch on the caller's stream, the surface records behind it (k_raycast.h in phip_raycast.hip)
  *   host_radiance.h phip_radiance_device: a render job without a film over the caller's rays -- the passes and the pass loop of host_render.h, k_shade_r for k_shade,
  *                  k_radiance_out for the film pass (k_shade_r.h in phip_shade_r.hip)
@@ -67,6 +71,7 @@
 #include "k_shade_trace.h"
 #include "k_shade_trace_w.h"     /* (for shadeTraceWideLdsBytes: the kernels of these three headers are templates that this unit does not instantiate) */
 #include "k_shade_r.h"           /* (for RaySamples, the argument of k_shade_r: likewise) */
+#include "appearance_hd.h"      /* (the arithmetic host_scene.h shares with the kernels of phip_appearance.hip, which this unit does not hold) */
 #ifndef PHIP_DEBUG_HOOKS
 #define PHIP_DEBUG_HOOKS 0
 #endif
@@ -86,6 +91,7 @@ static int setErr(int code, const std::string &msg) { g_err = msg; return code; 
 #include "host_render.h"
 #include "host_multi.h"
 #include "host_update.h"
+#include "host_appearance.h"
 #include "host_raycast.h"
 #include "host_radiance.h"
 #include "host_camera_film.h"
@@ -121,7 +127,7 @@ static int renderImpl(phip_scene *sc, const phip_render_params *p, float *dOut, 
 struct ErrorCodes { int invalid, other; };
 static const ErrorCodes CREATE_ERRORS = { PHIP_ERR_UNSUPPORTED, PHIP_ERR_INVALID };     /* phip_scene_create: a scene the back end does not serve / a malformed one */
 static const ErrorCodes RENDER_ERRORS = { PHIP_ERR_INVALID, PHIP_ERR_DEVICE };          /* phip_render, phip_render_device: a bad argument / the runtime */
-static const ErrorCodes DEVICE_ERRORS = { PHIP_ERR_DEVICE, PHIP_ERR_DEVICE };           /* phip_scene_replicate, phip_scene_update, phip_scene_rebuild, phip_film_to_host, phip_trace, phip_trace_device: their bodies check arguments themselves */
+static const ErrorCodes DEVICE_ERRORS = { PHIP_ERR_DEVICE, PHIP_ERR_DEVICE };           /* phip_scene_replicate, phip_scene_update, phip_scene_rebuild, phip_scene_update_appearance, phip_film_to_host, phip_trace, phip_trace_device: their bodies check arguments themselves */
 template <typename Body> static int guarded(const ErrorCodes &codes, Body body) {
     try {
         return body();
@@ -201,6 +207,18 @@ int phip_scene_rebuild(phip_scene *scene, const phip_update_desc *u, phip_update
         phip_update_desc none; memset(&none, 0, sizeof(none));          /* update == NULL: the scene's current vertices and camera */
         /* a scene of at most 64 Wald records keeps its packed leaf table and the tree of its creation: the update serves it */
         return updateScene(scene, u ? *u : none, out_info, scene->wideOnly);
+    });
+}
+
+int phip_scene_update_appearance(phip_scene *scene, const phip_appearance_desc *desc, phip_appearance_info *out_info) {
+    if (!scene) return setErr(PHIP_ERR_INVALID, "NULL argument");
+    if (out_info) memset(out_info, 0, sizeof(*out_info));
+    if (appearanceEmpty(desc)) return PHIP_OK;          /* nothing to change */
+    int n = phip_device_count();
+    if (n <= 0) return n == 0 ? setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback") : PHIP_ERR_DEVICE;
+    return guarded(DEVICE_ERRORS, [&]() -> int {
+        std::lock_guard<std::mutex> lock(scene->renderLock);          /* serialises with renders */
+        return updateAppearance(scene, *desc, out_info);
     });
 }
 
@@ -487,6 +505,8 @@ size_t phip_abi_sizeof(int which) {
         case 15: return sizeof(phip_radiance_desc);      /* (14 stays unassigned: see include/phip.h) */
         case 17: return sizeof(phip_camera_rays_desc);   /* (16 likewise) */
         case 18: return sizeof(phip_film_desc);
+        case 20: return sizeof(phip_appearance_desc);    /* (19 likewise) */
+        case 21: return sizeof(phip_appearance_info);
         default: return 0;
     }
 }

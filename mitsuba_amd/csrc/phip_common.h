@@ -114,3 +114,14 @@ struct CameraFilmKernels {
     void (*film[2])(DevScene, RenderConst, const float4 *, float *, int, unsigned long long *);
 };
 CameraFilmKernels phipCameraFilmKernels();
+/* the kernels of phip_scene_update_appearance (phip_appearance.hip, k_appearance.h); ShapeWords (appearance_hd.h) is the per-shape table of the records pass */
+namespace pt { namespace detail { struct ShapeWords; } }
+struct AppearanceKernels {
+    void (*texmax)(const float *, uint32_t, uint32_t *);
+    void (*texels)(const float *, float4 *, uint32_t);
+    void (*envRows)(const float4 *, int, int, float *, float *, float *);
+    void (*envMarginal)(const float *, int, float *, float *);
+    void (*records)(float4 *, uint32_t, uint32_t, const uint32_t *, const pt::detail::ShapeWords *, uint8_t *);
+    void (*classes)(float4 *, const uint32_t *, uint32_t, const uint8_t *, uint32_t);
+};
+AppearanceKernels phipAppearanceKernels();

@@ -659,3 +659,56 @@ extern "C" int phip_debug_host_film_args(const phip_render_params *params, const
     if (const char *bad = filmArgsError(params, desc, code)) return setErr(code, std::string("phip_film_device: ") + bad);
     return PHIP_OK;
 }
+
+/* phip_scene_update_appearance's refusals on a machine without a device (host_appearance.h): the scene's look is taken from the descriptor of its creation by the
+   creation's host stages, the call's checks run on it -- with host pointers all of them, the textures' maxima and the environment map's CDF through the functions
+   of appearance_hd.h the kernels run; with device_pointers = 1 those that need no texel.  The code the entry point would return, the message in phip_last_error */
+extern "C" int phip_debug_host_appearance_args(const phip_scene_desc *created, const phip_appearance_desc *a) {
+    if (!created) return setErr(PHIP_ERR_INVALID, "NULL argument");
+    try {
+        phip_scene sc;
+        SceneBuild B(&sc, *created);
+        B.validateDesc();
+        B.flattenShapes(); B.packTextures(); B.materials(); B.emitterSelection(); B.buildEnvmap();
+        B.keepAppearance();
+        if (appearanceEmpty(a)) return PHIP_OK;
+        AppearanceLook L;
+        if (int rc = appearanceRefusal([&] { appearanceArgs(&sc, *a, L); })) return rc;
+        const SceneUpdateState::Appearance &P = sc.upd.app;
+        L.texMax = P.texMax;
+        if (a->textures && !a->device_pointers)
+            for (uint32_t i = 0; i < a->n_textures; ++i) {
+                if (!a->textures[i].width) continue;
+                float m = 0.0f;
+                const float *c = a->textures[i].levels[0];
+                for (size_t k = 0; k < (size_t) P.texDesc[i].lw[0] * P.texDesc[i].lh[0]; ++k) m = detail::texelMaxStep(m, c[3 * k], c[3 * k + 1], c[3 * k + 2]);
+                L.texMax[i] = m;
+            }
+        if (int rc = appearanceRefusal([&] { appearanceLook(&sc, *a, L); })) return rc;
+        if (a->envmap && !a->device_pointers) {
+            phip_scene_desc d2 = *created; d2.envmap = *a->envmap;
+            phip_scene sc2;
+            SceneBuild B2(&sc2, d2);
+            B2.envIsMap = true;
+            if (int rc = appearanceRefusal([&] { B2.buildEnvmap(); })) return rc;
+        }
+        return PHIP_OK;
+    } catch (const std::exception &e) { return setErr(PHIP_ERR_INVALID, e.what()); }
+}
+
+/* the environment map's sampling tables as phip_scene_create builds them (SceneBuild::buildEnvmap, around appearance_hd.h): cdf_cols (w + 1) * h, cdf_rows h + 1,
+   row_weights h floats, and the normalization */
+extern "C" int phip_debug_host_envmap_cdf(const phip_envmap *envmap, float *cdf_cols, float *cdf_rows, float *row_weights, float *normalization) {
+    if (!envmap || !cdf_cols || !cdf_rows || !row_weights || !normalization) return setErr(PHIP_ERR_INVALID, "NULL argument");
+    try {
+        phip_scene_desc d; memset(&d, 0, sizeof(d)); d.envmap = *envmap;
+        phip_scene sc;
+        SceneBuild B(&sc, d);
+        B.envIsMap = true;
+        B.buildEnvmap();
+        memcpy(cdf_cols, B.envCdfCols.data(), B.envCdfCols.size() * sizeof(float)); memcpy(cdf_rows, B.envCdfRows.data(), B.envCdfRows.size() * sizeof(float));
+        memcpy(row_weights, B.envRowWeights.data(), B.envRowWeights.size() * sizeof(float));
+        *normalization = sc.devs[0]->dev.env.normalization;
+        return PHIP_OK;
+    } catch (const std::exception &e) { return setErr(PHIP_ERR_INVALID, e.what()); }
+}

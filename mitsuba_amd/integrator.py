@@ -215,6 +215,86 @@ class Scene:
             self.desc.camera = camera
         return info
 
+    def update_appearance(self, materials=None, emitters=None, textures=None, envmap=None, stream=None):
+        """New materials, emitter radiances / sampling weights, texture contents and / or a new environment map on the scene as created, in place
+        (phip_scene_update_appearance): afterwards the scene is the one a fresh creation with this look would have given.
+        materials, emitters: sequences of phip_material / phip_emitter, one per material / emitter of the scene (emitter types and shapes stay).
+        textures: one entry per texture of the scene -- None leaves it alone; else a dict as SceneBuilder keeps it: "levels" (the pyramid, (h, w, 3) float32 each,
+        sizes as created) and optionally "wrap_u", "wrap_v", "filter", "aniso", "scale", "offset" (default: the creation's).
+        envmap: a dict with "levels" (level 0 first), and optionally "scale" and "to_world" (4 x 4; default: the creation's).
+        Texel arrays are numpy arrays (host memory) or contiguous float32 torch tensors on the scene's device, read in place (`stream`: the stream their producer
+        ran on); a mix of both is refused.  Returns the phip_appearance_info as a dict; PhipError on a refusal, the scene unchanged."""
+        d = self.desc
+        a = A.phip_appearance_desc()
+        keep, on_device = [], []
+
+        def texels(x, h, w, what):
+            if isinstance(x, np.ndarray) or not hasattr(x, "data_ptr"):
+                x = np.ascontiguousarray(x, dtype=np.float32)
+                if x.size != 3 * h * w:
+                    raise ValueError("%s: expected %d x %d x 3 values" % (what, h, w))
+                keep.append(x); on_device.append(False)
+                return C.cast(x.ctypes.data, C.POINTER(C.c_float))
+            import torch
+            if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != 3 * h * w:
+                raise ValueError("%s: expected a contiguous float32 tensor of %d x %d x 3 values" % (what, h, w))
+            if not x.is_cuda or (x.device.index or 0) != self.device:
+                raise ValueError("%s: the tensor is not on the scene's device" % what)
+            keep.append(x); on_device.append(True)
+            return C.cast(x.data_ptr(), C.POINTER(C.c_float))
+
+        def level_sizes(w, h, n):
+            out = [(h, w)]
+            while len(out) < n:
+                w, h = max(1, (w + 1) // 2), max(1, (h + 1) // 2)
+                out.append((h, w))
+            return out
+
+        if materials is not None:
+            arr = (A.phip_material * max(1, len(materials)))(*materials)
+            a.n_materials, a.materials = len(materials), arr
+            keep.append(arr)
+        if emitters is not None:
+            arr = (A.phip_emitter * max(1, len(emitters)))(*emitters)
+            a.n_emitters, a.emitters = len(emitters), arr
+            keep.append(arr)
+        if textures is not None:
+            arr = (A.phip_texture * max(1, len(textures)))()
+            for i, t in enumerate(textures):
+                if t is None or i >= d.n_textures:
+                    continue                                      # width 0: this texture stays (a wrong count is the library's to refuse)
+                old = d.textures[i]
+                arr[i].width, arr[i].height, arr[i].n_levels = old.width, old.height, len(t["levels"])
+                for l, (h, w) in enumerate(level_sizes(old.width, old.height, min(len(t["levels"]), A.PHIP_MIP_MAX_LEVELS))):
+                    arr[i].levels[l] = texels(t["levels"][l], h, w, "textures[%d] level %d" % (i, l))
+                arr[i].wrap_u, arr[i].wrap_v = t.get("wrap_u", old.wrap_u), t.get("wrap_v", old.wrap_v)
+                arr[i].filter_type, arr[i].max_anisotropy = t.get("filter", old.filter_type), t.get("aniso", old.max_anisotropy)
+                arr[i].uv_scale[:] = t.get("scale", tuple(old.uv_scale)); arr[i].uv_offset[:] = t.get("offset", tuple(old.uv_offset))
+            a.n_textures, a.textures = len(textures), arr
+            keep.append(arr)
+        if envmap is not None:
+            e = A.phip_envmap()
+            old = d.envmap
+            e.width, e.height, e.n_levels = old.width, old.height, len(envmap["levels"])
+            for l, (h, w) in enumerate(level_sizes(old.width, old.height, min(len(envmap["levels"]), A.PHIP_ENVMAP_MAX_LEVELS))):
+                e.levels[l] = texels(envmap["levels"][l], h, w, "envmap level %d" % l)
+            e.texels = e.levels[0]
+            e.scale = envmap.get("scale", old.scale)
+            e.to_world[:] = [float(v) for v in np.asarray(envmap["to_world"], np.float32).reshape(-1)] if "to_world" in envmap else list(old.to_world)
+            a.envmap = C.pointer(e)
+            keep.append(e)
+        if len(set(on_device)) > 1:
+            raise ValueError("texel arrays must all be host arrays or all be device tensors")
+        a.device_pointers = 1 if on_device and on_device[0] else 0
+        if stream is not None:
+            a.stream = getattr(stream, "cuda_stream", stream)
+        info = A.phip_appearance_info()
+        rc = self._L.phip_scene_update_appearance(self._h, C.byref(a), C.byref(info))
+        del keep                                                  # (held until the call has returned)
+        if rc != 0:
+            raise _ffi.PhipError(rc, "phip_scene_update_appearance")
+        return info.as_dict()
+
     def film_to_host(self, d_ptr, host_ptr):
         """a device-resident frame (render_device's output, e.g. after an RCCL reduce) to host memory, as phip_render delivers it"""
         rc = self._L.phip_film_to_host(self._h, C.c_void_p(d_ptr), C.c_void_p(host_ptr))
