@@ -433,7 +433,7 @@ int  phip_trace_device(phip_scene *scene, const phip_ray *d_rays, size_t n,
        integrator, PHIP_FLAG_KERNEL_TIMING.  Ignored: what concerns the film -- shards, block size, the progress callback (its totals are the film's),
        PHIP_FLAG_ENVMAP_BILINEAR_BACKGROUND, the flags that choose a fused kernel.  Refused, PHIP_ERR_INVALID: PHIP_FLAG_SAMPLE_BUFFER, PHIP_FLAG_ACCUMULATE.
      Differentials.  The caller's ray has none: a bitmap texture at the first vertex and a directly visible environment map are read the way later vertices read
-       them, level 0 and bilinear.  This is the one difference from a camera ray; on a scene without textures and without an envmap there is none, and sample k of a
+       them, level 0 and bilinear (phip_bsdf_device reads textured parameters the same way: bsdfTextures without partials).  This is the one difference from a camera ray; on a scene without textures and without an envmap there is none, and sample k of a
        ray equals sample k of the pixel whose camera ray it is and whose index (y * crop_width + x) is its key, bit for bit (PHIP_FLAG_SAMPLE_BUFFER, phip_get_samples).
      Output.  d_out[i].rgb is the float64 sum of the spp float32 sample values, in ascending k, divided by spp and rounded once to float32; d_out[i].alpha the same mean
        of the samples' alpha, 1 where the caller's ray hit and 0 where it did not.  A non-finite or negative sample is counted in invalid_samples and contributes
@@ -506,6 +506,88 @@ typedef struct phip_film_desc {
 } phip_film_desc;
 #define PHIP_FILM_SIGNED 1u
 int  phip_film_device(phip_scene *scene, const phip_render_params *params, const phip_film_desc *desc, phip_stats *out_stats /* may be NULL */);
+
+/* Shading in parts: what an integrator does between two ray casts, on DEVICE memory -- for the caller's own integrator over phip_camera_rays_device,
+   phip_trace_device and phip_film_device (ambient occlusion, a direct-lighting variant, path guiding, a learned sampler, the caller's own multiple importance
+   sampling).  The three calls are the reference's public interfaces: BSDF::eval / pdf / sample; Scene::sampleEmitterDirect without its visibility test;
+   Intersection::Le / Scene::evalEnvironment with Scene::pdfEmitterDirect.  Their arithmetic is the path integrator's own -- the device functions its vertex calls,
+   compiled with the product's flags -- so a value equals the one a render computes from the same inputs, bit for bit.
+     Conventions, those of phip_trace_device: every pointer is device memory of the scene's device and 16-byte aligned, arrays of 2 floats 8-byte aligned; a host
+       pointer, another device's pointer or a misaligned one is PHIP_ERR_INVALID and nothing is written.  n == 0 returns PHIP_OK and touches nothing; n is at most
+       2^32 - 256 (PHIP_ERR_INVALID beyond).  `stream` is the caller's hipStream_t or NULL: the work is ordered after it, completion is synchronous on return.
+       The calls take the scene's render lock and allocate nothing: inputs and outputs are the caller's.  Inputs are not validated for finiteness.
+       PHIP_ERR_INVALID for a NULL scene, a NULL desc or a NULL required pointer; PHIP_ERR_DEVICE without a GPU: there is no CPU fallback.  The message
+       (phip_last_error) starts with the function's name.  There are no render parameters, hence no n_devices: the scene's first device serves. */
+
+/* BSDF::eval / pdf / sample at the hits of a ray cast: d_rays and d_hits are what phip_trace_device read and wrote; wi is the shading frame's toLocal(-d).
+     Textures.  Textured parameters are read as later path vertices read them -- level 0, no UV partials -- the sentence of phip_radiance_device's "Differentials";
+       on a mesh without texture coordinates the coordinates are the hit's (u, v), as in phip_surface.uv.
+     Two-sided.  A `twosided` adapter is resolved by the side of arrival: its second nested model serves wi.z < 0 (phip_surface.material names the model).
+     A miss (prim == PHIP_NO_HIT; also a primitive index the scene does not have) writes zeros to every output asked for.
+     The integrator's strictNormals test is the integrator's and is not applied: phip_surface.ng is there for the caller's own.
+     PHIP_ERR_INVALID beside the conventions': no output asked for, d_eval without d_wo, d_sampled without d_samples, a flag other than PHIP_BSDF_LOCAL. */
+typedef struct phip_bsdf_sample {
+    float wo[3]; float pdf;            /* the sampled direction (world space; PHIP_BSDF_LOCAL: shading frame) and its density: solid angle, or discrete for a delta component */
+    float weight[3]; float eta;        /* value / pdf, cosine included, as BSDF::sample returns it; the relative index of refraction along the sampled direction (1: no refraction) */
+    uint32_t flags;                    /* PHIP_BSDF_SAMPLED_VALID | PHIP_BSDF_SAMPLED_DELTA */
+    uint32_t reserved[3];              /* 0 */
+} phip_bsdf_sample;                    /* 48 bytes; a failed sample (weight zero) is all zero */
+#define PHIP_BSDF_SAMPLED_DELTA 1u
+#define PHIP_BSDF_SAMPLED_VALID 2u
+#define PHIP_BSDF_LOCAL 1u             /* phip_bsdf_desc.flags: d_wo is read, and phip_bsdf_sample.wo written, in the shading frame instead of world space */
+typedef struct phip_bsdf_desc {
+    const phip_ray *d_rays;            /* n rays: their directions are read */
+    const phip_hit *d_hits;            /* n hits of those rays */
+    size_t          n;
+    const float    *d_wo;              /* NULL, or n x float4: xyz = the outgoing direction (w is not read) */
+    const float    *d_samples;         /* NULL, or n x float2 in [0, 1) */
+    float          *d_eval;            /* NULL, or n x float4: rgb = BSDF::eval in the solid-angle measure, cosine included; w = BSDF::pdf.  Needs d_wo */
+    phip_bsdf_sample *d_sampled;       /* NULL, or n records.  Needs d_samples */
+    float          *d_wi_local;        /* NULL, or n x float4: wi in the shading frame, w = 0 */
+    uint32_t        flags;             /* PHIP_BSDF_LOCAL or 0 */
+    uint32_t        reserved;
+    void           *stream;
+} phip_bsdf_desc;
+int  phip_bsdf_device(phip_scene *scene, const phip_bsdf_desc *desc);
+
+/* Scene::sampleEmitterDirect(dRec, sample, testVisibility = false): one emitter sample per reference point.  An environment emitter (`constant`, `envmap`) is
+   served; a scene without emitters writes "no sample" everywhere.  Visibility is the caller's next phip_trace_device call with d_occluded on d_shadow_rays: this
+   call traces nothing. */
+typedef struct phip_emitter_sample {
+    float d[3]; float dist;            /* unit direction from the reference point to the sampled position, and the distance */
+    float value[3]; float pdf;         /* radiance / pdf, the emitter selection probability included: sampleEmitterDirect's return; pdf: solid-angle density times that probability */
+    int32_t emitter;                   /* id into emitters[], or -1: no sample (pdf == 0), every other field 0 */
+    uint32_t reserved[3];
+} phip_emitter_sample;                 /* 48 bytes */
+typedef struct phip_emitter_sample_desc {
+    const float *d_ref;                /* n x float4: xyz = the reference point */
+    const float *d_ref_n;              /* NULL, or n x float4: xyz = the normal at the reference point.  NULL is the zero normal of a point that lies on no surface
+                                          (DirectSamplingRecord::refN); the path integrator passes zero too at a transmissive or two-sided-transmissive surface */
+    const float *d_samples;            /* n x float2 in [0, 1) */
+    size_t       n;
+    phip_emitter_sample *d_sampled;    /* n records */
+    phip_ray    *d_shadow_rays;        /* NULL, or n rays: the shadow ray the `path` integrator traces for the sample -- o = the reference point, mint = Epsilon (scaled by
+                                          the origin's magnitude when it is traced, as every ray's), d, maxt = dist * (1 - ShadowEpsilon).  An entry without a sample is
+                                          the empty interval mint = 0, maxt = -1, for which phip_trace_device answers "not occluded" without traversing */
+    void        *stream;
+} phip_emitter_sample_desc;
+int  phip_emitter_sample_device(phip_scene *scene, const phip_emitter_sample_desc *desc);
+
+/* The emitted radiance a ray meets and the density with which emitter sampling would have produced it: the other half of multiple importance sampling
+   (path.cpp, the block behind bsdf->sample).  At a hit on an area emitter rgb = its.Le(-d), zero on the back; at a miss in a scene with an environment emitter rgb =
+   evalEnvironment for a ray without differentials (the lookup later vertices use); otherwise rgb = 0.  w = Scene::pdfEmitterDirect for that record in the solid-angle
+   measure, the selection probability included, and 0 where rgb comes from no emitter -- also at a miss whose origin lies outside the environment emitter's sphere
+   (its fillDirectSamplingRecord refuses the ray; the integrator adds nothing there). */
+typedef struct phip_emitter_eval_desc {
+    const phip_ray *d_rays;            /* n rays: origin and direction are read */
+    const phip_hit *d_hits;            /* n hits of those rays */
+    const float    *d_ref_n;           /* NULL (zero normals), or n x float4: the normal at the ray's origin; enters only through dot(d, refN) and refN.isZero() */
+    size_t          n;
+    float          *d_eval;            /* n x float4 */
+    int32_t        *d_emitter;         /* NULL, or n x int32: the emitter's id, or -1 */
+    void           *stream;
+} phip_emitter_eval_desc;
+int  phip_emitter_eval_device(phip_scene *scene, const phip_emitter_eval_desc *desc);
 
 /* Replicates the device-resident scene (geometry, acceleration structure, materials, textures) from the scene's device
    to each listed device (device-to-device copies over xGMI), so that a later multi-device render starts immediately. */
@@ -624,7 +706,7 @@ int  phip_scene_accel_info(const phip_scene *scene, phip_accel_info *out);
 /* Utilities for callers that fill a phip_scene_desc without Mitsuba at hand (the test harness, bench.py): the table of the reference's default `gaussian` reconstruction
  * filter with the given standard deviation -- (radius, PHIP_FILTER_RESOLUTION + 1 values), rfilter.cpp:38-57 + gaussian.cpp:34-57; the Mitsuba shim copies the scene's own
  * filter instead -- and sizeof of the ABI's structs by index (0 phip_material, 1 phip_shape, 2 phip_emitter, 3 phip_camera, 4 phip_film, 5 phip_scene_desc,
- * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info, 11 phip_update_desc, 12 phip_update_info, 13 phip_surface, 15 phip_radiance_desc; 14 is unassigned and answers 0: tests/test_raycast_device_host.py pins phip_abi_sizeof(14) == 0 as "one past the last struct" and stays as it is, so the new struct skips that index; 16 is unassigned likewise: tests/test_radiance_device_host.py pins it; 17 phip_camera_rays_desc, 18 phip_film_desc), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
+ * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info, 11 phip_update_desc, 12 phip_update_info, 13 phip_surface, 15 phip_radiance_desc; 14 is unassigned and answers 0: tests/test_raycast_device_host.py pins phip_abi_sizeof(14) == 0 as "one past the last struct" and stays as it is, so the new struct skips that index; 16 is unassigned likewise: tests/test_radiance_device_host.py pins it; 17 phip_camera_rays_desc, 18 phip_film_desc; 19 is unassigned likewise: tests/test_camera_film_host.py pins it; 20 phip_appearance_desc, 21 phip_appearance_info; 22 is unassigned likewise: tests/test_appearance_host.py pins it; 23 phip_bsdf_desc, 24 phip_bsdf_sample, 25 phip_emitter_sample_desc, 26 phip_emitter_sample, 27 phip_emitter_eval_desc), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
 void   phip_gaussian_filter(float stddev, float *radius, float *table);
 size_t phip_abi_sizeof(int which);
 

@@ -204,6 +204,34 @@ class phip_appearance_info(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class phip_bsdf_sample(C.Structure):
+    _fields_ = [("wo", C.c_float * 3), ("pdf", C.c_float), ("weight", C.c_float * 3), ("eta", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+PHIP_BSDF_SAMPLED_DELTA = 1
+PHIP_BSDF_SAMPLED_VALID = 2
+PHIP_BSDF_LOCAL = 1
+
+
+class phip_bsdf_desc(C.Structure):
+    _fields_ = [("d_rays", C.c_void_p), ("d_hits", C.c_void_p), ("n", C.c_size_t), ("d_wo", C.c_void_p), ("d_samples", C.c_void_p), ("d_eval", C.c_void_p),
+                ("d_sampled", C.c_void_p), ("d_wi_local", C.c_void_p), ("flags", C.c_uint32), ("reserved", C.c_uint32), ("stream", C.c_void_p)]
+
+
+class phip_emitter_sample(C.Structure):
+    _fields_ = [("d", C.c_float * 3), ("dist", C.c_float), ("value", C.c_float * 3), ("pdf", C.c_float), ("emitter", C.c_int32), ("reserved", C.c_uint32 * 3)]
+
+
+class phip_emitter_sample_desc(C.Structure):
+    _fields_ = [("d_ref", C.c_void_p), ("d_ref_n", C.c_void_p), ("d_samples", C.c_void_p), ("n", C.c_size_t), ("d_sampled", C.c_void_p), ("d_shadow_rays", C.c_void_p),
+                ("stream", C.c_void_p)]
+
+
+class phip_emitter_eval_desc(C.Structure):
+    _fields_ = [("d_rays", C.c_void_p), ("d_hits", C.c_void_p), ("d_ref_n", C.c_void_p), ("n", C.c_size_t), ("d_eval", C.c_void_p), ("d_emitter", C.c_void_p),
+                ("stream", C.c_void_p)]
+
+
 def default_render_params(**kw):
     """MonteCarloIntegrator defaults (src/librender/integrator.cpp:190-225)."""
     p = phip_render_params()

@@ -57,6 +57,8 @@ UNITS += [("phip_raycast.hip", [], "phip_raycast.o")]
 UNITS += [("phip_camera_film.hip", [], "phip_camera_film.o")]
 # phip_appearance.hip (the kernels of phip_scene_update_appearance, k_appearance.h): one small object, inserted likewise
 UNITS += [("phip_appearance.hip", [], "phip_appearance.o")]
+# phip_shading_parts.hip (the kernels of phip_bsdf_device, phip_emitter_sample_device and phip_emitter_eval_device, k_shading_parts.h): one object, inserted likewise
+UNITS += [("phip_shading_parts.hip", [], "phip_shading_parts.o")]
 # phip_update.hip (the refit kernels of phip_scene_update, k_update.h): one small object, appended likewise
 UNITS += [("phip_update.hip", [], "phip_update.o")]
 # phip_rebuild.hip (the device build of phip_scene_rebuild, k_rebuild.h, with rocPRIM's sort and scan): one object, appended likewise
@@ -146,6 +148,8 @@ def _build_locked(sid, out_lib, verbose):
             return 5.0
         if name.startswith("phip_camera_film") or name.startswith("phip_appearance"):
             return 3.0
+        if name.startswith("phip_shading_parts"):
+            return 12.0
         if name.startswith("phip_radiance"):
             return feat_cost.get(int(re.match(r"phip_radiance(\d)", name).group(1)), 20.0)
         return 31.0 if name.startswith("phip_mega") else 14.0
@@ -184,8 +188,8 @@ TEST_VARIANTS = {"fault": "-DMEGA_MB_FAULT=1",       # waves of fused launches r
                  "cap32": "-DWP_CAP=32u",            # 32-entry task stacks: nearly every push of a big scene spills to memory
                  "overflow": "-DWP_CAP=64u -DWP_SPILL_CAP=64u"}      # 128-entry task stacks, half of them spilled: the tree-in-memory scenes outgrow them -- the wave stops, the pass is re-rendered
 # sources whose objects a variant takes from the product build: its flags do not concern them (the task stacks are k_mega's and k_shade_trace_w's)
-VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip", "cap32": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip",
-                 "overflow": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip"}
+VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip", "cap32": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip",
+                 "overflow": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip"}
 
 
 def build_test_variant(tag):
@@ -231,6 +235,9 @@ def lib():
     L.phip_radiance_device.argtypes = [C.c_void_p, C.POINTER(A.phip_render_params), C.POINTER(A.phip_radiance_desc), C.POINTER(A.phip_stats)]
     L.phip_camera_rays_device.argtypes = [C.c_void_p, C.POINTER(A.phip_render_params), C.POINTER(A.phip_camera_rays_desc)]
     L.phip_film_device.argtypes = [C.c_void_p, C.POINTER(A.phip_render_params), C.POINTER(A.phip_film_desc), C.POINTER(A.phip_stats)]
+    L.phip_bsdf_device.argtypes = [C.c_void_p, C.POINTER(A.phip_bsdf_desc)]
+    L.phip_emitter_sample_device.argtypes = [C.c_void_p, C.POINTER(A.phip_emitter_sample_desc)]
+    L.phip_emitter_eval_device.argtypes = [C.c_void_p, C.POINTER(A.phip_emitter_eval_desc)]
     L.phip_cancel.argtypes = [C.c_void_p]
     L.phip_scene_replicate.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
     L.phip_scene_update.argtypes = [C.c_void_p, C.POINTER(A.phip_update_desc), C.POINTER(A.phip_update_info)]
@@ -296,6 +303,12 @@ def debug_lib():
     L.phip_debug_host_film_args.argtypes = [C.POINTER(A.phip_render_params), C.POINTER(A.phip_film_desc)]
     L.phip_debug_host_appearance_args.argtypes = [C.POINTER(A.phip_scene_desc), C.POINTER(A.phip_appearance_desc)]
     L.phip_debug_host_envmap_cdf.argtypes = [C.POINTER(A.phip_envmap), fp, fp, fp, fp]
+    L.phip_debug_host_bsdf_args.argtypes = [C.c_int, C.POINTER(A.phip_bsdf_desc)]
+    L.phip_debug_host_emitter_sample_args.argtypes = [C.c_int, C.POINTER(A.phip_emitter_sample_desc)]
+    L.phip_debug_host_emitter_eval_args.argtypes = [C.c_int, C.POINTER(A.phip_emitter_eval_desc)]
+    L.phip_debug_host_bsdf_parts.argtypes = [C.POINTER(A.phip_scene_desc), C.POINTER(A.phip_bsdf_desc)]
+    L.phip_debug_host_emitter_sample.argtypes = [C.POINTER(A.phip_scene_desc), C.POINTER(A.phip_emitter_sample_desc)]
+    L.phip_debug_host_emitter_eval.argtypes = [C.POINTER(A.phip_scene_desc), C.POINTER(A.phip_emitter_eval_desc)]
     L.phip_debug_fmath.argtypes = [C.c_int, C.c_int, C.c_size_t, fp, fp, fp]
     L.phip_debug_selected_kernel.argtypes = [C.c_int] * 7; L.phip_debug_selected_kernel.restype = C.c_char_p
     _debug = L

@@ -15,7 +15,7 @@
  *       iteration that shades a slot's vertex and traces its shadow ray and its next ray on the packed leaf table in LDS (k_shade_trace.h); scenes of that
  *       kind whose tree lives in L2: k_shade_trace_w, the same iteration on the 8-wide tree in memory (k_shade_trace_w.h)
  *
- * libphip.so is 47 objects of ten sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
+ * libphip.so is 48 objects of eleven sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
  * at plan time (host_render.h -- shadeUnit: the one table over the feature sets; megaKernelOf -> FusedPlan::kernel in planFused, shadeKernelOf / shadeTraceWideKernelOf ->
  * WavefrontPlan::vertex / vertexWide in selectVertexKernel), asks the runtime for the residency of the persistent ones (residentBlocksPerCU) and launches them.
  * Kernels and where they live:
@@ -43,6 +43,8 @@
  *   k_shade_r.h   phip_radiance_device: k_shade_r (k_shade with a caller's ray array as its source of samples), k_radiance_out (the mean of a ray's samples)  [phip_shade_r.hip]
  *   k_camera_film.h  phip_camera_rays_device / phip_film_device: k_camera_rays (the camera samples of the counter stream), k_film_values (k_film's gather on a
  *                 caller's per-sample values)                                                                                                              [phip_camera_film.hip]
+ *   k_shading_parts.h  phip_bsdf_device / phip_emitter_sample_device / phip_emitter_eval_device: k_bsdf_parts, k_emitter_sample, k_emitter_eval -- one lane per item around
+ *                 the vertex's own BSDF and emitter functions (dv_scene.h)                                                                                 [phip_shading_parts.hip]
  *
  * This file: the C ABI -- error state, the guard that maps what an entry point's body throws to its error code, the entry of both render functions, the film's way
  * to the host and the extern "C" entry points.  The rest of the host side is three headers by concern, each including the ones before it:
@@ -59,6 +61,8 @@
  *                  k_radiance_out for the film pass (k_shade_r.h in phip_shade_r.hip)
  *   host_camera_film.h phip_camera_rays_device and phip_film_device: the camera samples out, per-sample values onto a film -- validation before any launch
  *                  (k_camera_film.h in phip_camera_film.hip)
+ *   host_shading_parts.h phip_bsdf_device, phip_emitter_sample_device and phip_emitter_eval_device: the BSDF at the hits of a ray cast, emitter sampling and emitter
+ *                  evaluation on the caller's arrays -- validation before any launch (k_shading_parts.h in phip_shading_parts.hip)
  * Not MFMA work: irregular traversal and gathers.  The product never includes, links or calls anything under oracle/.
  */
 #include "phip_common.h"
@@ -71,6 +75,7 @@
 #include "k_shade_trace.h"
 #include "k_shade_trace_w.h"     /* (for shadeTraceWideLdsBytes: the kernels of these three headers are templates that this unit does not instantiate) */
 #include "k_shade_r.h"           /* (for RaySamples, the argument of k_shade_r: likewise) */
+#include "k_shading_parts.h"   /* (the per-item statements, for the host twins: the kernels are phip_shading_parts.hip's) */
 #include "appearance_hd.h"      /* (the arithmetic host_scene.h shares with the kernels of phip_appearance.hip, which this unit does not hold) */
 #ifndef PHIP_DEBUG_HOOKS
 #define PHIP_DEBUG_HOOKS 0
@@ -95,6 +100,7 @@ static int setErr(int code, const std::string &msg) { g_err = msg; return code; 
 #include "host_raycast.h"
 #include "host_radiance.h"
 #include "host_camera_film.h"
+#include "host_shading_parts.h"
 
 /* Entry of both render functions: validation, the scene's render lock, single- or multi-device dispatch, the sticky
    cancellation flag (consumed by the call that observed it). */
@@ -127,7 +133,7 @@ static int renderImpl(phip_scene *sc, const phip_render_params *p, float *dOut, 
 struct ErrorCodes { int invalid, other; };
 static const ErrorCodes CREATE_ERRORS = { PHIP_ERR_UNSUPPORTED, PHIP_ERR_INVALID };     /* phip_scene_create: a scene the back end does not serve / a malformed one */
 static const ErrorCodes RENDER_ERRORS = { PHIP_ERR_INVALID, PHIP_ERR_DEVICE };          /* phip_render, phip_render_device: a bad argument / the runtime */
-static const ErrorCodes DEVICE_ERRORS = { PHIP_ERR_DEVICE, PHIP_ERR_DEVICE };           /* phip_scene_replicate, phip_scene_update, phip_scene_rebuild, phip_scene_update_appearance, phip_film_to_host, phip_trace, phip_trace_device: their bodies check arguments themselves */
+static const ErrorCodes DEVICE_ERRORS = { PHIP_ERR_DEVICE, PHIP_ERR_DEVICE };           /* phip_scene_replicate, phip_scene_update, phip_scene_rebuild, phip_scene_update_appearance, phip_film_to_host, phip_trace, phip_trace_device, phip_bsdf_device, phip_emitter_sample_device, phip_emitter_eval_device: their bodies check arguments themselves */
 template <typename Body> static int guarded(const ErrorCodes &codes, Body body) {
     try {
         return body();
@@ -136,6 +142,22 @@ template <typename Body> static int guarded(const ErrorCodes &codes, Body body) 
     } catch (const std::exception &e) {
         return setErr(codes.other, e.what());
     }
+}
+
+/* the three shading parts: arguments (no device needed), the device, the scene's render lock, the launch */
+template <typename Desc, typename Check, typename Run>
+static int shadingPartsEntry(const char *name, phip_scene *scene, const Desc *desc, Check check, Run run) {
+    if (const char *bad = check(scene != nullptr, desc)) return setErr(PHIP_ERR_INVALID, std::string(name) + ": " + bad);
+    if (desc->n == 0) return PHIP_OK;
+    int nDev = phip_device_count();
+    if (nDev <= 0) return setErr(PHIP_ERR_DEVICE, std::string(name) + ": " + (nDev == 0 ? std::string("no HIP device visible: path_hip has no CPU fallback") : g_err));
+    const int rc = guarded(DEVICE_ERRORS, [&]() -> int {
+        HIP_TRY(hipSetDevice(scene->devs[0]->device));
+        std::lock_guard<std::mutex> lock(scene->renderLock);
+        return run(scene, desc);
+    });
+    if (rc == PHIP_ERR_DEVICE) g_err = std::string(name) + ": " + g_err;      /* (what the runtime said; the refusals carry the name already) */
+    return rc;
 }
 
 extern "C" {
@@ -446,6 +468,10 @@ int phip_film_device(phip_scene *scene, const phip_render_params *params, const 
     });
 }
 
+int phip_bsdf_device(phip_scene *scene, const phip_bsdf_desc *desc) { return shadingPartsEntry("phip_bsdf_device", scene, desc, bsdfArgsError, bsdfDevice); }
+int phip_emitter_sample_device(phip_scene *scene, const phip_emitter_sample_desc *desc) { return shadingPartsEntry("phip_emitter_sample_device", scene, desc, emitterSampleArgsError, emitterSampleDevice); }
+int phip_emitter_eval_device(phip_scene *scene, const phip_emitter_eval_desc *desc) { return shadingPartsEntry("phip_emitter_eval_device", scene, desc, emitterEvalArgsError, emitterEvalDevice); }
+
 void phip_cancel(phip_scene *scene) { if (scene && scene->cancelFlag) __atomic_store_n(scene->cancelFlag, 1, __ATOMIC_RELAXED); }
 
 void phip_develop(const float *rgbaw, size_t n_pixels, float *out_rgb) {
@@ -507,6 +533,11 @@ size_t phip_abi_sizeof(int which) {
         case 18: return sizeof(phip_film_desc);
         case 20: return sizeof(phip_appearance_desc);    /* (19 likewise) */
         case 21: return sizeof(phip_appearance_info);
+        case 23: return sizeof(phip_bsdf_desc);          /* (22 likewise) */
+        case 24: return sizeof(phip_bsdf_sample);
+        case 25: return sizeof(phip_emitter_sample_desc);
+        case 26: return sizeof(phip_emitter_sample);
+        case 27: return sizeof(phip_emitter_eval_desc);
         default: return 0;
     }
 }

@@ -2,7 +2,7 @@
  * phip_common.h -- what every translation unit of libphip.so starts with: HIP, the C ABI, the device scene layout and
  * shading functions (dv_scene.h), the path-pool layout (k_pool.h), the error macro.
  *
- * libphip.so is built from nine sources (46 objects) so that they compile in parallel:
+ * libphip.so is built from eleven sources (48 objects) so that they compile in parallel:
  *   phip.hip          the C ABI + traversal and film kernels, with the host side it includes by concern: host_scene.h (scene build, replicas), host_render.h (kernel
  *                     selection, one device's render loop), host_multi.h (multi-device orchestration, RCCL): 1 object
  *   phip_shade.hip    k_shade / k_shade_direct / k_shade_trace instantiations behind the look-ups phipShade*KernelF<n> -- compiled per feature set (-DSHADE_FEAT=0..3, 8
@@ -16,6 +16,9 @@
  *   phip_shade_r.hip  the kernels of phip_radiance_device (k_shade_r.h) behind phipShadeRaysKernelS<s>F<n> and phipRadianceOutKernel -- per feature set (-DSHADE_FEAT=0..3) and
  *                     strictNormals (-DSHADE_PART=0 / 1): 8 objects
  *   phip_camera_film.hip  the kernels of phip_camera_rays_device and phip_film_device (k_camera_film.h) behind phipCameraFilmKernels: 1 object
+ *   phip_appearance.hip   the kernels of phip_scene_update_appearance (k_appearance.h) behind phipAppearanceKernels: 1 object
+ *   phip_shading_parts.hip  the kernels of phip_bsdf_device, phip_emitter_sample_device and phip_emitter_eval_device (k_shading_parts.h) behind
+ *                     phipShadingPartsKernels: 1 object
  * The other units hold kernels and the look-ups that return them, nothing else: every launch and every query of the runtime is in phip.hip and its host headers
  * (but for the launches inside rocPRIM's sort and scan, which phip_rebuild.hip wraps).
  * No device function is called across units (everything on the device side is inline in headers), so no -fgpu-rdc.
@@ -125,3 +128,12 @@ struct AppearanceKernels {
     void (*classes)(float4 *, const uint32_t *, uint32_t, const uint8_t *, uint32_t);
 };
 AppearanceKernels phipAppearanceKernels();
+/* the kernels of phip_bsdf_device, phip_emitter_sample_device and phip_emitter_eval_device (phip_shading_parts.hip, k_shading_parts.h).  bsdf[eval | 2 * sample]:
+   (scene, rays, hits, wo, samples, n, local, eval out, sampled out, wi out); emitterSample / emitterEval[the scene has an environment emitter]:
+   (scene, ref, refN, samples, n, sampled out, shadow rays out) and (scene, rays, hits, refN, n, eval out, emitter out) */
+struct ShadingPartsKernels {
+    void (*bsdf[4])(DevScene, const float4 *, const float4 *, const float4 *, const float2 *, uint32_t, uint32_t, float4 *, float4 *, float4 *);
+    void (*emitterSample[2])(DevScene, const float4 *, const float4 *, const float2 *, uint32_t, float4 *, float4 *);
+    void (*emitterEval[2])(DevScene, const float4 *, const float4 *, const float4 *, uint32_t, float4 *, int32_t *);
+};
+ShadingPartsKernels phipShadingPartsKernels();

@@ -712,3 +712,106 @@ extern "C" int phip_debug_host_envmap_cdf(const phip_envmap *envmap, float *cdf_
         return PHIP_OK;
     } catch (const std::exception &e) { return setErr(PHIP_ERR_INVALID, e.what()); }
 }
+
+/* ---- phip_bsdf_device, phip_emitter_sample_device, phip_emitter_eval_device without a device ---- */
+/* their checks of the arguments (host_shading_parts.h): the code the entry point would return for them, PHIP_OK when it would go on to the device and the
+   pointers' attributes; the message in phip_last_error.  have_scene = 0: the scene argument is NULL */
+extern "C" int phip_debug_host_bsdf_args(int have_scene, const phip_bsdf_desc *desc) {
+    if (const char *bad = bsdfArgsError(have_scene != 0, desc)) return setErr(PHIP_ERR_INVALID, std::string("phip_bsdf_device: ") + bad);
+    return PHIP_OK;
+}
+extern "C" int phip_debug_host_emitter_sample_args(int have_scene, const phip_emitter_sample_desc *desc) {
+    if (const char *bad = emitterSampleArgsError(have_scene != 0, desc)) return setErr(PHIP_ERR_INVALID, std::string("phip_emitter_sample_device: ") + bad);
+    return PHIP_OK;
+}
+extern "C" int phip_debug_host_emitter_eval_args(int have_scene, const phip_emitter_eval_desc *desc) {
+    if (const char *bad = emitterEvalArgsError(have_scene != 0, desc)) return setErr(PHIP_ERR_INVALID, std::string("phip_emitter_eval_device: ") + bad);
+    return PHIP_OK;
+}
+
+/* The DevScene of a descriptor on the host: the stages phip_scene_create runs before it uploads (none of them calls HIP) -- shapes, textures, materials, emitters,
+   the tree (for the scene box the environment emitter's sphere is made of), shading records, the emitter table, the environment map's tables -- with the
+   DevScene's pointers bound to the builder's arrays instead of device buffers.  What the items of k_shading_parts.h read of a scene is all there. */
+struct HostSceneTwin {
+    phip_scene sc; SceneBuild B; DevScene S;
+    explicit HostSceneTwin(const phip_scene_desc &d) : B(&sc, d) {
+        B.validateDesc();
+        B.flattenShapes(); B.packTextures(); B.materials(); B.emitterSelection();
+        B.buildAccel();
+        B.shadingRecords();
+        B.packEmitterTable(); B.environmentSphere(); B.buildEnvmap();
+        B.sceneConstants();
+        S = B.D;
+        S.triShade = B.ts.data(); S.materials = B.mats.data(); S.emitterTab = B.tab.data();
+        S.texTexels = B.texTexels.data(); S.textures = B.texDesc.data();
+        S.env.texels = B.envTexels.data(); S.env.levels = &B.envLevels; S.env.cdfRows = B.envCdfRows.data(); S.env.cdfCols = B.envCdfCols.data(); S.env.rowWeights = B.envRowWeights.data();
+    }
+    EmitterTab table() const { EmitterTab T; T.t = S.emitterTab; T.n = S.nEmitters; T.normalization = S.emitterNormalization; return T; }
+};
+
+/* The host twins: the statement each kernel of k_shading_parts.h evaluates per lane, over the same descriptor with HOST pointers, after the entry point's own
+   argument checks (alignment included) */
+extern "C" int phip_debug_host_bsdf_parts(const phip_scene_desc *created, const phip_bsdf_desc *b) {
+    if (!created) return setErr(PHIP_ERR_INVALID, "NULL argument");
+    if (const char *bad = bsdfArgsError(true, b)) return setErr(PHIP_ERR_INVALID, std::string("phip_bsdf_device: ") + bad);
+    try {
+        HostSceneTwin H(*created);
+        const float4 *rays = (const float4 *) b->d_rays, *hits = (const float4 *) b->d_hits, *wo = (const float4 *) b->d_wo;
+        const float2 *smp = (const float2 *) b->d_samples;
+        const bool local = (b->flags & PHIP_BSDF_LOCAL) != 0;
+        for (size_t i = 0; i < b->n; ++i) {
+            const float4 rd = rays[2 * i + 1];
+            const V3 woIn = b->d_eval ? V3(wo[i].x, wo[i].y, wo[i].z) : V3(0.0f);
+            const V2 s = b->d_sampled ? V2(smp[i].x, smp[i].y) : V2(0.0f, 0.0f);
+            BsdfPartsOut o;
+            if (b->d_eval && b->d_sampled) bsdfPartsItem<true, true>(H.S, H.S.materials, V3(rd.x, rd.y, rd.z), hits[i], woIn, s, local, o);
+            else if (b->d_eval) bsdfPartsItem<true, false>(H.S, H.S.materials, V3(rd.x, rd.y, rd.z), hits[i], woIn, s, local, o);
+            else if (b->d_sampled) bsdfPartsItem<false, true>(H.S, H.S.materials, V3(rd.x, rd.y, rd.z), hits[i], woIn, s, local, o);
+            else bsdfPartsItem<false, false>(H.S, H.S.materials, V3(rd.x, rd.y, rd.z), hits[i], woIn, s, local, o);
+            if (b->d_eval) ((float4 *) b->d_eval)[i] = o.eval;
+            if (b->d_sampled) { float4 *d = (float4 *) b->d_sampled + 3 * i; d[0] = o.s0; d[1] = o.s1; d[2] = o.s2; }
+            if (b->d_wi_local) ((float4 *) b->d_wi_local)[i] = o.wi;
+        }
+        return PHIP_OK;
+    } catch (const std::exception &e) { return setErr(PHIP_ERR_INVALID, e.what()); }
+}
+
+extern "C" int phip_debug_host_emitter_sample(const phip_scene_desc *created, const phip_emitter_sample_desc *e) {
+    if (!created) return setErr(PHIP_ERR_INVALID, "NULL argument");
+    if (const char *bad = emitterSampleArgsError(true, e)) return setErr(PHIP_ERR_INVALID, std::string("phip_emitter_sample_device: ") + bad);
+    try {
+        HostSceneTwin H(*created);
+        const EmitterTab T = H.table();
+        const float4 *ref = (const float4 *) e->d_ref, *refN = (const float4 *) e->d_ref_n;
+        const float2 *smp = (const float2 *) e->d_samples;
+        for (size_t i = 0; i < e->n; ++i) {
+            const V3 rn = refN ? V3(refN[i].x, refN[i].y, refN[i].z) : V3(0.0f);
+            EmitterSampleOut o;
+            if (H.S.envEmitter >= 0) emitterSampleItem<true>(H.S, T, V3(ref[i].x, ref[i].y, ref[i].z), rn, V2(smp[i].x, smp[i].y), o);
+            else emitterSampleItem<false>(H.S, T, V3(ref[i].x, ref[i].y, ref[i].z), rn, V2(smp[i].x, smp[i].y), o);
+            float4 *d = (float4 *) e->d_sampled + 3 * i; d[0] = o.s0; d[1] = o.s1; d[2] = o.s2;
+            if (e->d_shadow_rays) { float4 *r = (float4 *) e->d_shadow_rays + 2 * i; r[0] = o.ro; r[1] = o.rd; }
+        }
+        return PHIP_OK;
+    } catch (const std::exception &x) { return setErr(PHIP_ERR_INVALID, x.what()); }
+}
+
+extern "C" int phip_debug_host_emitter_eval(const phip_scene_desc *created, const phip_emitter_eval_desc *e) {
+    if (!created) return setErr(PHIP_ERR_INVALID, "NULL argument");
+    if (const char *bad = emitterEvalArgsError(true, e)) return setErr(PHIP_ERR_INVALID, std::string("phip_emitter_eval_device: ") + bad);
+    try {
+        HostSceneTwin H(*created);
+        const EmitterTab T = H.table();
+        const float4 *rays = (const float4 *) e->d_rays, *hits = (const float4 *) e->d_hits, *refN = (const float4 *) e->d_ref_n;
+        for (size_t i = 0; i < e->n; ++i) {
+            const float4 ro = rays[2 * i], rd = rays[2 * i + 1];
+            const V3 rn = refN ? V3(refN[i].x, refN[i].y, refN[i].z) : V3(0.0f);
+            float4 ev; int32_t emitter;
+            if (H.S.envEmitter >= 0) emitterEvalItem<true>(H.S, T, V3(ro.x, ro.y, ro.z), V3(rd.x, rd.y, rd.z), hits[i], rn, ev, emitter);
+            else emitterEvalItem<false>(H.S, T, V3(ro.x, ro.y, ro.z), V3(rd.x, rd.y, rd.z), hits[i], rn, ev, emitter);
+            ((float4 *) e->d_eval)[i] = ev;
+            if (e->d_emitter) e->d_emitter[i] = emitter;
+        }
+        return PHIP_OK;
+    } catch (const std::exception &x) { return setErr(PHIP_ERR_INVALID, x.what()); }
+}

@@ -158,6 +158,80 @@ class Scene:
             raise _ffi.PhipError(rc, "phip_film_device")
         return out, st
 
+    def _device_tensor(self, t, name, cols, dtype=None, rows=None, optional=False):
+        """a contiguous (n, cols) tensor of `dtype` (default float32) on the scene's device, as the shading parts read and write them"""
+        import torch
+        if t is None and optional:
+            return None
+        dtype = dtype or torch.float32
+        if not hasattr(t, "data_ptr") or t.dtype != dtype or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != cols or (rows is not None and t.shape[0] != rows):
+            raise ValueError("%s: expected a contiguous %s tensor of shape (%s, %d)" % (name, str(dtype).replace("torch.", ""), "n" if rows is None else rows, cols))
+        if not t.is_cuda or (t.device.index or 0) != self.device:
+            raise ValueError("%s: the tensor is not on the scene's device" % name)
+        return t
+
+    def bsdf(self, rays, hits, wo=None, samples=None, local=False, wi_local=False, stream=None):
+        """BSDF::eval / pdf / sample at the hits of a ray cast (phip_bsdf_device).  rays (n, 8) and hits (n, 4) are what rayIntersectDevice read and returned.
+        wo: (n, 4) float32, xyz = the outgoing direction -> eval, (n, 4) = the BSDF's value (solid-angle measure, cosine included) and its pdf.
+        samples: (n, 2) float32 in [0, 1) -> sampled, (n, 12) float32: the words of phip_bsdf_sample -- wo, pdf, weight = value / pdf, eta, flags (view as int32:
+        PHIP_BSDF_SAMPLED_VALID | _DELTA), three reserved words; a failed sample is all zero.  local: wo is given, and the sampled direction returned, in the shading
+        frame instead of world space.  wi_local: also return wi in the shading frame, (n, 4).  Returns (eval, sampled, wi_local), None where not asked for.
+        A miss is all zero.  ValueError for a tensor of another dtype, layout or device; PhipError for what the library refuses (no output asked for)."""
+        import torch
+        rays = self._device_tensor(rays, "rays", 8)
+        n = rays.shape[0]
+        hits = self._device_tensor(hits, "hits", 4, rows=n)
+        wo = self._device_tensor(wo, "wo", 4, rows=n, optional=True)
+        samples = self._device_tensor(samples, "samples", 2, rows=n, optional=True)
+        ev = torch.empty((n, 4), dtype=torch.float32, device=rays.device) if wo is not None else None
+        sampled = torch.empty((n, 12), dtype=torch.float32, device=rays.device) if samples is not None else None
+        wi = torch.empty((n, 4), dtype=torch.float32, device=rays.device) if wi_local else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        d = A.phip_bsdf_desc(d_rays=ptr(rays), d_hits=ptr(hits), n=n, d_wo=ptr(wo), d_samples=ptr(samples), d_eval=ptr(ev), d_sampled=ptr(sampled), d_wi_local=ptr(wi),
+                             flags=A.PHIP_BSDF_LOCAL if local else 0, reserved=0, stream=getattr(stream, "cuda_stream", stream))
+        rc = self._L.phip_bsdf_device(self._h, C.byref(d))
+        if rc != 0:
+            raise _ffi.PhipError(rc, "phip_bsdf_device")
+        return ev, sampled, wi
+
+    def emitter_sample(self, ref, ref_n, samples, shadow_rays=False, stream=None):
+        """Scene::sampleEmitterDirect without its visibility test (phip_emitter_sample_device).  ref: (n, 4) float32, xyz = the reference points; ref_n: (n, 4), their
+        normals, or None (points on no surface); samples: (n, 2) in [0, 1).  Returns (sampled, rays): sampled (n, 12) float32, the words of phip_emitter_sample -- d,
+        dist, value = radiance / pdf, pdf, emitter (view as int32; -1: no sample, all else 0), three reserved words; rays (n, 8), the shadow rays to hand to
+        rayIntersectDevice(shadow=True) -- the empty interval where there is no sample --, or None."""
+        import torch
+        ref = self._device_tensor(ref, "ref", 4)
+        n = ref.shape[0]
+        ref_n = self._device_tensor(ref_n, "ref_n", 4, rows=n, optional=True)
+        samples = self._device_tensor(samples, "samples", 2, rows=n)
+        sampled = torch.empty((n, 12), dtype=torch.float32, device=ref.device)
+        rays = torch.empty((n, 8), dtype=torch.float32, device=ref.device) if shadow_rays else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        d = A.phip_emitter_sample_desc(d_ref=ptr(ref), d_ref_n=ptr(ref_n), d_samples=ptr(samples), n=n, d_sampled=ptr(sampled), d_shadow_rays=ptr(rays),
+                                       stream=getattr(stream, "cuda_stream", stream))
+        rc = self._L.phip_emitter_sample_device(self._h, C.byref(d))
+        if rc != 0:
+            raise _ffi.PhipError(rc, "phip_emitter_sample_device")
+        return sampled, rays
+
+    def emitter_eval(self, rays, hits, ref_n=None, emitter=False, stream=None):
+        """The emitted radiance a ray meets and the density with which emitter sampling would have produced it (phip_emitter_eval_device): rays (n, 8), hits (n, 4)
+        as for bsdf; ref_n (n, 4): the normals at the rays' origins, or None (zero).  Returns (eval, emitter): (n, 4) float32 = Le(-d) at a hit on an area emitter,
+        the environment's radiance at a miss, else 0, and pdfEmitterDirect in the solid-angle measure; (n,) int32 emitter ids (-1: none) if emitter=True, else None."""
+        import torch
+        rays = self._device_tensor(rays, "rays", 8)
+        n = rays.shape[0]
+        hits = self._device_tensor(hits, "hits", 4, rows=n)
+        ref_n = self._device_tensor(ref_n, "ref_n", 4, rows=n, optional=True)
+        ev = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        em = torch.empty((n,), dtype=torch.int32, device=rays.device) if emitter else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        d = A.phip_emitter_eval_desc(d_rays=ptr(rays), d_hits=ptr(hits), d_ref_n=ptr(ref_n), n=n, d_eval=ptr(ev), d_emitter=ptr(em), stream=getattr(stream, "cuda_stream", stream))
+        rc = self._L.phip_emitter_eval_device(self._h, C.byref(d))
+        if rc != 0:
+            raise _ffi.PhipError(rc, "phip_emitter_eval_device")
+        return ev, em
+
     def replicate(self, devices):
         """Copies the device scene to further GPUs ahead of a multi-device render (phip_scene_replicate)."""
         arr = (C.c_int32 * len(devices))(*devices)
