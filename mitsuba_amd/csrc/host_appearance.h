@@ -6,7 +6,7 @@
  * the creation runs too.  So every entry point gives the bits it gives on a scene created with the new look.
  * Order: the checks that need no device (appearanceArgs), the caller's texels to the device (device_pointers = 0: the same kernels run on the uploaded copy),
  * the new textures' maxima, the material / emitter stages (appearanceLook), the environment map into FRESH buffers and its refusals -- and only then the writes.
- * Host code only; included by phip.hip alone, after host_update.h.  The caller holds the scene's render lock.
+ * Host code only; included by phip.hip alone, after host_update.h.  The caller holds the scene's render lock and has made the scene's device current.
  */
 #pragma once
 #include "host_update.h"
@@ -96,7 +96,6 @@ static int updateAppearance(phip_scene *sc, const phip_appearance_desc &a, phip_
     DevScene &D = sd.dev;
     AppearanceLook L;
     if (int rc = appearanceRefusal([&] { appearanceArgs(sc, a, L); })) return rc;
-    HIP_TRY(hipSetDevice(sd.device));
     HIP_TRY(hipDeviceSynchronize());
     const AppearanceKernels K = phipAppearanceKernels();
     auto blocks = [](size_t items) { return dim3((unsigned) ((items + APP_BLOCK - 1) / APP_BLOCK)); };

@@ -9,7 +9,6 @@
  */
 #pragma once
 #include "host_render.h"
-#include "host_raycast.h"
 
 /* what both calls read of the parameters, without a device: NULL, or the refusal and its code (`who` has no sampler but the counter stream) */
 static const char *cameraFilmParamsError(const phip_render_params *p, int &code) {
@@ -29,10 +28,10 @@ static const char *cameraRaysArgsError(const phip_render_params *p, const phip_c
     if (const char *bad = cameraFilmParamsError(p, code)) return bad;
     if (!r->d_pixels || r->m) {                                 /* (an empty list: no pointer is looked at) */
         if (!r->d_rays) return "d_rays must not be NULL";
-        if ((uintptr_t) r->d_rays & 15u) return "d_rays must be 16-byte aligned";
-        if (((uintptr_t) r->d_keys & 7u) || ((uintptr_t) r->d_positions & 7u)) return "d_keys and d_positions must be 8-byte aligned";
-        if ((uintptr_t) r->d_pixels & 3u) return "d_pixels must be 4-byte aligned";
-        if (r->d_pixels && (r->m > RAYCAST_MAX_RAYS || r->m * (unsigned long long) p->spp > RAYCAST_MAX_RAYS)) return "more than 2^32 - 256 samples in one call";
+        if (misaligned(r->d_rays, 16)) return "d_rays must be 16-byte aligned";
+        if (misaligned(r->d_keys, 8) || misaligned(r->d_positions, 8)) return "d_keys and d_positions must be 8-byte aligned";
+        if (misaligned(r->d_pixels, 4)) return "d_pixels must be 4-byte aligned";
+        if (r->d_pixels && (r->m > CALL_MAX_ITEMS || r->m * (unsigned long long) p->spp > CALL_MAX_ITEMS)) return "more than 2^32 - 256 samples in one call";
     }
     code = PHIP_ERR_UNSUPPORTED;
     if (p->sampler != PHIP_SAMPLER_CTR) return "PHIP_SAMPLER_CTR only: the other samplers' streams are addressed by film coordinates";
@@ -49,7 +48,7 @@ static const char *filmArgsError(const phip_render_params *p, const phip_film_de
     const int bs = p->block_size > 0 ? p->block_size : 32;
     if (bs < 2 || bs > 128 || (bs & (bs - 1))) return "block_size must be a power of two in [2,128]";
     if (!f->d_values || !f->d_out) return "d_values and d_out must not be NULL";
-    if (((uintptr_t) f->d_values & 15u) || ((uintptr_t) f->d_out & 15u)) return "d_values and d_out must be 16-byte aligned";
+    if (misaligned(f->d_values, 16) || misaligned(f->d_out, 16)) return "d_values and d_out must be 16-byte aligned";
     if (f->flags & ~PHIP_FILM_SIGNED) return "unknown flag";
     code = PHIP_ERR_UNSUPPORTED;
     if (p->sampler != PHIP_SAMPLER_CTR) return "PHIP_SAMPLER_CTR only: the other samplers' streams are addressed by film coordinates";
@@ -57,13 +56,16 @@ static const char *filmArgsError(const phip_render_params *p, const phip_film_de
     return nullptr;
 }
 
-/* the device the call names, which must be the scene's, and the stream its work is ordered on */
-static hipStream_t cameraFilmStream(SceneDev &sd, const phip_render_params *p, const std::string &who) {
-    const int device = p->n_devices == 1 ? p->devices[0] : p->device;
-    if (device != sd.device) throw std::invalid_argument(who + "scene was created on a different device");
-    if (p->stream) return (hipStream_t) p->stream;
-    if (!sd.stream) HIP_TRY(hipStreamCreate(&sd.stream));
-    return sd.stream;
+/* ... as the entry points and their test hooks return them */
+static int cameraRaysRefusal(const phip_render_params *p, const phip_camera_rays_desc *r) {
+    int code = PHIP_OK;
+    const char *bad = cameraRaysArgsError(p, r, code);
+    return refusal("phip_camera_rays_device", code, bad);
+}
+static int filmRefusal(const phip_render_params *p, const phip_film_desc *f) {
+    int code = PHIP_OK;
+    const char *bad = filmArgsError(p, f, code);
+    return refusal("phip_film_device", code, bad);
 }
 
 /* the constants k_camera_rays and k_film_values read: the stream's, and the samples of the call as one pass */
@@ -82,16 +84,15 @@ static int cameraRaysDevice(phip_scene *sc, const phip_render_params *p, const p
     const unsigned long long nPixels = (unsigned long long) sd.dev.film.width * (unsigned long long) sd.dev.film.height;
     const unsigned long long m = r->d_pixels ? (unsigned long long) r->m : nPixels;
     if (m == 0) return PHIP_OK;
-    if (m * (unsigned long long) p->spp > RAYCAST_MAX_RAYS) return setErr(PHIP_ERR_INVALID, who + "more than 2^32 - 256 samples in one call");
-    const void *ptrs[4] = { r->d_rays, r->d_keys, r->d_positions, r->d_pixels };
-    for (int i = 0; i < 4; ++i)
-        if (ptrs[i] && !onSceneDevice(ptrs[i], sd.device)) return setErr(PHIP_ERR_INVALID, who + "d_pixels, d_rays, d_keys and d_positions must be device memory of the scene's device");
-    const hipStream_t stream = cameraFilmStream(sd, p, who);
+    if (m * (unsigned long long) p->spp > CALL_MAX_ITEMS) return setErr(PHIP_ERR_INVALID, who + "more than 2^32 - 256 samples in one call");
+    if (!allOnSceneDevice(sd, { r->d_rays, r->d_keys, r->d_positions, r->d_pixels })) return setErr(PHIP_ERR_INVALID, who + "d_pixels, d_rays, d_keys and d_positions must be device memory of the scene's device");
+    requireSceneDevice(sd, p, who);
+    const hipStream_t stream = sceneStream(sd, p->stream);
     const CameraFilmKernels K = phipCameraFilmKernels();
     if (r->d_pixels) {          /* the list, before anything is written */
         unsigned long long bad = 0;
         HIP_TRY(hipMemsetAsync(sd.invalid.p, 0, sizeof(unsigned long long), stream));
-        hipLaunchKernelGGL(K.pixelsCheck, dim3((unsigned) ((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, r->d_pixels, (uint32_t) m, (uint32_t) nPixels, sd.invalid.p);
+        hipLaunchKernelGGL(K.pixelsCheck, dim3(blocksFor(m)), dim3(BLOCK), 0, stream, r->d_pixels, (uint32_t) m, (uint32_t) nPixels, sd.invalid.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
         HIP_TRY(hipMemcpy(&bad, sd.invalid.p, sizeof(bad), hipMemcpyDeviceToHost));
@@ -99,7 +100,7 @@ static int cameraRaysDevice(phip_scene *sc, const phip_render_params *p, const p
     }
     const uint32_t n = (uint32_t) (m * (unsigned long long) p->spp);
     const RenderConst rc = cameraFilmConstants(p, 0);
-    hipLaunchKernelGGL(K.rays, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, sd.dev, rc, r->d_pixels, n, (float4 *) r->d_rays, (uint2 *) r->d_keys, (float2 *) r->d_positions);
+    hipLaunchKernelGGL(K.rays, dim3(blocksFor(n)), dim3(BLOCK), 0, stream, sd.dev, rc, r->d_pixels, n, (float4 *) r->d_rays, (uint2 *) r->d_keys, (float2 *) r->d_positions);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     return PHIP_OK;
@@ -114,8 +115,9 @@ static int filmDevice(phip_scene *sc, const phip_render_params *p, const phip_fi
     if (bs < D.film.border) return setErr(PHIP_ERR_INVALID, who + "The block size must be larger than the image reconstruction filter radius!");      /* renderproc.cpp:175-176 */
     D.film.blockSize = bs;
     int tileShift = 0; while ((1 << tileShift) < bs) ++tileShift;
-    if (!onSceneDevice(f->d_values, sd.device) || !onSceneDevice(f->d_out, sd.device)) return setErr(PHIP_ERR_INVALID, who + "d_values and d_out must be device memory of the scene's device");
-    const hipStream_t stream = cameraFilmStream(sd, p, who);
+    if (!allOnSceneDevice(sd, { f->d_values, f->d_out })) return setErr(PHIP_ERR_INVALID, who + "d_values and d_out must be device memory of the scene's device");
+    requireSceneDevice(sd, p, who);
+    const hipStream_t stream = sceneStream(sd, p->stream);
     const CameraFilmKernels K = phipCameraFilmKernels();
     const RenderConst rc = cameraFilmConstants(p, tileShift);
     const bool timing = (p->flags & PHIP_FLAG_KERNEL_TIMING) != 0;

@@ -5,13 +5,10 @@
  * and not the rays: no chunking, and nothing is allocated after a scene's first call -- the spill region, the draw counters and the per-wave statistics are the
  * buffers the wavefront render keeps in the SceneDev (the render lock serialises the two).  The plan is resolved once per scene and again when the node cache
  * changed (phip_scene_rebuild: another tree, another LDS plan).
- * Host code only; included by phip.hip alone, after host_update.h (onSceneDevice).  The caller holds the scene's render lock.
+ * Host code only; included by phip.hip alone, after host_render.h.  The caller holds the scene's render lock.
  */
 #pragma once
 #include "host_render.h"
-#include "host_update.h"
-
-#define RAYCAST_MAX_RAYS ((size_t) 0xFFFFFF00u)        /* ray indices are 32-bit handles, 0xFFFFFFFF is none (INVALID_RAY); whole chunks of 64 and blocks of 256 stay below it */
 
 /* the server's kernels, LDS plan and resident grid for this scene's tree */
 static void planRaycast(SceneDev &sd) {
@@ -22,31 +19,29 @@ static void planRaycast(SceneDev &sd) {
     R.lds = wideLdsBytes(D.wideNodeCache, WIDE_BLOCK) + wideDealBytes(WIDE_BLOCK);
     const Residency res = residentBlocksPerCU((const void *) R.k.cast, WIDE_BLOCK, R.lds);
     if (res.limit != hipSuccess) throw std::runtime_error(std::string("k_raycast_p: hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize): ") + hipGetErrorString(res.limit));
-    int nCU = 256;
-    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, sd.device) == hipSuccess) nCU = prop.multiProcessorCount; }
+    const int nCU = cuCount(sd.device, 256);
     const int perCU = std::max(1, std::min(res.blocks > 0 ? res.blocks : 1, WIDE_WAVES * 256 / WIDE_BLOCK));
     R.blocks = (unsigned) (nCU * perCU);
     R.nodeCache = D.wideNodeCache;
 }
 
-static int traceDevice(phip_scene *sc, const phip_ray *dRays, size_t n, phip_hit *dHits, uint8_t *dOccluded, phip_surface *dSurfaces, hipStream_t callerStream, phip_stats *stats) {
+static int traceDevice(phip_scene *sc, const phip_ray *dRays, size_t n, phip_hit *dHits, uint8_t *dOccluded, phip_surface *dSurfaces, void *callerStream, phip_stats *stats) {
     SceneDev &sd = *sc->devs[0];
     const std::string who = "phip_trace_device: ";
     if (stats) memset(stats, 0, sizeof(*stats));
     if (dSurfaces && !dHits) return setErr(PHIP_ERR_INVALID, who + "d_surfaces needs d_hits");
     if (n == 0) return PHIP_OK;
-    if (n > RAYCAST_MAX_RAYS) return setErr(PHIP_ERR_INVALID, who + "more than 2^32 - 256 rays in one call");
+    if (n > CALL_MAX_ITEMS) return setErr(PHIP_ERR_INVALID, who + "more than 2^32 - 256 rays in one call");
     const auto t0 = std::chrono::steady_clock::now();
     const void *ptrs[4] = { dRays, dHits, dSurfaces, dOccluded };
     for (int i = 0; i < 4; ++i) {
         if (!ptrs[i]) continue;
         if (!onSceneDevice(ptrs[i], sd.device)) return setErr(PHIP_ERR_INVALID, who + "rays, hits, occlusion and surfaces must be device memory of the scene's device");
-        if (i < 3 && ((uintptr_t) ptrs[i] & 15u)) return setErr(PHIP_ERR_INVALID, who + "rays, hits and surfaces must be 16-byte aligned");
+        if (i < 3 && misaligned(ptrs[i], 16)) return setErr(PHIP_ERR_INVALID, who + "rays, hits and surfaces must be 16-byte aligned");
     }
     planRaycast(sd);
     const SceneDev::RaycastPlan &R = sd.raycast;
-    if (!sd.stream) HIP_TRY(hipStreamCreate(&sd.stream));
-    const hipStream_t stream = callerStream ? callerStream : sd.stream;
+    const hipStream_t stream = sceneStream(sd, callerStream);
     const unsigned blocks = (unsigned) std::min<size_t>(R.blocks, (n + WIDE_BLOCK - 1) / WIDE_BLOCK);
     /* the buffers cover the resident grid, whatever this call's: a later call of any size finds them */
     const size_t spillWords = (size_t) R.blocks * WIDE_BLOCK * SPILL_DEPTH, nWavesMax = (size_t) R.blocks * (WIDE_BLOCK / 64);
@@ -62,7 +57,7 @@ static int traceDevice(phip_scene *sc, const phip_ray *dRays, size_t n, phip_hit
     ev.record(stream);
     hipLaunchKernelGGL(R.k.cast, dim3(blocks), dim3(WIDE_BLOCK), R.lds, stream, sd.dev, (const float4 *) dRays, (uint32_t) n, (float4 *) dHits, dOccluded, P, sd.drawCounters.p);
     ev.record(stream);
-    if (dSurfaces) hipLaunchKernelGGL(R.k.surfaces, dim3((unsigned) ((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, sd.dev, (const float4 *) dRays, (const float4 *) dHits, (uint32_t) n, (float4 *) dSurfaces);
+    if (dSurfaces) hipLaunchKernelGGL(R.k.surfaces, dim3(blocksFor(n)), dim3(BLOCK), 0, stream, sd.dev, (const float4 *) dRays, (const float4 *) dHits, (uint32_t) n, (float4 *) dSurfaces);
     ev.record(stream);
     if (stats) {
         HIP_TRY(hipMemsetAsync(sd.counters.p, 0, sizeof(Counters), stream));

@@ -3,10 +3,10 @@
  * over the feature sets; megaKernelOf, shadeKernelOf, shadeTraceWideKernelOf), the residency query of the persistent ones (residentBlocksPerCU), the byte model
  * of the statistics, validation of the parameters, the plans (FusedPlan, WavefrontPlan), and the render as stages over one RenderJob with renderOnDevice as
  * their one pass loop.  Every kernel launch of a render is here.
- * Host code only; included by phip.hip alone, after host_scene.h.
+ * Host code only; included by phip.hip alone, after host_boundary.h.
  */
 #pragma once
-#include "host_scene.h"
+#include "host_boundary.h"
 
 /* ---- which kernel a render runs (the look-ups of the other units: phip_common.h) ---- */
 /* The look-ups of one feature set of the shading kernels (FEAT: 1 environment emitter, 2 bitmap textures, 8 the QMC samplers -- without / with both other features) */
@@ -770,10 +770,9 @@ static void passResults(RenderJob &J) {
 static int renderOnDevice(phip_scene *sc, SceneDev &sd, const phip_render_params *p, int shardIndex, int shardCount, float *dOut, phip_stats *stats) {
     HIP_TRY(hipSetDevice(sd.device));
     RenderJob J(sc, sd, p, dOut);
-    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, sd.device) == hipSuccess) J.nCU = prop.multiProcessorCount; }
+    J.nCU = cuCount(sd.device, J.nCU);
     shardTiles(J, shardIndex, shardCount);
-    J.stream = (p->n_devices <= 1) ? (hipStream_t) p->stream : nullptr;    /* a caller's stream belongs to one device */
-    if (!J.stream) { if (!sd.stream) HIP_TRY(hipStreamCreate(&sd.stream)); J.stream = sd.stream; }
+    J.stream = sceneStream(sd, p->n_devices <= 1 ? p->stream : nullptr);    /* a caller's stream belongs to one device */
     planPasses(J, (unsigned long long) sd.nLocalTiles * ((unsigned long long) J.bs * J.bs));
     if (J.keepSamples) { sd.sampleOut.alloc((size_t) J.W * J.H * (size_t) p->spp); HIP_TRY(hipMemsetAsync(sd.sampleOut.p, 0, sd.sampleOut.n * sizeof(float4), J.stream)); }
     sd.haveSamples = J.keepSamples; sd.lastSpp = (uint32_t) p->spp;

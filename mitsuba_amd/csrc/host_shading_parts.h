@@ -4,73 +4,62 @@
  * phip_film_device these are the parts of a render the caller's own integrator is written over.
  * The calls take no render parameters: there is no sampler, no pass and no pool -- one launch of one lane per item, ordered after the caller's stream and complete on
  * return.  They allocate nothing.  Everything is validated before the launch, so a refused call has written nothing.
- * Host code only; included by phip.hip alone, after host_camera_film.h.  The caller holds the scene's render lock.
+ * Host code only; included by phip.hip alone, after host_boundary.h.  The caller holds the scene's render lock.
  */
 #pragma once
-#include "host_raycast.h"
+#include "host_boundary.h"
 
 /* What the arguments say without a device (the debug library tests it on a machine without one): NULL, or the refusal.  Every refusal is PHIP_ERR_INVALID.
    n == 0 is served before any pointer is looked at. */
-static bool partsMisaligned(const void *p, size_t align) { return ((uintptr_t) p & (align - 1u)) != 0; }
 
 static const char *bsdfArgsError(bool haveScene, const phip_bsdf_desc *b) {
     if (!haveScene || !b) return "NULL argument";
     if (b->flags & ~PHIP_BSDF_LOCAL) return "unknown flag";
     if (b->n == 0) return nullptr;
-    if (b->n > RAYCAST_MAX_RAYS) return "more than 2^32 - 256 items in one call";
+    if (b->n > CALL_MAX_ITEMS) return "more than 2^32 - 256 items in one call";
     if (!b->d_rays || !b->d_hits) return "d_rays and d_hits must not be NULL";
     if (!b->d_eval && !b->d_sampled && !b->d_wi_local) return "no output: one of d_eval, d_sampled and d_wi_local must be set";
     if (b->d_eval && !b->d_wo) return "d_eval needs d_wo";
     if (b->d_sampled && !b->d_samples) return "d_sampled needs d_samples";
-    if (partsMisaligned(b->d_rays, 16) || partsMisaligned(b->d_hits, 16) || partsMisaligned(b->d_wo, 16) || partsMisaligned(b->d_eval, 16) || partsMisaligned(b->d_sampled, 16) ||
-        partsMisaligned(b->d_wi_local, 16)) return "d_rays, d_hits, d_wo, d_eval, d_sampled and d_wi_local must be 16-byte aligned";
-    if (partsMisaligned(b->d_samples, 8)) return "d_samples must be 8-byte aligned";
+    if (misaligned(b->d_rays, 16) || misaligned(b->d_hits, 16) || misaligned(b->d_wo, 16) || misaligned(b->d_eval, 16) || misaligned(b->d_sampled, 16) ||
+        misaligned(b->d_wi_local, 16)) return "d_rays, d_hits, d_wo, d_eval, d_sampled and d_wi_local must be 16-byte aligned";
+    if (misaligned(b->d_samples, 8)) return "d_samples must be 8-byte aligned";
     return nullptr;
 }
 
 static const char *emitterSampleArgsError(bool haveScene, const phip_emitter_sample_desc *e) {
     if (!haveScene || !e) return "NULL argument";
     if (e->n == 0) return nullptr;
-    if (e->n > RAYCAST_MAX_RAYS) return "more than 2^32 - 256 items in one call";
+    if (e->n > CALL_MAX_ITEMS) return "more than 2^32 - 256 items in one call";
     if (!e->d_ref || !e->d_samples || !e->d_sampled) return "d_ref, d_samples and d_sampled must not be NULL";
-    if (partsMisaligned(e->d_ref, 16) || partsMisaligned(e->d_ref_n, 16) || partsMisaligned(e->d_sampled, 16) || partsMisaligned(e->d_shadow_rays, 16))
+    if (misaligned(e->d_ref, 16) || misaligned(e->d_ref_n, 16) || misaligned(e->d_sampled, 16) || misaligned(e->d_shadow_rays, 16))
         return "d_ref, d_ref_n, d_sampled and d_shadow_rays must be 16-byte aligned";
-    if (partsMisaligned(e->d_samples, 8)) return "d_samples must be 8-byte aligned";
+    if (misaligned(e->d_samples, 8)) return "d_samples must be 8-byte aligned";
     return nullptr;
 }
 
 static const char *emitterEvalArgsError(bool haveScene, const phip_emitter_eval_desc *e) {
     if (!haveScene || !e) return "NULL argument";
     if (e->n == 0) return nullptr;
-    if (e->n > RAYCAST_MAX_RAYS) return "more than 2^32 - 256 items in one call";
+    if (e->n > CALL_MAX_ITEMS) return "more than 2^32 - 256 items in one call";
     if (!e->d_rays || !e->d_hits || !e->d_eval) return "d_rays, d_hits and d_eval must not be NULL";
-    if (partsMisaligned(e->d_rays, 16) || partsMisaligned(e->d_hits, 16) || partsMisaligned(e->d_ref_n, 16) || partsMisaligned(e->d_eval, 16) || partsMisaligned(e->d_emitter, 16))
+    if (misaligned(e->d_rays, 16) || misaligned(e->d_hits, 16) || misaligned(e->d_ref_n, 16) || misaligned(e->d_eval, 16) || misaligned(e->d_emitter, 16))
         return "d_rays, d_hits, d_ref_n, d_eval and d_emitter must be 16-byte aligned";
     return nullptr;
 }
 
-/* every pointer given is device memory of the scene's device */
-template <size_t N> static bool partsOnDevice(const SceneDev &sd, const void *const (&ptrs)[N]) {
-    for (size_t i = 0; i < N; ++i)
-        if (ptrs[i] && !onSceneDevice(ptrs[i], sd.device)) return false;
-    return true;
-}
-/* the stream the launch is ordered on: the caller's, or the scene's */
-static hipStream_t partsStream(SceneDev &sd, void *callerStream) {
-    if (callerStream) return (hipStream_t) callerStream;
-    if (!sd.stream) HIP_TRY(hipStreamCreate(&sd.stream));
-    return sd.stream;
-}
-#define PARTS_NOT_ON_DEVICE "every pointer must be device memory of the scene's device"
-static unsigned partsBlocks(size_t n) { return (unsigned) ((n + BLOCK - 1) / BLOCK); }
+/* ... as the entry points and their test hooks return them */
+static int bsdfRefusal(bool haveScene, const phip_bsdf_desc *b) { return refusal("phip_bsdf_device", PHIP_ERR_INVALID, bsdfArgsError(haveScene, b)); }
+static int emitterSampleRefusal(bool haveScene, const phip_emitter_sample_desc *e) { return refusal("phip_emitter_sample_device", PHIP_ERR_INVALID, emitterSampleArgsError(haveScene, e)); }
+static int emitterEvalRefusal(bool haveScene, const phip_emitter_eval_desc *e) { return refusal("phip_emitter_eval_device", PHIP_ERR_INVALID, emitterEvalArgsError(haveScene, e)); }
 
 static int bsdfDevice(phip_scene *sc, const phip_bsdf_desc *b) {
     SceneDev &sd = *sc->devs[0];
-    const void *const ptrs[7] = { b->d_rays, b->d_hits, b->d_wo, b->d_samples, b->d_eval, b->d_sampled, b->d_wi_local };
-    if (!partsOnDevice(sd, ptrs)) return setErr(PHIP_ERR_INVALID, "phip_bsdf_device: " PARTS_NOT_ON_DEVICE);
-    const hipStream_t stream = partsStream(sd, b->stream);
+    if (!allOnSceneDevice(sd, { b->d_rays, b->d_hits, b->d_wo, b->d_samples, b->d_eval, b->d_sampled, b->d_wi_local }))
+        return setErr(PHIP_ERR_INVALID, "phip_bsdf_device: every pointer must be device memory of the scene's device");
+    const hipStream_t stream = sceneStream(sd, b->stream);
     const ShadingPartsKernels K = phipShadingPartsKernels();
-    hipLaunchKernelGGL(K.bsdf[(b->d_eval ? 1 : 0) | (b->d_sampled ? 2 : 0)], dim3(partsBlocks(b->n)), dim3(BLOCK), 0, stream, sd.dev, (const float4 *) b->d_rays, (const float4 *) b->d_hits,
+    hipLaunchKernelGGL(K.bsdf[(b->d_eval ? 1 : 0) | (b->d_sampled ? 2 : 0)], dim3(blocksFor(b->n)), dim3(BLOCK), 0, stream, sd.dev, (const float4 *) b->d_rays, (const float4 *) b->d_hits,
                        (const float4 *) b->d_wo, (const float2 *) b->d_samples, (uint32_t) b->n, (uint32_t) (b->flags & PHIP_BSDF_LOCAL), (float4 *) b->d_eval, (float4 *) b->d_sampled, (float4 *) b->d_wi_local);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
@@ -79,11 +68,11 @@ static int bsdfDevice(phip_scene *sc, const phip_bsdf_desc *b) {
 
 static int emitterSampleDevice(phip_scene *sc, const phip_emitter_sample_desc *e) {
     SceneDev &sd = *sc->devs[0];
-    const void *const ptrs[5] = { e->d_ref, e->d_ref_n, e->d_samples, e->d_sampled, e->d_shadow_rays };
-    if (!partsOnDevice(sd, ptrs)) return setErr(PHIP_ERR_INVALID, "phip_emitter_sample_device: " PARTS_NOT_ON_DEVICE);
-    const hipStream_t stream = partsStream(sd, e->stream);
+    if (!allOnSceneDevice(sd, { e->d_ref, e->d_ref_n, e->d_samples, e->d_sampled, e->d_shadow_rays }))
+        return setErr(PHIP_ERR_INVALID, "phip_emitter_sample_device: every pointer must be device memory of the scene's device");
+    const hipStream_t stream = sceneStream(sd, e->stream);
     const ShadingPartsKernels K = phipShadingPartsKernels();
-    hipLaunchKernelGGL(K.emitterSample[sd.dev.envEmitter >= 0 ? 1 : 0], dim3(partsBlocks(e->n)), dim3(BLOCK), 0, stream, sd.dev, (const float4 *) e->d_ref, (const float4 *) e->d_ref_n,
+    hipLaunchKernelGGL(K.emitterSample[sd.dev.envEmitter >= 0 ? 1 : 0], dim3(blocksFor(e->n)), dim3(BLOCK), 0, stream, sd.dev, (const float4 *) e->d_ref, (const float4 *) e->d_ref_n,
                        (const float2 *) e->d_samples, (uint32_t) e->n, (float4 *) e->d_sampled, (float4 *) e->d_shadow_rays);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
@@ -92,11 +81,11 @@ static int emitterSampleDevice(phip_scene *sc, const phip_emitter_sample_desc *e
 
 static int emitterEvalDevice(phip_scene *sc, const phip_emitter_eval_desc *e) {
     SceneDev &sd = *sc->devs[0];
-    const void *const ptrs[5] = { e->d_rays, e->d_hits, e->d_ref_n, e->d_eval, e->d_emitter };
-    if (!partsOnDevice(sd, ptrs)) return setErr(PHIP_ERR_INVALID, "phip_emitter_eval_device: " PARTS_NOT_ON_DEVICE);
-    const hipStream_t stream = partsStream(sd, e->stream);
+    if (!allOnSceneDevice(sd, { e->d_rays, e->d_hits, e->d_ref_n, e->d_eval, e->d_emitter }))
+        return setErr(PHIP_ERR_INVALID, "phip_emitter_eval_device: every pointer must be device memory of the scene's device");
+    const hipStream_t stream = sceneStream(sd, e->stream);
     const ShadingPartsKernels K = phipShadingPartsKernels();
-    hipLaunchKernelGGL(K.emitterEval[sd.dev.envEmitter >= 0 ? 1 : 0], dim3(partsBlocks(e->n)), dim3(BLOCK), 0, stream, sd.dev, (const float4 *) e->d_rays, (const float4 *) e->d_hits,
+    hipLaunchKernelGGL(K.emitterEval[sd.dev.envEmitter >= 0 ? 1 : 0], dim3(blocksFor(e->n)), dim3(BLOCK), 0, stream, sd.dev, (const float4 *) e->d_rays, (const float4 *) e->d_hits,
                        (const float4 *) e->d_ref_n, (uint32_t) e->n, (float4 *) e->d_eval, e->d_emitter);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));

@@ -9,10 +9,10 @@
  * phip_scene_rebuild is the same call with one more step (rebuild = true; scenes on the 8-wide tree only): behind the scene box a new topology is built on the
  * device (host_rebuild.h), the Wald and refit passes run on IT, and everything the call writes goes to fresh buffers that are swapped in at the end -- the
  * depth of the new tree is known only then, and a refusal has to leave the scene unchanged.
- * Host code only; included by phip.hip alone, after host_scene.h.  The caller holds the scene's render lock.
+ * Host code only; included by phip.hip alone, after host_boundary.h.  The caller holds the scene's render lock and has made the scene's device current.
  */
 #pragma once
-#include "host_scene.h"
+#include "host_boundary.h"
 #include "host_rebuild.h"
 
 /* the creation's side tables on the device, the scratch of the passes: made by a scene's first update */
@@ -27,13 +27,6 @@ static void updateDeviceTables(phip_scene *sc) {
     U.onDevice = true;
 }
 
-/* a caller's device array: device memory of the scene's device */
-static bool onSceneDevice(const void *p, int device) {
-    hipPointerAttribute_t attr; memset(&attr, 0, sizeof(attr));
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void) hipGetLastError(); return false; }
-    return attr.type == hipMemoryTypeDevice && attr.device == device;
-}
-
 static int updateScene(phip_scene *sc, const phip_update_desc &u, phip_update_info *info, bool rebuild = false) {
     const auto t0 = std::chrono::steady_clock::now();
     const std::string who = rebuild ? "phip_scene_rebuild: " : "phip_scene_update: ";
@@ -43,14 +36,13 @@ static int updateScene(phip_scene *sc, const phip_update_desc &u, phip_update_in
     if (u.normals && !U.hasNormals) return setErr(PHIP_ERR_INVALID, who + "normals for a scene that was created without normals");
     const phip_camera cam = u.camera ? *u.camera : sc->descCopy.camera;
     for (int i = 0; i < 16; ++i) if (!std::isfinite(cam.to_world[i])) return setErr(PHIP_ERR_INVALID, who + "non-finite camera transform");
-    HIP_TRY(hipSetDevice(sd.device));
     HIP_TRY(hipDeviceSynchronize());          /* (a render on a caller's stream has been waited for by its call; this costs nothing then) */
     const bool newVertices = (u.positions || u.normals) && U.nTriangles > 0;
     UpdateArgs A; memset(&A, 0, sizeof(A));
     if (U.nTriangles > 0) {
         updateDeviceTables(sc);
         if (u.device_pointers) {
-            if ((u.positions && !onSceneDevice(u.positions, sd.device)) || (u.normals && !onSceneDevice(u.normals, sd.device)))
+            if (!allOnSceneDevice(sd, { u.positions, u.normals }))
                 return setErr(PHIP_ERR_INVALID, who + "device_pointers = 1, but positions / normals are not device memory of the scene's device");
             HIP_TRY(hipStreamSynchronize((hipStream_t) u.stream));           /* ordered after the caller's producer */
             A.positions = u.positions; A.normals = u.normals;

@@ -46,10 +46,13 @@
  *   k_shading_parts.h  phip_bsdf_device / phip_emitter_sample_device / phip_emitter_eval_device: k_bsdf_parts, k_emitter_sample, k_emitter_eval -- one lane per item around
  *                 the vertex's own BSDF and emitter functions (dv_scene.h)                                                                                 [phip_shading_parts.hip]
  *
- * This file: the C ABI -- error state, the guard that maps what an entry point's body throws to its error code, the entry of both render functions, the film's way
- * to the host and the extern "C" entry points.  The rest of the host side is three headers by concern, each including the ones before it:
+ * This file: the C ABI -- error state, the guard that maps what an entry point's body throws to its error code (guarded) and the one that brings the entry points on
+ * the caller's device memory to their bodies (onDevice: a device, the scene's device current, the render lock), the entry of both render functions, the film's way
+ * to the host and the extern "C" entry points.  The rest of the host side is headers by concern, each including the ones before it:
  *   host_scene.h   scene construction as stages over one SceneBuild (validation, host arrays, BVH build via bvh.h, the choice of the device paths, one upload;
  *                  camera set-up), replication of the scene to further GPUs through SceneDev's one list of buffers
+ *   host_boundary.h what a call on the caller's device memory needs, once: whose memory a pointer is, its alignment, the items of one call, the caller's stream or
+ *                  the scene's, the device the parameters name, a device's CU count, a refusal under its call's name
  *   host_render.h  the choice of each render's kernels and the render loop of one device
  *   host_multi.h   the multi-device orchestration (one host thread + stream per GPU, ncclReduce of the films over RCCL/xGMI)
  *   host_update.h  phip_scene_update: new vertices and camera on the tree as built (the kernels: k_update.h in phip_update.hip); with host_rebuild.h, which it
@@ -59,10 +62,10 @@
  *   host_raycast.h phip_trace_device: the persistent ray server's plan and launch on the caller's stream, the surface records behind it (k_raycast.h in phip_raycast.hip)
  *   host_radiance.h phip_radiance_device: a render job without a film over the caller's rays -- the passes and the pass loop of host_render.h, k_shade_r for k_shade,
  *                  k_radiance_out for the film pass (k_shade_r.h in phip_shade_r.hip)
- *   host_camera_film.h phip_camera_rays_device and phip_film_device: the camera samples out, per-sample values onto a film -- validation before any launch
- *                  (k_camera_film.h in phip_camera_film.hip)
+ *   host_camera_film.h phip_camera_rays_device and phip_film_device: the camera samples out, per-sample values onto a film (k_camera_film.h in phip_camera_film.hip)
  *   host_shading_parts.h phip_bsdf_device, phip_emitter_sample_device and phip_emitter_eval_device: the BSDF at the hits of a ray cast, emitter sampling and emitter
- *                  evaluation on the caller's arrays -- validation before any launch (k_shading_parts.h in phip_shading_parts.hip)
+ *                  evaluation on the caller's arrays (k_shading_parts.h in phip_shading_parts.hip)
+ * Each of the last four holds its call's checks of the arguments that need no device (`*ArgsError`, `*Refusal`: all of them come before any launch) and its body.
  * Not MFMA work: irregular traversal and gathers.  The product never includes, links or calls anything under oracle/.
  */
 #include "phip_common.h"
@@ -93,6 +96,7 @@ static int setErr(int code, const std::string &msg) { g_err = msg; return code; 
  *  host side: the scene, one device's render, the render on several devices
  * ====================================================================================== */
 #include "host_scene.h"
+#include "host_boundary.h"
 #include "host_render.h"
 #include "host_multi.h"
 #include "host_update.h"
@@ -110,8 +114,7 @@ static int renderLocked(phip_scene *sc, const phip_render_params *p, float *dOut
     if (p->n_devices > 1) {
         rc = renderMultiDevice(sc, p, dOut, stats);
     } else {
-        const int device = p->n_devices == 1 ? p->devices[0] : p->device;
-        if (device != sc->devs[0]->device) throw std::invalid_argument("scene was created on a different device");
+        requireSceneDevice(*sc->devs[0], p);
         rc = renderOnDevice(sc, *sc->devs[0], p, p->shard_index, p->shard_count > 0 ? p->shard_count : 1, dOut, stats);
     }
     if (rc == PHIP_ERR_CANCELLED) {
@@ -133,7 +136,7 @@ static int renderImpl(phip_scene *sc, const phip_render_params *p, float *dOut, 
 struct ErrorCodes { int invalid, other; };
 static const ErrorCodes CREATE_ERRORS = { PHIP_ERR_UNSUPPORTED, PHIP_ERR_INVALID };     /* phip_scene_create: a scene the back end does not serve / a malformed one */
 static const ErrorCodes RENDER_ERRORS = { PHIP_ERR_INVALID, PHIP_ERR_DEVICE };          /* phip_render, phip_render_device: a bad argument / the runtime */
-static const ErrorCodes DEVICE_ERRORS = { PHIP_ERR_DEVICE, PHIP_ERR_DEVICE };           /* phip_scene_replicate, phip_scene_update, phip_scene_rebuild, phip_scene_update_appearance, phip_film_to_host, phip_trace, phip_trace_device, phip_bsdf_device, phip_emitter_sample_device, phip_emitter_eval_device: their bodies check arguments themselves */
+static const ErrorCodes DEVICE_ERRORS = { PHIP_ERR_DEVICE, PHIP_ERR_DEVICE };           /* every other guarded entry point: its body checks the arguments itself and returns its refusals */
 template <typename Body> static int guarded(const ErrorCodes &codes, Body body) {
     try {
         return body();
@@ -144,19 +147,20 @@ template <typename Body> static int guarded(const ErrorCodes &codes, Body body) 
     }
 }
 
-/* the three shading parts: arguments (no device needed), the device, the scene's render lock, the launch */
-template <typename Desc, typename Check, typename Run>
-static int shadingPartsEntry(const char *name, phip_scene *scene, const Desc *desc, Check check, Run run) {
-    if (const char *bad = check(scene != nullptr, desc)) return setErr(PHIP_ERR_INVALID, std::string(name) + ": " + bad);
-    if (desc->n == 0) return PHIP_OK;
-    int nDev = phip_device_count();
-    if (nDev <= 0) return setErr(PHIP_ERR_DEVICE, std::string(name) + ": " + (nDev == 0 ? std::string("no HIP device visible: path_hip has no CPU fallback") : g_err));
-    const int rc = guarded(DEVICE_ERRORS, [&]() -> int {
+/* The entry points that need a device, once their own checks of the arguments have passed: a device to run on, the scene's device current, the scene's render lock
+   (it serialises the call with the renders), the body.  `name`: the call's name goes in front of PHIP_ERR_DEVICE's text -- what the runtime said; the body's own
+   refusals carry it already -- as the three shading parts have it; NULL: the text as it is. */
+static const char NO_DEVICE[] = "no HIP device visible: path_hip has no CPU fallback";
+template <typename Body> static int onDevice(const ErrorCodes &codes, phip_scene *scene, const char *name, Body body) {
+    const std::string who = name ? std::string(name) + ": " : std::string();
+    const int nDev = phip_device_count();
+    if (nDev <= 0) return setErr(PHIP_ERR_DEVICE, who + (nDev == 0 ? std::string(NO_DEVICE) : g_err));
+    const int rc = guarded(codes, [&]() -> int {
         HIP_TRY(hipSetDevice(scene->devs[0]->device));
         std::lock_guard<std::mutex> lock(scene->renderLock);
-        return run(scene, desc);
+        return body();
     });
-    if (rc == PHIP_ERR_DEVICE) g_err = std::string(name) + ": " + g_err;      /* (what the runtime said; the refusals carry the name already) */
+    if (name && rc == PHIP_ERR_DEVICE) g_err = who + g_err;
     return rc;
 }
 
@@ -182,7 +186,7 @@ int phip_device_count(void) {
 phip_scene *phip_scene_create(const phip_scene_desc *desc, int device) {
     if (!desc) { setErr(PHIP_ERR_INVALID, "desc is NULL"); return nullptr; }
     int n = phip_device_count();
-    if (n <= 0) { if (n == 0) setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback"); return nullptr; }
+    if (n <= 0) { if (n == 0) setErr(PHIP_ERR_DEVICE, NO_DEVICE); return nullptr; }
     if (device < 0 || device >= n) { setErr(PHIP_ERR_INVALID, "device ordinal out of range"); return nullptr; }
     phip_scene *sc = new (std::nothrow) phip_scene();
     if (!sc) { setErr(PHIP_ERR_NOMEM, "out of memory"); return nullptr; }
@@ -211,21 +215,13 @@ int phip_scene_replicate(phip_scene *scene, const int32_t *devices, int32_t n_de
 int phip_scene_update(phip_scene *scene, const phip_update_desc *u, phip_update_info *out_info) {
     if (!scene || !u) return setErr(PHIP_ERR_INVALID, "NULL argument");
     if (out_info) memset(out_info, 0, sizeof(*out_info));
-    int n = phip_device_count();
-    if (n <= 0) return n == 0 ? setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback") : PHIP_ERR_DEVICE;
-    return guarded(DEVICE_ERRORS, [&]() -> int {
-        std::lock_guard<std::mutex> lock(scene->renderLock);          /* serialises with renders */
-        return updateScene(scene, *u, out_info);
-    });
+    return onDevice(DEVICE_ERRORS, scene, nullptr, [&] { return updateScene(scene, *u, out_info); });
 }
 
 int phip_scene_rebuild(phip_scene *scene, const phip_update_desc *u, phip_update_info *out_info) {
     if (!scene) return setErr(PHIP_ERR_INVALID, "NULL argument");
     if (out_info) memset(out_info, 0, sizeof(*out_info));
-    int n = phip_device_count();
-    if (n <= 0) return n == 0 ? setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback") : PHIP_ERR_DEVICE;
-    return guarded(DEVICE_ERRORS, [&]() -> int {
-        std::lock_guard<std::mutex> lock(scene->renderLock);
+    return onDevice(DEVICE_ERRORS, scene, nullptr, [&] {
         phip_update_desc none; memset(&none, 0, sizeof(none));          /* update == NULL: the scene's current vertices and camera */
         /* a scene of at most 64 Wald records keeps its packed leaf table and the tree of its creation: the update serves it */
         return updateScene(scene, u ? *u : none, out_info, scene->wideOnly);
@@ -236,12 +232,7 @@ int phip_scene_update_appearance(phip_scene *scene, const phip_appearance_desc *
     if (!scene) return setErr(PHIP_ERR_INVALID, "NULL argument");
     if (out_info) memset(out_info, 0, sizeof(*out_info));
     if (appearanceEmpty(desc)) return PHIP_OK;          /* nothing to change */
-    int n = phip_device_count();
-    if (n <= 0) return n == 0 ? setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback") : PHIP_ERR_DEVICE;
-    return guarded(DEVICE_ERRORS, [&]() -> int {
-        std::lock_guard<std::mutex> lock(scene->renderLock);          /* serialises with renders */
-        return updateAppearance(scene, *desc, out_info);
-    });
+    return onDevice(DEVICE_ERRORS, scene, nullptr, [&] { return updateAppearance(scene, *desc, out_info); });
 }
 
 int phip_render_device(phip_scene *scene, const phip_render_params *params, void *d_out, phip_stats *out_stats) {
@@ -269,13 +260,13 @@ static void parallelCopy(char *dst, const char *src, size_t bytes) {
     for (auto &t : th) t.join();
 }
 static void filmToHost(SceneDev &sd, float *dst, const float *dFilm, size_t bytes) {
-    if (!sd.stream) HIP_TRY(hipStreamCreate(&sd.stream));
+    const hipStream_t stream = sceneStream(sd, nullptr);
     hipPointerAttribute_t attr; memset(&attr, 0, sizeof(attr));
     const hipError_t e = hipPointerGetAttributes(&attr, dst);
     if (e != hipSuccess) (void) hipGetLastError();             /* an unregistered host pointer is "invalid value" on some runtimes: pageable */
     if (e == hipSuccess && attr.type == hipMemoryTypeHost) {
-        HIP_TRY(hipMemcpyAsync(dst, dFilm, bytes, hipMemcpyDeviceToHost, sd.stream));
-        HIP_TRY(hipStreamSynchronize(sd.stream));
+        HIP_TRY(hipMemcpyAsync(dst, dFilm, bytes, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         return;
     }
     if (bytes <= ((size_t) 256 << 10)) {                       /* a small frame: not worth 8 MB of pinned staging (their allocation is 8 ms) */
@@ -289,8 +280,8 @@ static void filmToHost(SceneDev &sd, float *dst, const float *dFilm, size_t byte
     const size_t nChunks = (bytes + FILM_STAGE_BYTES - 1) / FILM_STAGE_BYTES;
     auto issue = [&](size_t c) {
         const size_t off = c * FILM_STAGE_BYTES, len = std::min(FILM_STAGE_BYTES, bytes - off);
-        HIP_TRY(hipMemcpyAsync(sd.stage[c & 1], (const char *) dFilm + off, len, hipMemcpyDeviceToHost, sd.stream));
-        HIP_TRY(hipEventRecord(sd.stageDone[c & 1], sd.stream));
+        HIP_TRY(hipMemcpyAsync(sd.stage[c & 1], (const char *) dFilm + off, len, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipEventRecord(sd.stageDone[c & 1], stream));
     };
     if (nChunks) issue(0);
     for (size_t c = 0; c < nChunks; ++c) {
@@ -416,61 +407,46 @@ int phip_trace(phip_scene *scene, const phip_ray *rays, size_t n, phip_hit *hits
 
 int phip_trace_device(phip_scene *scene, const phip_ray *d_rays, size_t n, phip_hit *d_hits, uint8_t *d_occluded, phip_surface *d_surfaces, void *stream, phip_stats *out_stats) {
     if (!scene || (!d_rays && n)) return setErr(PHIP_ERR_INVALID, "NULL argument");
-    int nDev = phip_device_count();
-    if (nDev <= 0) return nDev == 0 ? setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback") : PHIP_ERR_DEVICE;
-    return guarded(DEVICE_ERRORS, [&]() -> int {
-        HIP_TRY(hipSetDevice(scene->devs[0]->device));
-        std::lock_guard<std::mutex> lock(scene->renderLock);
-        return traceDevice(scene, d_rays, n, d_hits, d_occluded, d_surfaces, (hipStream_t) stream, out_stats);
-    });
+    return onDevice(DEVICE_ERRORS, scene, nullptr, [&] { return traceDevice(scene, d_rays, n, d_hits, d_occluded, d_surfaces, stream, out_stats); });
 }
 
 int phip_radiance_device(phip_scene *scene, const phip_render_params *params, const phip_radiance_desc *desc, phip_stats *out_stats) {
-    int code = PHIP_OK;
-    if (const char *bad = radianceArgsError(params, desc, code)) return setErr(code, std::string("phip_radiance_device: ") + bad);
+    if (const int rc = radianceRefusal(params, desc)) return rc;
     if (!scene) return setErr(PHIP_ERR_INVALID, "NULL argument");
     if (out_stats) memset(out_stats, 0, sizeof(*out_stats));
     if (desc->n == 0) return PHIP_OK;
-    int nDev = phip_device_count();
-    if (nDev <= 0) return nDev == 0 ? setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback") : PHIP_ERR_DEVICE;
-    return guarded(RENDER_ERRORS, [&]() -> int {
-        HIP_TRY(hipSetDevice(scene->devs[0]->device));
-        std::lock_guard<std::mutex> lock(scene->renderLock);
-        return radianceDevice(scene, params, desc, out_stats);
-    });
+    return onDevice(RENDER_ERRORS, scene, nullptr, [&] { return radianceDevice(scene, params, desc, out_stats); });
 }
 
 int phip_camera_rays_device(phip_scene *scene, const phip_render_params *params, const phip_camera_rays_desc *desc) {
-    int code = PHIP_OK;
-    if (const char *bad = cameraRaysArgsError(params, desc, code)) return setErr(code, std::string("phip_camera_rays_device: ") + bad);
+    if (const int rc = cameraRaysRefusal(params, desc)) return rc;
     if (!scene) return setErr(PHIP_ERR_INVALID, "NULL argument");
     if (desc->d_pixels && desc->m == 0) return PHIP_OK;
-    int nDev = phip_device_count();
-    if (nDev <= 0) return nDev == 0 ? setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback") : PHIP_ERR_DEVICE;
-    return guarded(RENDER_ERRORS, [&]() -> int {
-        HIP_TRY(hipSetDevice(scene->devs[0]->device));
-        std::lock_guard<std::mutex> lock(scene->renderLock);
-        return cameraRaysDevice(scene, params, desc);
-    });
+    return onDevice(RENDER_ERRORS, scene, nullptr, [&] { return cameraRaysDevice(scene, params, desc); });
 }
 
 int phip_film_device(phip_scene *scene, const phip_render_params *params, const phip_film_desc *desc, phip_stats *out_stats) {
-    int code = PHIP_OK;
-    if (const char *bad = filmArgsError(params, desc, code)) return setErr(code, std::string("phip_film_device: ") + bad);
+    if (const int rc = filmRefusal(params, desc)) return rc;
     if (!scene) return setErr(PHIP_ERR_INVALID, "NULL argument");
     if (out_stats) memset(out_stats, 0, sizeof(*out_stats));
-    int nDev = phip_device_count();
-    if (nDev <= 0) return nDev == 0 ? setErr(PHIP_ERR_DEVICE, "no HIP device visible: path_hip has no CPU fallback") : PHIP_ERR_DEVICE;
-    return guarded(RENDER_ERRORS, [&]() -> int {
-        HIP_TRY(hipSetDevice(scene->devs[0]->device));
-        std::lock_guard<std::mutex> lock(scene->renderLock);
-        return filmDevice(scene, params, desc, out_stats);
-    });
+    return onDevice(RENDER_ERRORS, scene, nullptr, [&] { return filmDevice(scene, params, desc, out_stats); });
 }
 
-int phip_bsdf_device(phip_scene *scene, const phip_bsdf_desc *desc) { return shadingPartsEntry("phip_bsdf_device", scene, desc, bsdfArgsError, bsdfDevice); }
-int phip_emitter_sample_device(phip_scene *scene, const phip_emitter_sample_desc *desc) { return shadingPartsEntry("phip_emitter_sample_device", scene, desc, emitterSampleArgsError, emitterSampleDevice); }
-int phip_emitter_eval_device(phip_scene *scene, const phip_emitter_eval_desc *desc) { return shadingPartsEntry("phip_emitter_eval_device", scene, desc, emitterEvalArgsError, emitterEvalDevice); }
+int phip_bsdf_device(phip_scene *scene, const phip_bsdf_desc *desc) {
+    if (const int rc = bsdfRefusal(scene != nullptr, desc)) return rc;
+    if (desc->n == 0) return PHIP_OK;
+    return onDevice(DEVICE_ERRORS, scene, "phip_bsdf_device", [&] { return bsdfDevice(scene, desc); });
+}
+int phip_emitter_sample_device(phip_scene *scene, const phip_emitter_sample_desc *desc) {
+    if (const int rc = emitterSampleRefusal(scene != nullptr, desc)) return rc;
+    if (desc->n == 0) return PHIP_OK;
+    return onDevice(DEVICE_ERRORS, scene, "phip_emitter_sample_device", [&] { return emitterSampleDevice(scene, desc); });
+}
+int phip_emitter_eval_device(phip_scene *scene, const phip_emitter_eval_desc *desc) {
+    if (const int rc = emitterEvalRefusal(scene != nullptr, desc)) return rc;
+    if (desc->n == 0) return PHIP_OK;
+    return onDevice(DEVICE_ERRORS, scene, "phip_emitter_eval_device", [&] { return emitterEvalDevice(scene, desc); });
+}
 
 void phip_cancel(phip_scene *scene) { if (scene && scene->cancelFlag) __atomic_store_n(scene->cancelFlag, 1, __ATOMIC_RELAXED); }
 

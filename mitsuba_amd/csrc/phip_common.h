@@ -3,8 +3,9 @@
  * shading functions (dv_scene.h), the path-pool layout (k_pool.h), the error macro.
  *
  * libphip.so is built from eleven sources (48 objects) so that they compile in parallel:
- *   phip.hip          the C ABI + traversal and film kernels, with the host side it includes by concern: host_scene.h (scene build, replicas), host_render.h (kernel
- *                     selection, one device's render loop), host_multi.h (multi-device orchestration, RCCL): 1 object
+ *   phip.hip          the C ABI + traversal and film kernels, with the host side it includes by concern: host_scene.h (scene build, replicas), host_boundary.h (what
+ *                     a call on the caller's device memory needs), host_render.h (kernel selection, one device's render loop), host_multi.h (multi-device
+ *                     orchestration, RCCL) and one header per entry point on the caller's device memory: 1 object
  *   phip_shade.hip    k_shade / k_shade_direct / k_shade_trace instantiations behind the look-ups phipShade*KernelF<n> -- compiled per feature set (-DSHADE_FEAT=0..3, 8
  *                     and 11: environment emitter, bitmap textures, the QMC samplers) and per part (-DSHADE_PART=0..3), 24 objects: see its header
  *   phip_shade_w.hip  k_shade_trace_w instantiations behind phipShadeTraceWideKernelF<n>, per feature set: 6 objects

@@ -643,21 +643,15 @@ extern "C" int phip_debug_rccl_selftest(int n_devices, size_t n_floats) {
 /* phip_radiance_device's checks of its arguments that need no device (host_radiance.h: radianceArgsError), for a machine without one: the code the entry point would
    return for them, PHIP_OK when it would go on to the scene and the pointers' attributes; the message in phip_last_error */
 extern "C" int phip_debug_host_radiance_args(const phip_render_params *params, const phip_radiance_desc *desc) {
-    int code = PHIP_OK;
-    if (const char *bad = radianceArgsError(params, desc, code)) return setErr(code, std::string("phip_radiance_device: ") + bad);
-    return PHIP_OK;
+    return radianceRefusal(params, desc);
 }
 
 /* ... and those of phip_camera_rays_device and phip_film_device (host_camera_film.h: cameraRaysArgsError, filmArgsError) */
 extern "C" int phip_debug_host_camera_rays_args(const phip_render_params *params, const phip_camera_rays_desc *desc) {
-    int code = PHIP_OK;
-    if (const char *bad = cameraRaysArgsError(params, desc, code)) return setErr(code, std::string("phip_camera_rays_device: ") + bad);
-    return PHIP_OK;
+    return cameraRaysRefusal(params, desc);
 }
 extern "C" int phip_debug_host_film_args(const phip_render_params *params, const phip_film_desc *desc) {
-    int code = PHIP_OK;
-    if (const char *bad = filmArgsError(params, desc, code)) return setErr(code, std::string("phip_film_device: ") + bad);
-    return PHIP_OK;
+    return filmRefusal(params, desc);
 }
 
 /* phip_scene_update_appearance's refusals on a machine without a device (host_appearance.h): the scene's look is taken from the descriptor of its creation by the
@@ -717,16 +711,13 @@ extern "C" int phip_debug_host_envmap_cdf(const phip_envmap *envmap, float *cdf_
 /* their checks of the arguments (host_shading_parts.h): the code the entry point would return for them, PHIP_OK when it would go on to the device and the
    pointers' attributes; the message in phip_last_error.  have_scene = 0: the scene argument is NULL */
 extern "C" int phip_debug_host_bsdf_args(int have_scene, const phip_bsdf_desc *desc) {
-    if (const char *bad = bsdfArgsError(have_scene != 0, desc)) return setErr(PHIP_ERR_INVALID, std::string("phip_bsdf_device: ") + bad);
-    return PHIP_OK;
+    return bsdfRefusal(have_scene != 0, desc);
 }
 extern "C" int phip_debug_host_emitter_sample_args(int have_scene, const phip_emitter_sample_desc *desc) {
-    if (const char *bad = emitterSampleArgsError(have_scene != 0, desc)) return setErr(PHIP_ERR_INVALID, std::string("phip_emitter_sample_device: ") + bad);
-    return PHIP_OK;
+    return emitterSampleRefusal(have_scene != 0, desc);
 }
 extern "C" int phip_debug_host_emitter_eval_args(int have_scene, const phip_emitter_eval_desc *desc) {
-    if (const char *bad = emitterEvalArgsError(have_scene != 0, desc)) return setErr(PHIP_ERR_INVALID, std::string("phip_emitter_eval_device: ") + bad);
-    return PHIP_OK;
+    return emitterEvalRefusal(have_scene != 0, desc);
 }
 
 /* The DevScene of a descriptor on the host: the stages phip_scene_create runs before it uploads (none of them calls HIP) -- shapes, textures, materials, emitters,
@@ -753,7 +744,7 @@ struct HostSceneTwin {
    argument checks (alignment included) */
 extern "C" int phip_debug_host_bsdf_parts(const phip_scene_desc *created, const phip_bsdf_desc *b) {
     if (!created) return setErr(PHIP_ERR_INVALID, "NULL argument");
-    if (const char *bad = bsdfArgsError(true, b)) return setErr(PHIP_ERR_INVALID, std::string("phip_bsdf_device: ") + bad);
+    if (const int rc = bsdfRefusal(true, b)) return rc;
     try {
         HostSceneTwin H(*created);
         const float4 *rays = (const float4 *) b->d_rays, *hits = (const float4 *) b->d_hits, *wo = (const float4 *) b->d_wo;
@@ -778,7 +769,7 @@ extern "C" int phip_debug_host_bsdf_parts(const phip_scene_desc *created, const 
 
 extern "C" int phip_debug_host_emitter_sample(const phip_scene_desc *created, const phip_emitter_sample_desc *e) {
     if (!created) return setErr(PHIP_ERR_INVALID, "NULL argument");
-    if (const char *bad = emitterSampleArgsError(true, e)) return setErr(PHIP_ERR_INVALID, std::string("phip_emitter_sample_device: ") + bad);
+    if (const int rc = emitterSampleRefusal(true, e)) return rc;
     try {
         HostSceneTwin H(*created);
         const EmitterTab T = H.table();
@@ -798,7 +789,7 @@ extern "C" int phip_debug_host_emitter_sample(const phip_scene_desc *created, co
 
 extern "C" int phip_debug_host_emitter_eval(const phip_scene_desc *created, const phip_emitter_eval_desc *e) {
     if (!created) return setErr(PHIP_ERR_INVALID, "NULL argument");
-    if (const char *bad = emitterEvalArgsError(true, e)) return setErr(PHIP_ERR_INVALID, std::string("phip_emitter_eval_device: ") + bad);
+    if (const int rc = emitterEvalRefusal(true, e)) return rc;
     try {
         HostSceneTwin H(*created);
         const EmitterTab T = H.table();

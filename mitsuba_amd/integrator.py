@@ -22,6 +22,21 @@ from . import _abi as A
 from . import _ffi
 
 
+def _ptr(t):
+    """the address of a tensor for a descriptor; None (NULL) for an output not asked for or an input not given"""
+    return t.data_ptr() if t is not None else None
+
+
+def _stream_handle(stream):
+    """the hipStream_t of a torch.cuda.Stream, or the raw handle (or None) as given"""
+    return getattr(stream, "cuda_stream", stream)
+
+
+def _check(rc, name):
+    if rc != 0:
+        raise _ffi.PhipError(rc, name)
+
+
 class Properties(dict):
     """Minimal typed property bag (include/mitsuba/core/properties.h)."""
 
@@ -60,9 +75,7 @@ class Scene:
 
     def accel_info(self):
         info = A.phip_accel_info()
-        rc = self._L.phip_scene_accel_info(self._h, C.byref(info))
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_scene_accel_info")
+        _check(self._L.phip_scene_accel_info(self._h, C.byref(info)), "phip_scene_accel_info")
         return info
 
     def rayIntersect(self, rays, closest=True, shadow=False):
@@ -72,11 +85,9 @@ class Scene:
         hits = np.zeros((n, 4), np.float32) if closest else None
         occ = np.zeros(n, np.uint8) if shadow else None
         st = A.phip_stats()
-        rc = self._L.phip_trace(self._h, r.ctypes.data_as(C.POINTER(A.phip_ray)), n,
-                                hits.ctypes.data_as(C.POINTER(A.phip_hit)) if closest else None,
-                                occ.ctypes.data_as(C.POINTER(C.c_uint8)) if shadow else None, C.byref(st))
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_trace")
+        _check(self._L.phip_trace(self._h, r.ctypes.data_as(C.POINTER(A.phip_ray)), n,
+                                  hits.ctypes.data_as(C.POINTER(A.phip_hit)) if closest else None,
+                                  occ.ctypes.data_as(C.POINTER(C.c_uint8)) if shadow else None, C.byref(st)), "phip_trace")
         return hits, occ, st
 
     def rayIntersectDevice(self, rays, closest=True, shadow=False, surfaces=False, stream=None):
@@ -86,24 +97,19 @@ class Scene:
         stats.trace_kernel_ms is the ray kernel's HIP-event time, stats.shade_kernel_ms that of the surface records' kernel.
         The rays must be finite.  ValueError for a tensor of another dtype, layout or device; PhipError for what the library refuses (surfaces without closest)."""
         import torch
-        if not hasattr(rays, "data_ptr") or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
-            raise ValueError("rays: expected a contiguous float32 tensor of shape (n, 8)")
-        if not rays.is_cuda or (rays.device.index or 0) != self.device:
-            raise ValueError("rays: the tensor is not on the scene's device")
+        rays = Scene._device_tensor(self, rays, "rays", 8)
         n = rays.shape[0]
         hits = torch.empty((n, 4), dtype=torch.float32, device=rays.device) if closest else None
         occ = torch.empty((n,), dtype=torch.uint8, device=rays.device) if shadow else None
         surf = torch.empty((n, 16), dtype=torch.float32, device=rays.device) if surfaces else None
-        ptr = lambda t: t.data_ptr() if t is not None else None
         st = A.phip_stats()
-        rc = self._L.phip_trace_device(self._h, ptr(rays), n, ptr(hits), ptr(occ), ptr(surf), getattr(stream, "cuda_stream", stream), C.byref(st))
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_trace_device")
+        rc = self._L.phip_trace_device(self._h, _ptr(rays), n, _ptr(hits), _ptr(occ), _ptr(surf), _stream_handle(stream), C.byref(st))
+        _check(rc, "phip_trace_device")
         return hits, occ, surf, st
 
     def _sensor_params(self, spp, seed, sample_offset, block_size, flags, stream):
         return A.default_render_params(spp=spp, seed=seed, sample_offset=sample_offset, block_size=block_size or self.block_size, device=self.device, flags=flags,
-                                       stream=getattr(stream, "cuda_stream", stream))
+                                       stream=_stream_handle(stream))
 
     def camera_rays(self, spp, seed=0, sample_offset=0, pixels=None, keys=True, positions=False, stream=None):
         """The camera samples a render traces, on the device (phip_camera_rays_device): for every pixel of the crop window in row-major order -- or for the pixels
@@ -114,11 +120,7 @@ class Scene:
         the library refuses (an index outside the crop window: nothing is written)."""
         import torch
         dev = torch.device("cuda", self.device)
-        if pixels is not None:
-            if not hasattr(pixels, "data_ptr") or pixels.dtype not in (torch.int32, torch.uint32) or not pixels.is_contiguous() or pixels.dim() != 1:
-                raise ValueError("pixels: expected a contiguous int32 or uint32 tensor of shape (m,)")
-            if not pixels.is_cuda or (pixels.device.index or 0) != self.device:
-                raise ValueError("pixels: the tensor is not on the scene's device")
+        pixels = Scene._device_tensor(self, pixels, "pixels", dtype=(torch.int32, torch.uint32), rows="m", optional=True)
         m = self.width * self.height if pixels is None else pixels.shape[0]
         n = m * spp
         rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
@@ -126,11 +128,9 @@ class Scene:
         pos = torch.empty((n, 2), dtype=torch.float32, device=dev) if positions else None
         if n == 0:                                  # an empty list: nothing to ask the library for
             return rays, k, pos
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        d = A.phip_camera_rays_desc(d_pixels=ptr(pixels), m=m, d_rays=ptr(rays), d_keys=ptr(k), d_positions=ptr(pos))
-        rc = self._L.phip_camera_rays_device(self._h, C.byref(self._sensor_params(spp, seed, sample_offset, None, 0, stream)), C.byref(d))
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_camera_rays_device")
+        d = A.phip_camera_rays_desc(d_pixels=_ptr(pixels), m=m, d_rays=_ptr(rays), d_keys=_ptr(k), d_positions=_ptr(pos))
+        p = self._sensor_params(spp, seed, sample_offset, None, 0, stream)
+        _check(self._L.phip_camera_rays_device(self._h, C.byref(p), C.byref(d)), "phip_camera_rays_device")
         return rays, k, pos
 
     def film(self, values, spp, seed=0, sample_offset=0, signed=False, out=None, accumulate=False, block_size=None, flags=0, stream=None):
@@ -153,19 +153,20 @@ class Scene:
         d = A.phip_film_desc(d_values=values.data_ptr(), d_out=out.data_ptr(), flags=A.PHIP_FILM_SIGNED if signed else 0, reserved=0)
         st = A.phip_stats()
         p = self._sensor_params(spp, seed, sample_offset, block_size, flags | (A.PHIP_FLAG_ACCUMULATE if accumulate else 0), stream)
-        rc = self._L.phip_film_device(self._h, C.byref(p), C.byref(d), C.byref(st))
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_film_device")
+        _check(self._L.phip_film_device(self._h, C.byref(p), C.byref(d), C.byref(st)), "phip_film_device")
         return out, st
 
-    def _device_tensor(self, t, name, cols, dtype=None, rows=None, optional=False):
-        """a contiguous (n, cols) tensor of `dtype` (default float32) on the scene's device, as the shading parts read and write them"""
+    def _device_tensor(self, t, name, cols=None, dtype=None, rows=None, optional=False):
+        """a contiguous tensor on the scene's device, as the calls on device memory read and write them: of shape (n, cols), or (n,) without `cols`; of `dtype`, one
+        torch dtype or a tuple of those accepted (default float32).  rows: the row count it must have, or the letter the refusal has for a free one (default n)"""
         import torch
         if t is None and optional:
             return None
-        dtype = dtype or torch.float32
-        if not hasattr(t, "data_ptr") or t.dtype != dtype or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != cols or (rows is not None and t.shape[0] != rows):
-            raise ValueError("%s: expected a contiguous %s tensor of shape (%s, %d)" % (name, str(dtype).replace("torch.", ""), "n" if rows is None else rows, cols))
+        dtypes = dtype if isinstance(dtype, tuple) else (dtype or torch.float32,)
+        shape = (lambda: t.dim() == 1) if cols is None else (lambda: t.dim() == 2 and t.shape[1] == cols)
+        if not hasattr(t, "data_ptr") or t.dtype not in dtypes or not t.is_contiguous() or not shape() or (isinstance(rows, int) and t.shape[0] != rows):
+            raise ValueError("%s: expected a contiguous %s tensor of shape (%s%s" % (name, " or ".join(str(d).replace("torch.", "") for d in dtypes),
+                                                                                      "n" if rows is None else rows, ",)" if cols is None else ", %d)" % cols))
         if not t.is_cuda or (t.device.index or 0) != self.device:
             raise ValueError("%s: the tensor is not on the scene's device" % name)
         return t
@@ -186,12 +187,9 @@ class Scene:
         ev = torch.empty((n, 4), dtype=torch.float32, device=rays.device) if wo is not None else None
         sampled = torch.empty((n, 12), dtype=torch.float32, device=rays.device) if samples is not None else None
         wi = torch.empty((n, 4), dtype=torch.float32, device=rays.device) if wi_local else None
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        d = A.phip_bsdf_desc(d_rays=ptr(rays), d_hits=ptr(hits), n=n, d_wo=ptr(wo), d_samples=ptr(samples), d_eval=ptr(ev), d_sampled=ptr(sampled), d_wi_local=ptr(wi),
-                             flags=A.PHIP_BSDF_LOCAL if local else 0, reserved=0, stream=getattr(stream, "cuda_stream", stream))
-        rc = self._L.phip_bsdf_device(self._h, C.byref(d))
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_bsdf_device")
+        d = A.phip_bsdf_desc(d_rays=_ptr(rays), d_hits=_ptr(hits), n=n, d_wo=_ptr(wo), d_samples=_ptr(samples), d_eval=_ptr(ev), d_sampled=_ptr(sampled), d_wi_local=_ptr(wi),
+                             flags=A.PHIP_BSDF_LOCAL if local else 0, reserved=0, stream=_stream_handle(stream))
+        _check(self._L.phip_bsdf_device(self._h, C.byref(d)), "phip_bsdf_device")
         return ev, sampled, wi
 
     def emitter_sample(self, ref, ref_n, samples, shadow_rays=False, stream=None):
@@ -206,12 +204,9 @@ class Scene:
         samples = self._device_tensor(samples, "samples", 2, rows=n)
         sampled = torch.empty((n, 12), dtype=torch.float32, device=ref.device)
         rays = torch.empty((n, 8), dtype=torch.float32, device=ref.device) if shadow_rays else None
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        d = A.phip_emitter_sample_desc(d_ref=ptr(ref), d_ref_n=ptr(ref_n), d_samples=ptr(samples), n=n, d_sampled=ptr(sampled), d_shadow_rays=ptr(rays),
-                                       stream=getattr(stream, "cuda_stream", stream))
-        rc = self._L.phip_emitter_sample_device(self._h, C.byref(d))
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_emitter_sample_device")
+        d = A.phip_emitter_sample_desc(d_ref=_ptr(ref), d_ref_n=_ptr(ref_n), d_samples=_ptr(samples), n=n, d_sampled=_ptr(sampled), d_shadow_rays=_ptr(rays),
+                                       stream=_stream_handle(stream))
+        _check(self._L.phip_emitter_sample_device(self._h, C.byref(d)), "phip_emitter_sample_device")
         return sampled, rays
 
     def emitter_eval(self, rays, hits, ref_n=None, emitter=False, stream=None):
@@ -225,19 +220,14 @@ class Scene:
         ref_n = self._device_tensor(ref_n, "ref_n", 4, rows=n, optional=True)
         ev = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
         em = torch.empty((n,), dtype=torch.int32, device=rays.device) if emitter else None
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        d = A.phip_emitter_eval_desc(d_rays=ptr(rays), d_hits=ptr(hits), d_ref_n=ptr(ref_n), n=n, d_eval=ptr(ev), d_emitter=ptr(em), stream=getattr(stream, "cuda_stream", stream))
-        rc = self._L.phip_emitter_eval_device(self._h, C.byref(d))
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_emitter_eval_device")
+        d = A.phip_emitter_eval_desc(d_rays=_ptr(rays), d_hits=_ptr(hits), d_ref_n=_ptr(ref_n), n=n, d_eval=_ptr(ev), d_emitter=_ptr(em), stream=_stream_handle(stream))
+        _check(self._L.phip_emitter_eval_device(self._h, C.byref(d)), "phip_emitter_eval_device")
         return ev, em
 
     def replicate(self, devices):
         """Copies the device scene to further GPUs ahead of a multi-device render (phip_scene_replicate)."""
         arr = (C.c_int32 * len(devices))(*devices)
-        rc = self._L.phip_scene_replicate(self._h, arr, len(devices))
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_scene_replicate")
+        _check(self._L.phip_scene_replicate(self._h, arr, len(devices)), "phip_scene_replicate")
 
     def update(self, positions=None, normals=None, camera=None, stream=None):
         """New vertex positions / normals / camera on the scene as created: a refit of the acceleration structure, not a rebuild (phip_scene_update).
@@ -278,13 +268,11 @@ class Scene:
             raise ValueError("positions and normals must both be host arrays or both be device tensors")
         u.device_pointers = 1 if on_device and on_device[0] else 0
         if stream is not None:
-            u.stream = getattr(stream, "cuda_stream", stream)
+            u.stream = _stream_handle(stream)
         if camera is not None:
             u.camera = C.pointer(camera)
         info = A.phip_update_info()
-        rc = getattr(self._L, entry)(self._h, C.byref(u), C.byref(info))
-        if rc != 0:
-            raise _ffi.PhipError(rc, entry)
+        _check(getattr(self._L, entry)(self._h, C.byref(u), C.byref(info)), entry)
         if camera is not None:
             self.desc.camera = camera
         return info
@@ -361,19 +349,16 @@ class Scene:
             raise ValueError("texel arrays must all be host arrays or all be device tensors")
         a.device_pointers = 1 if on_device and on_device[0] else 0
         if stream is not None:
-            a.stream = getattr(stream, "cuda_stream", stream)
+            a.stream = _stream_handle(stream)
         info = A.phip_appearance_info()
         rc = self._L.phip_scene_update_appearance(self._h, C.byref(a), C.byref(info))
         del keep                                                  # (held until the call has returned)
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_scene_update_appearance")
+        _check(rc, "phip_scene_update_appearance")
         return info.as_dict()
 
     def film_to_host(self, d_ptr, host_ptr):
         """a device-resident frame (render_device's output, e.g. after an RCCL reduce) to host memory, as phip_render delivers it"""
-        rc = self._L.phip_film_to_host(self._h, C.c_void_p(d_ptr), C.c_void_p(host_ptr))
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_film_to_host")
+        _check(self._L.phip_film_to_host(self._h, C.c_void_p(d_ptr), C.c_void_p(host_ptr)), "phip_film_to_host")
 
     def close(self):
         if getattr(self, "_h", None):
@@ -467,8 +452,7 @@ class PathHIP:
         self.stats = st
         if rc == A.PHIP_ERR_CANCELLED:
             return False
-        if rc != 0:
-            raise _ffi.PhipError(rc, entry)
+        _check(rc, entry)
         return True
 
     def render(self, scene, film, spp, seed=0, shard_index=0, shard_count=1, flags=0, **extra):
@@ -499,10 +483,7 @@ class PathHIP:
         `stream` is the stream the rays' producer ran on (a torch.cuda.Stream or a raw handle).  The call's statistics are kept in self.stats.
         ValueError for a tensor of another dtype, layout or device; PhipError for what the library refuses; None if the call was cancelled."""
         import torch
-        if not hasattr(rays, "data_ptr") or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
-            raise ValueError("rays: expected a contiguous float32 tensor of shape (n, 8)")
-        if not rays.is_cuda or (rays.device.index or 0) != scene.device:
-            raise ValueError("rays: the tensor is not on the scene's device")
+        rays = Scene._device_tensor(scene, rays, "rays", 8)
         n = rays.shape[0]
         if stream_ids is not None:
             if not hasattr(stream_ids, "data_ptr") or stream_ids.dtype not in (torch.int32, torch.uint32) or not stream_ids.is_contiguous() or tuple(stream_ids.shape) != (n,):
@@ -518,7 +499,7 @@ class PathHIP:
                 raise ValueError("pairs: the tensor is not on the rays' device")
             stream_ids = pairs
         out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
-        p = self.params(scene, spp, seed, flags=flags, stream=getattr(stream, "cuda_stream", stream), **extra)
+        p = self.params(scene, spp, seed, flags=flags, stream=_stream_handle(stream), **extra)
         d = A.phip_radiance_desc(d_rays=rays.data_ptr() if n else None, n=n, d_stream=stream_ids.data_ptr() if stream_ids is not None and n else None,
                                  first_stream=first_stream, reserved=A.PHIP_RADIANCE_STREAM_PAIRS if pairs is not None else 0, d_out=out.data_ptr() if n else None)
         return out if self._call("phip_radiance_device", scene, p, C.byref(d)) else None
@@ -526,9 +507,7 @@ class PathHIP:
     def samples(self, scene, spp):
         """Per-sample (R,G,B,alpha) of the last render made with PHIP_FLAG_SAMPLE_BUFFER: [y][x][sample]."""
         out = np.zeros((scene.height, scene.width, spp, 4), np.float32)
-        rc = _ffi.lib().phip_get_samples(scene._h, _ffi.fptr(out), scene.height * scene.width * spp)
-        if rc != 0:
-            raise _ffi.PhipError(rc, "phip_get_samples")
+        _check(_ffi.lib().phip_get_samples(scene._h, _ffi.fptr(out), scene.height * scene.width * spp), "phip_get_samples")
         return out
 
     def cancel(self):
