@@ -676,6 +676,30 @@ typedef struct phip_appearance_info {
 } phip_appearance_info;
 int phip_scene_update_appearance(phip_scene *scene, const phip_appearance_desc *desc, phip_appearance_info *out_info /* may be NULL */);
 
+/* The MIP pyramid of a texture or an environment map exactly as the reference's TMIPMap builds and stores it (mipmap.h:181-270: a two-lobe Lanczos Resampler per
+   axis, X then Y, every level made from the float32 level before it, clamped to [0, max_value] after each pass, negative channels of level 0 set to 0; every level
+   stored in half precision), from a level 0 in DEVICE memory into caller-allocated levels in device memory -- what phip_texture.levels[] / phip_envmap.levels[]
+   and, with device_pointers = 1, phip_appearance_desc take.  The scene gives the device and the stream (and owns the scratch: the call takes the render lock); it is
+   not changed.  The bits are those of the host call phip_mip_pyramid below, and the reference's own.  Complete on return.
+   Refusals, PHIP_ERR_INVALID, all before anything is written: a NULL scene or desc, a zero size, a size of 65536 or more (the creation's limit), an n_levels that is
+   not the pyramid's own count (sizes halve with max(1, (n + 1) / 2) down to 1 x 1), a bad wrap mode, a max_value that is not > 0 (NaN included), a missing level
+   pointer, a pointer that is not 4-byte aligned, levels that overlap (but for d_levels[0] == d_level0), a pointer that is not device memory of the scene's device.
+   PHIP_ERR_DEVICE without a GPU. */
+typedef struct phip_pyramid_desc {
+    uint32_t width, height;        /* of level 0 */
+    uint32_t n_levels;             /* the complete count */
+    uint32_t wrap_u, wrap_v;       /* phip_wrap_mode per axis: what a tap outside the image reads (an environment map: repeat, clamp) */
+    float    max_value;            /* 1 for a bitmap texture, +infinity for an environment map */
+    const float *d_level0;         /* height x width x 3 floats (RGB), tight: the layout of phip_texture.levels[] */
+    float *d_levels[PHIP_MIP_MAX_LEVELS];   /* d_levels[l], 1 <= l < n_levels: the output levels, caller-allocated, tight RGB floats.  d_levels[0]: NULL (level 0 is
+                                      not written), d_level0 itself (rounded in place) or memory of its own */
+    void *stream;                  /* the hipStream_t the producer of d_level0 ran on, or NULL; the call is ordered after it */
+} phip_pyramid_desc;
+int phip_mip_pyramid_device(phip_scene *scene, const phip_pyramid_desc *desc);
+/* The same pyramid on HOST memory, without a device: every pointer of the descriptor is host memory, `stream` is ignored.  The same statements run (pyramid_hd.h), so
+   the levels are the device call's bit for bit; the refusals are the same but for the device's. */
+int phip_mip_pyramid(const phip_pyramid_desc *desc);
+
 /* Thread-safe and sticky, like Scheduler::cancel on a process (src/libcore/sched.cpp): a running phip_render returns
    PHIP_ERR_CANCELLED; a request that arrives before the render starts cancels that render.  The flag is consumed by the
    call that observes it. */
@@ -706,7 +730,7 @@ int  phip_scene_accel_info(const phip_scene *scene, phip_accel_info *out);
 /* Utilities for callers that fill a phip_scene_desc without Mitsuba at hand (the test harness, bench.py): the table of the reference's default `gaussian` reconstruction
  * filter with the given standard deviation -- (radius, PHIP_FILTER_RESOLUTION + 1 values), rfilter.cpp:38-57 + gaussian.cpp:34-57; the Mitsuba shim copies the scene's own
  * filter instead -- and sizeof of the ABI's structs by index (0 phip_material, 1 phip_shape, 2 phip_emitter, 3 phip_camera, 4 phip_film, 5 phip_scene_desc,
- * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info, 11 phip_update_desc, 12 phip_update_info, 13 phip_surface, 15 phip_radiance_desc; 14 is unassigned and answers 0: tests/test_raycast_device_host.py pins phip_abi_sizeof(14) == 0 as "one past the last struct" and stays as it is, so the new struct skips that index; 16 is unassigned likewise: tests/test_radiance_device_host.py pins it; 17 phip_camera_rays_desc, 18 phip_film_desc; 19 is unassigned likewise: tests/test_camera_film_host.py pins it; 20 phip_appearance_desc, 21 phip_appearance_info; 22 is unassigned likewise: tests/test_appearance_host.py pins it; 23 phip_bsdf_desc, 24 phip_bsdf_sample, 25 phip_emitter_sample_desc, 26 phip_emitter_sample, 27 phip_emitter_eval_desc), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
+ * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info, 11 phip_update_desc, 12 phip_update_info, 13 phip_surface, 15 phip_radiance_desc; 14 is unassigned and answers 0: tests/test_raycast_device_host.py pins phip_abi_sizeof(14) == 0 as "one past the last struct" and stays as it is, so the new struct skips that index; 16 is unassigned likewise: tests/test_radiance_device_host.py pins it; 17 phip_camera_rays_desc, 18 phip_film_desc; 19 is unassigned likewise: tests/test_camera_film_host.py pins it; 20 phip_appearance_desc, 21 phip_appearance_info; 22 is unassigned likewise: tests/test_appearance_host.py pins it; 23 phip_bsdf_desc, 24 phip_bsdf_sample, 25 phip_emitter_sample_desc, 26 phip_emitter_sample, 27 phip_emitter_eval_desc; 28 is unassigned likewise: tests/test_shading_parts_host.py pins it; 29 phip_pyramid_desc), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
 void   phip_gaussian_filter(float stddev, float *radius, float *table);
 size_t phip_abi_sizeof(int which);
 

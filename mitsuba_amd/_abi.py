@@ -232,6 +232,11 @@ class phip_emitter_eval_desc(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+class phip_pyramid_desc(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_levels", C.c_uint32), ("wrap_u", C.c_uint32), ("wrap_v", C.c_uint32),
+                ("max_value", C.c_float), ("d_level0", C.c_void_p), ("d_levels", C.c_void_p * PHIP_MIP_MAX_LEVELS), ("stream", C.c_void_p)]
+
+
 def default_render_params(**kw):
     """MonteCarloIntegrator defaults (src/librender/integrator.cpp:190-225)."""
     p = phip_render_params()

@@ -59,6 +59,8 @@ UNITS += [("phip_camera_film.hip", [], "phip_camera_film.o")]
 UNITS += [("phip_appearance.hip", [], "phip_appearance.o")]
 # phip_shading_parts.hip (the kernels of phip_bsdf_device, phip_emitter_sample_device and phip_emitter_eval_device, k_shading_parts.h): one object, inserted likewise
 UNITS += [("phip_shading_parts.hip", [], "phip_shading_parts.o")]
+# phip_pyramid.hip (the kernels of phip_mip_pyramid_device, k_pyramid.h): one small object, inserted likewise
+UNITS += [("phip_pyramid.hip", [], "phip_pyramid.o")]
 # phip_update.hip (the refit kernels of phip_scene_update, k_update.h): one small object, appended likewise
 UNITS += [("phip_update.hip", [], "phip_update.o")]
 # phip_rebuild.hip (the device build of phip_scene_rebuild, k_rebuild.h, with rocPRIM's sort and scan): one object, appended likewise
@@ -146,7 +148,7 @@ def _build_locked(sid, out_lib, verbose):
             return 13.0
         if name.startswith("phip_raycast"):
             return 5.0
-        if name.startswith("phip_camera_film") or name.startswith("phip_appearance"):
+        if name.startswith("phip_camera_film") or name.startswith("phip_appearance") or name.startswith("phip_pyramid"):
             return 3.0
         if name.startswith("phip_shading_parts"):
             return 12.0
@@ -186,10 +188,12 @@ def _build_locked(sid, out_lib, verbose):
 TEST_VARIANTS = {"fault": "-DMEGA_MB_FAULT=1",       # waves of fused launches report that they gave up (by default the first wave of every launch; PHIP_TEST_FAULT_* in phip.hip
                                                      # choose others): the frame must come from the re-rendered pass
                  "cap32": "-DWP_CAP=32u",            # 32-entry task stacks: nearly every push of a big scene spills to memory
-                 "overflow": "-DWP_CAP=64u -DWP_SPILL_CAP=64u"}      # 128-entry task stacks, half of them spilled: the tree-in-memory scenes outgrow them -- the wave stops, the pass is re-rendered
+                 "overflow": "-DWP_CAP=64u -DWP_SPILL_CAP=64u",      # 128-entry task stacks, half of them spilled: the tree-in-memory scenes outgrow them -- the wave stops, the pass is re-rendered
+                 "notail": "-DPYRAMID_TAIL=0"}       # not a test's: tools/gpu_pyramid.py measures phip_mip_pyramid_device without its single-block tail kernel (host_pyramid.h)
 # sources whose objects a variant takes from the product build: its flags do not concern them (the task stacks are k_mega's and k_shade_trace_w's)
-VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip", "cap32": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip",
-                 "overflow": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip"}
+VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip phip_pyramid.hip", "cap32": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip phip_pyramid.hip",
+                 "overflow": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip phip_pyramid.hip",
+                 "notail": "phip_shade.hip phip_shade_w.hip phip_mega.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip phip_pyramid.hip"}
 
 
 def build_test_variant(tag):
@@ -243,6 +247,8 @@ def lib():
     L.phip_scene_update.argtypes = [C.c_void_p, C.POINTER(A.phip_update_desc), C.POINTER(A.phip_update_info)]
     L.phip_scene_rebuild.argtypes = [C.c_void_p, C.POINTER(A.phip_update_desc), C.POINTER(A.phip_update_info)]
     L.phip_scene_update_appearance.argtypes = [C.c_void_p, C.POINTER(A.phip_appearance_desc), C.POINTER(A.phip_appearance_info)]
+    L.phip_mip_pyramid_device.argtypes = [C.c_void_p, C.POINTER(A.phip_pyramid_desc)]
+    L.phip_mip_pyramid.argtypes = [C.POINTER(A.phip_pyramid_desc)]
     L.phip_develop.argtypes = [fp, C.c_size_t, fp]
     L.phip_scene_accel_info.argtypes = [C.c_void_p, C.POINTER(A.phip_accel_info)]
     L.phip_gaussian_filter.argtypes = [C.c_float, fp, fp]
@@ -306,6 +312,7 @@ def debug_lib():
     L.phip_debug_host_bsdf_args.argtypes = [C.c_int, C.POINTER(A.phip_bsdf_desc)]
     L.phip_debug_host_emitter_sample_args.argtypes = [C.c_int, C.POINTER(A.phip_emitter_sample_desc)]
     L.phip_debug_host_emitter_eval_args.argtypes = [C.c_int, C.POINTER(A.phip_emitter_eval_desc)]
+    L.phip_debug_host_pyramid_args.argtypes = [C.c_int, C.POINTER(A.phip_pyramid_desc)]
     L.phip_debug_host_bsdf_parts.argtypes = [C.POINTER(A.phip_scene_desc), C.POINTER(A.phip_bsdf_desc)]
     L.phip_debug_host_emitter_sample.argtypes = [C.POINTER(A.phip_scene_desc), C.POINTER(A.phip_emitter_sample_desc)]
     L.phip_debug_host_emitter_eval.argtypes = [C.POINTER(A.phip_scene_desc), C.POINTER(A.phip_emitter_eval_desc)]

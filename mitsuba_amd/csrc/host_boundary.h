@@ -1,7 +1,7 @@
 /*
  * host_boundary.h -- what a call on the caller's device memory needs, stated once: whose memory a pointer is, how it is aligned, how many items one call takes,
  * the stream its work is ordered on, the device its parameters name, a device's CU count, one block per BLOCK items, a refusal under its call's name.
- * The per-call headers (host_raycast.h, host_radiance.h, host_camera_film.h, host_shading_parts.h, host_update.h, host_appearance.h) and host_render.h use these
+ * The per-call headers (host_raycast.h, host_radiance.h, host_camera_film.h, host_shading_parts.h, host_pyramid.h, host_update.h, host_appearance.h) and host_render.h use these
  * and keep the texts of their own refusals; the guard that brings an entry point to its body is phip.hip's (onDevice).
  * Host code only; included by phip.hip alone, after host_scene.h.
  */
@@ -23,6 +23,11 @@ static bool onSceneDevice(const void *p, int device) {
 static bool allOnSceneDevice(const SceneDev &sd, std::initializer_list<const void *> ptrs) {
     for (const void *p : ptrs)
         if (p && !onSceneDevice(p, sd.device)) return false;
+    return true;
+}
+static bool allOnSceneDevice(const SceneDev &sd, const void *const *ptrs, size_t n) {          /* (an array of them: the levels of phip_mip_pyramid_device) */
+    for (size_t i = 0; i < n; ++i)
+        if (ptrs[i] && !onSceneDevice(ptrs[i], sd.device)) return false;
     return true;
 }
 

@@ -142,6 +142,7 @@ struct SceneDev {
        a call that takes several passes, two double2 per ray -- the one buffer of that call that grows with its ray count */
     struct RadiancePlan { ShadeRaysKernel vertex[2] = { nullptr, nullptr }; RadianceOutKernel out = nullptr; } radiance;
     DevBuf<double2> radianceAcc;
+    DevBuf<float> pyramidScratch;                                                           /* phip_mip_pyramid_device (host_pyramid.h): the float32 chain and the X-pass temporary; grow-only */
     DevBuf<float> film, patchImg;                                                           /* patchImg: k_film_splat's 16 x 16 patch images (k_film.h) */
     uint32_t lastSpp = 0, nLocalTiles = 0; unsigned long long localPixels = 0;
     int tileKey[3] = { -1, -1, -1 };

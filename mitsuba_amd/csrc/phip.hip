@@ -15,7 +15,7 @@
  *       iteration that shades a slot's vertex and traces its shadow ray and its next ray on the packed leaf table in LDS (k_shade_trace.h); scenes of that
  *       kind whose tree lives in L2: k_shade_trace_w, the same iteration on the 8-wide tree in memory (k_shade_trace_w.h)
  *
- * libphip.so is 48 objects of eleven sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
+ * libphip.so is 49 objects of twelve sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
  * at plan time (host_render.h -- shadeUnit: the one table over the feature sets; megaKernelOf -> FusedPlan::kernel in planFused, shadeKernelOf / shadeTraceWideKernelOf ->
  * WavefrontPlan::vertex / vertexWide in selectVertexKernel), asks the runtime for the residency of the persistent ones (residentBlocksPerCU) and launches them.
  * Kernels and where they live:
@@ -39,6 +39,8 @@
  *   k_rebuild.h   the new topology of phip_scene_rebuild: Morton keys, the binary radix tree, its collapse to the 8-wide layout level by level      [phip_rebuild.hip]
  *   k_appearance.h  phip_scene_update_appearance: the texel maximum and conversion, the environment map's CDFs, the material words of the shading records, the shade
  *                 classes of the Wald records (appearance_hd.h: the arithmetic the creation shares)                                                          [phip_appearance.hip]
+ *   k_pyramid.h   phip_mip_pyramid_device: level 0 into the float32 chain, one pass of one resampling step, the pyramid's tail in one block's LDS (pyramid_hd.h: the
+ *                 statements the host call phip_mip_pyramid runs too)                                                                                 [phip_pyramid.hip]
  *   k_raycast.h   phip_trace_device: k_raycast_p (k_wide.h's persistent loop on a caller's ray array), k_surfaces (the record at every hit)            [phip_raycast.hip]
  *   k_shade_r.h   phip_radiance_device: k_shade_r (k_shade with a caller's ray array as its source of samples), k_radiance_out (the mean of a ray's samples)  [phip_shade_r.hip]
  *   k_camera_film.h  phip_camera_rays_device / phip_film_device: k_camera_rays (the camera samples of the counter stream), k_film_values (k_film's gather on a
@@ -65,7 +67,8 @@
  *   host_camera_film.h phip_camera_rays_device and phip_film_device: the camera samples out, per-sample values onto a film (k_camera_film.h in phip_camera_film.hip)
  *   host_shading_parts.h phip_bsdf_device, phip_emitter_sample_device and phip_emitter_eval_device: the BSDF at the hits of a ray cast, emitter sampling and emitter
  *                  evaluation on the caller's arrays (k_shading_parts.h in phip_shading_parts.hip)
- * Each of the last four holds its call's checks of the arguments that need no device (`*ArgsError`, `*Refusal`: all of them come before any launch) and its body.
+ *   host_pyramid.h phip_mip_pyramid_device and phip_mip_pyramid: the reference's MIP pyramid from a level 0 in device / host memory (k_pyramid.h in phip_pyramid.hip)
+ * Each of the last five holds its call's checks of the arguments that need no device (`*ArgsError`, `*Refusal`: all of them come before any launch) and its body.
  * Not MFMA work: irregular traversal and gathers.  The product never includes, links or calls anything under oracle/.
  */
 #include "phip_common.h"
@@ -105,6 +108,7 @@ static int setErr(int code, const std::string &msg) { g_err = msg; return code; 
 #include "host_radiance.h"
 #include "host_camera_film.h"
 #include "host_shading_parts.h"
+#include "host_pyramid.h"
 
 /* Entry of both render functions: validation, the scene's render lock, single- or multi-device dispatch, the sticky
    cancellation flag (consumed by the call that observed it). */
@@ -448,6 +452,11 @@ int phip_emitter_eval_device(phip_scene *scene, const phip_emitter_eval_desc *de
     return onDevice(DEVICE_ERRORS, scene, "phip_emitter_eval_device", [&] { return emitterEvalDevice(scene, desc); });
 }
 
+int phip_mip_pyramid_device(phip_scene *scene, const phip_pyramid_desc *desc) {
+    if (const int rc = pyramidDeviceRefusal(scene != nullptr, desc)) return rc;
+    return onDevice(DEVICE_ERRORS, scene, "phip_mip_pyramid_device", [&] { return mipPyramidDevice(scene, desc); });
+}
+
 void phip_cancel(phip_scene *scene) { if (scene && scene->cancelFlag) __atomic_store_n(scene->cancelFlag, 1, __ATOMIC_RELAXED); }
 
 void phip_develop(const float *rgbaw, size_t n_pixels, float *out_rgb) {
@@ -488,6 +497,12 @@ void phip_gaussian_filter(float stddev, float *radius, float *table32) {
     *radius = r;
 }
 
+/* TMIPMap's pyramid on host memory (host_pyramid.h, pyramid_hd.h): the twin of phip_mip_pyramid_device's kernels */
+int phip_mip_pyramid(const phip_pyramid_desc *desc) {
+    if (const int rc = pyramidHostRefusal(desc)) return rc;
+    return guarded(DEVICE_ERRORS, [&]() -> int { mipPyramidHost(desc); return PHIP_OK; });
+}
+
 size_t phip_abi_sizeof(int which) {
     switch (which) {
         case 0: return sizeof(phip_material);
@@ -514,6 +529,7 @@ size_t phip_abi_sizeof(int which) {
         case 25: return sizeof(phip_emitter_sample_desc);
         case 26: return sizeof(phip_emitter_sample);
         case 27: return sizeof(phip_emitter_eval_desc);
+        case 29: return sizeof(phip_pyramid_desc);       /* (28 likewise) */
         default: return 0;
     }
 }

@@ -2,7 +2,7 @@
  * phip_common.h -- what every translation unit of libphip.so starts with: HIP, the C ABI, the device scene layout and
  * shading functions (dv_scene.h), the path-pool layout (k_pool.h), the error macro.
  *
- * libphip.so is built from eleven sources (48 objects) so that they compile in parallel:
+ * libphip.so is built from twelve sources (49 objects) so that they compile in parallel:
  *   phip.hip          the C ABI + traversal and film kernels, with the host side it includes by concern: host_scene.h (scene build, replicas), host_boundary.h (what
  *                     a call on the caller's device memory needs), host_render.h (kernel selection, one device's render loop), host_multi.h (multi-device
  *                     orchestration, RCCL) and one header per entry point on the caller's device memory: 1 object
@@ -20,6 +20,7 @@
  *   phip_appearance.hip   the kernels of phip_scene_update_appearance (k_appearance.h) behind phipAppearanceKernels: 1 object
  *   phip_shading_parts.hip  the kernels of phip_bsdf_device, phip_emitter_sample_device and phip_emitter_eval_device (k_shading_parts.h) behind
  *                     phipShadingPartsKernels: 1 object
+ *   phip_pyramid.hip  the kernels of phip_mip_pyramid_device (k_pyramid.h) behind phipPyramidKernels: 1 object
  * The other units hold kernels and the look-ups that return them, nothing else: every launch and every query of the runtime is in phip.hip and its host headers
  * (but for the launches inside rocPRIM's sort and scan, which phip_rebuild.hip wraps).
  * No device function is called across units (everything on the device side is inline in headers), so no -fgpu-rdc.
@@ -138,3 +139,13 @@ struct ShadingPartsKernels {
     void (*emitterEval[2])(DevScene, const float4 *, const float4 *, const float4 *, uint32_t, float4 *, int32_t *);
 };
 ShadingPartsKernels phipShadingPartsKernels();
+/* the kernels of phip_mip_pyramid_device (phip_pyramid.hip, k_pyramid.h; PyramidOuts: pyramid_hd.h).  level0: (level 0, texels, chain out, rounded out);
+   pass: (source, source width, source height, float32 out, rounded out, axis, wrap mode, max value); tail: (float32 level, width, height, its index, the caller's
+   levels, wrap u, wrap v, max value) */
+struct PyramidOuts;
+struct PyramidKernels {
+    void (*level0)(const float *, size_t, float *, float *);
+    void (*pass)(const float *, int, int, float *, float *, int, uint32_t, float);
+    void (*tail)(const float *, int, int, int, PyramidOuts, uint32_t, uint32_t, float);
+};
+PyramidKernels phipPyramidKernels();

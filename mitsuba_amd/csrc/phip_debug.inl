@@ -720,6 +720,11 @@ extern "C" int phip_debug_host_emitter_eval_args(int have_scene, const phip_emit
     return emitterEvalRefusal(have_scene != 0, desc);
 }
 
+/* phip_mip_pyramid_device's checks of the arguments (host_pyramid.h) likewise: everything but whose memory the pointers are */
+extern "C" int phip_debug_host_pyramid_args(int have_scene, const phip_pyramid_desc *desc) {
+    return pyramidDeviceRefusal(have_scene != 0, desc);
+}
+
 /* The DevScene of a descriptor on the host: the stages phip_scene_create runs before it uploads (none of them calls HIP) -- shapes, textures, materials, emitters,
    the tree (for the scene box the environment emitter's sphere is made of), shading records, the emitter table, the environment map's tables -- with the
    DevScene's pointers bound to the builder's arrays instead of device buffers.  What the items of k_shading_parts.h read of a scene is all there. */

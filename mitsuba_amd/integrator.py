@@ -277,6 +277,48 @@ class Scene:
             self.desc.camera = camera
         return info
 
+    def mip_pyramid(self, level0, wrap_u="repeat", wrap_v=None, max_value=1.0, out=None, stream=None):
+        """The MIP pyramid of a texture or an environment map as the reference's TMIPMap builds and stores it, on the scene's device (phip_mip_pyramid_device; the
+        host call of the same bits: scene.mip_pyramid_lanczos).  level0: a contiguous (h, w, 3) float32 tensor on the scene's device.  wrap_u / wrap_v: "clamp",
+        "repeat", "mirror", "zero", "one" or the PHIP_WRAP_* value (wrap_v defaults to wrap_u); max_value: 1 for a texture, infinity for an environment map
+        (which takes repeat x clamp).  out: None, or one tensor per level to write into -- out[0] may be None (level 0 is not written) or level0 itself (rounded in
+        place); without `out` every level is allocated, level 0 included.  stream: the stream level0's producer ran on.  Returns the list of levels, level 0
+        first (None where out[0] was None): what update_appearance takes as "levels"."""
+        import torch
+        from .scene import WRAP_MODES, pyramid_sizes
+        if not hasattr(level0, "data_ptr") or level0.dim() != 3 or level0.shape[2] != 3 or not level0.is_contiguous():
+            raise ValueError("level0: expected a contiguous float32 tensor of shape (h, w, 3)")
+        level0 = self._device_tensor(level0.view(-1), "level0").view(level0.shape)
+        sizes = pyramid_sizes(level0.shape[1], level0.shape[0])
+        if out is None:
+            out = [torch.empty((h, w, 3), dtype=torch.float32, device=level0.device) for h, w in sizes]
+        if len(out) != len(sizes):
+            raise ValueError("out: expected %d levels" % len(sizes))
+        p = A.phip_pyramid_desc()
+        p.width, p.height, p.n_levels = level0.shape[1], level0.shape[0], len(sizes)
+        p.wrap_u = WRAP_MODES.get(wrap_u, wrap_u)
+        p.wrap_v = p.wrap_u if wrap_v is None else WRAP_MODES.get(wrap_v, wrap_v)
+        p.max_value = max_value
+        p.d_level0 = _ptr(level0)
+        for l, ((h, w), o) in enumerate(zip(sizes, out)):
+            if o is None and l == 0:
+                continue
+            if o is None or o.numel() != 3 * h * w:
+                raise ValueError("out[%d]: expected %d x %d x 3 values" % (l, h, w))
+            p.d_levels[l] = _ptr(self._device_tensor(o.view(-1), "out[%d]" % l))
+        p.stream = _stream_handle(stream)
+        _check(self._L.phip_mip_pyramid_device(self._h, C.byref(p)), "phip_mip_pyramid_device")
+        return list(out)
+
+    def _levels_of(self, entry, n_levels, wrap_u, wrap_v, max_value, stream):
+        """the "levels" of a texture or envmap dict of update_appearance: as given, or built from its "image" -- a device tensor on the device, an array on the host"""
+        if "image" not in entry:
+            return entry["levels"]
+        from .scene import mip_pyramid_lanczos
+        image = entry["image"]
+        levels = self.mip_pyramid(image, wrap_u, wrap_v, max_value, stream=stream) if hasattr(image, "data_ptr") else mip_pyramid_lanczos(image, wrap_u, wrap_v, max_value)
+        return levels[:max(1, n_levels)]
+
     def update_appearance(self, materials=None, emitters=None, textures=None, envmap=None, stream=None):
         """New materials, emitter radiances / sampling weights, texture contents and / or a new environment map on the scene as created, in place
         (phip_scene_update_appearance): afterwards the scene is the one a fresh creation with this look would have given.
@@ -284,6 +326,9 @@ class Scene:
         textures: one entry per texture of the scene -- None leaves it alone; else a dict as SceneBuilder keeps it: "levels" (the pyramid, (h, w, 3) float32 each,
         sizes as created) and optionally "wrap_u", "wrap_v", "filter", "aniso", "scale", "offset" (default: the creation's).
         envmap: a dict with "levels" (level 0 first), and optionally "scale" and "to_world" (4 x 4; default: the creation's).
+        In place of "levels" a texture or envmap dict may carry "image", level 0 alone: the levels the scene was created with are then built as the reference
+        builds them (mip_pyramid on the device for a tensor, scene.mip_pyramid_lanczos for an array) -- a texture with its own wrap modes and the bound 1, the
+        environment map with repeat x clamp and no bound -- and passed on; a tensor never leaves the device.
         Texel arrays are numpy arrays (host memory) or contiguous float32 torch tensors on the scene's device, read in place (`stream`: the stream their producer
         ran on); a mix of both is refused.  Returns the phip_appearance_info as a dict; PhipError on a refusal, the scene unchanged."""
         d = self.desc
@@ -326,9 +371,10 @@ class Scene:
                 if t is None or i >= d.n_textures:
                     continue                                      # width 0: this texture stays (a wrong count is the library's to refuse)
                 old = d.textures[i]
-                arr[i].width, arr[i].height, arr[i].n_levels = old.width, old.height, len(t["levels"])
-                for l, (h, w) in enumerate(level_sizes(old.width, old.height, min(len(t["levels"]), A.PHIP_MIP_MAX_LEVELS))):
-                    arr[i].levels[l] = texels(t["levels"][l], h, w, "textures[%d] level %d" % (i, l))
+                levels = self._levels_of(t, old.n_levels, t.get("wrap_u", old.wrap_u), t.get("wrap_v", old.wrap_v), 1.0, stream)
+                arr[i].width, arr[i].height, arr[i].n_levels = old.width, old.height, len(levels)
+                for l, (h, w) in enumerate(level_sizes(old.width, old.height, min(len(levels), A.PHIP_MIP_MAX_LEVELS))):
+                    arr[i].levels[l] = texels(levels[l], h, w, "textures[%d] level %d" % (i, l))
                 arr[i].wrap_u, arr[i].wrap_v = t.get("wrap_u", old.wrap_u), t.get("wrap_v", old.wrap_v)
                 arr[i].filter_type, arr[i].max_anisotropy = t.get("filter", old.filter_type), t.get("aniso", old.max_anisotropy)
                 arr[i].uv_scale[:] = t.get("scale", tuple(old.uv_scale)); arr[i].uv_offset[:] = t.get("offset", tuple(old.uv_offset))
@@ -337,9 +383,10 @@ class Scene:
         if envmap is not None:
             e = A.phip_envmap()
             old = d.envmap
-            e.width, e.height, e.n_levels = old.width, old.height, len(envmap["levels"])
-            for l, (h, w) in enumerate(level_sizes(old.width, old.height, min(len(envmap["levels"]), A.PHIP_ENVMAP_MAX_LEVELS))):
-                e.levels[l] = texels(envmap["levels"][l], h, w, "envmap level %d" % l)
+            levels = self._levels_of(envmap, old.n_levels, A.PHIP_WRAP_REPEAT, A.PHIP_WRAP_CLAMP, float("inf"), stream)
+            e.width, e.height, e.n_levels = old.width, old.height, len(levels)
+            for l, (h, w) in enumerate(level_sizes(old.width, old.height, min(len(levels), A.PHIP_ENVMAP_MAX_LEVELS))):
+                e.levels[l] = texels(levels[l], h, w, "envmap level %d" % l)
             e.texels = e.levels[0]
             e.scale = envmap.get("scale", old.scale)
             e.to_world[:] = [float(v) for v in np.asarray(envmap["to_world"], np.float32).reshape(-1)] if "to_world" in envmap else list(old.to_world)

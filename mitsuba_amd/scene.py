@@ -66,6 +66,42 @@ def mip_pyramid(level0):
     return out
 
 
+WRAP_MODES = {"clamp": A.PHIP_WRAP_CLAMP, "repeat": A.PHIP_WRAP_REPEAT, "mirror": A.PHIP_WRAP_MIRROR, "zero": A.PHIP_WRAP_ZERO, "one": A.PHIP_WRAP_ONE}
+
+
+def pyramid_sizes(w, h):
+    """[(h, w)] of every level of a complete pyramid, level 0 first (mipmap.h:182-192)"""
+    out = [(h, w)]
+    while w > 1 or h > 1:
+        w, h = max(1, (w + 1) // 2), max(1, (h + 1) // 2)
+        out.append((h, w))
+    return out
+
+
+def mip_pyramid_lanczos(level0, wrap_u="repeat", wrap_v=None, max_value=1.0):
+    """MIP levels of an (H, W, 3) image exactly as the reference's TMIPMap builds and stores them (phip_mip_pyramid: the two-lobe Lanczos resampler per axis, every
+    level from the float32 level before it, clamped to [0, max_value], stored in half precision) -- level 0 included, which comes back clamped at 0 and rounded.
+    wrap_u / wrap_v: "clamp", "repeat", "mirror", "zero", "one" or the PHIP_WRAP_* value; a texture takes its own wrap modes and max_value 1, an environment map
+    repeat x clamp and infinity.  Runs on the host: no GPU is needed."""
+    from . import _ffi
+    t = np.ascontiguousarray(level0, dtype=np.float32)
+    assert t.ndim == 3 and t.shape[2] == 3
+    sizes = pyramid_sizes(t.shape[1], t.shape[0])
+    out = [np.empty((h, w, 3), np.float32) for h, w in sizes]
+    p = A.phip_pyramid_desc()
+    p.width, p.height, p.n_levels = t.shape[1], t.shape[0], len(sizes)
+    p.wrap_u = WRAP_MODES.get(wrap_u, wrap_u)
+    p.wrap_v = p.wrap_u if wrap_v is None else WRAP_MODES.get(wrap_v, wrap_v)
+    p.max_value = max_value
+    p.d_level0 = t.ctypes.data
+    for l, o in enumerate(out):
+        p.d_levels[l] = o.ctypes.data
+    rc = _ffi.lib().phip_mip_pyramid(C.byref(p))
+    if rc != 0:
+        raise _ffi.PhipError(rc, "phip_mip_pyramid")
+    return out
+
+
 class SceneBuilder:
     def __init__(self):
         self.positions = []      # list of (n,3) float32
@@ -96,13 +132,18 @@ class SceneBuilder:
     def bitmap(self, image, wrap="repeat", wrap_v=None, filter_type="ewa", max_anisotropy=20.0,
                uscale=1.0, vscale=1.0, uoffset=0.0, voffset=0.0, pyramid=True):
         """<texture type="bitmap">: `image` = (H, W, 3) float RGB in [0, 1] as the plugin stores MIP level 0; the pyramid
-        comes from `mip_pyramid` (or pass the levels) unless the filter is nearest / bilinear."""
-        wraps = {"repeat": A.PHIP_WRAP_REPEAT, "clamp": A.PHIP_WRAP_CLAMP, "mirror": A.PHIP_WRAP_MIRROR, "zero": A.PHIP_WRAP_ZERO, "one": A.PHIP_WRAP_ONE}
+        comes from `mip_pyramid` (or pass the levels; pyramid="lanczos": the reference's own levels from `mip_pyramid_lanczos`, level 0 included) unless the filter
+        is nearest / bilinear."""
+        wraps = WRAP_MODES
         filters = {"nearest": A.PHIP_FILTER_NEAREST, "bilinear": A.PHIP_FILTER_BILINEAR, "trilinear": A.PHIP_FILTER_TRILINEAR, "ewa": A.PHIP_FILTER_EWA}
         t = np.ascontiguousarray(image, dtype=np.float32)
         assert t.ndim == 3 and t.shape[2] == 3
         need = filter_type in ("trilinear", "ewa")          # mipmap.h:182-192: nearest / bilinear keep a single level
-        levels = (mip_pyramid(t) if pyramid is True else [t] + [np.ascontiguousarray(l, np.float32) for l in pyramid[1:]]) if need else [t]
+        if isinstance(pyramid, str):
+            assert pyramid == "lanczos", pyramid
+            levels = mip_pyramid_lanczos(t, wrap, wrap_v or wrap, 1.0) if need else [t]
+        else:
+            levels = (mip_pyramid(t) if pyramid is True else [t] + [np.ascontiguousarray(l, np.float32) for l in pyramid[1:]]) if need else [t]
         self.textures.append({"levels": levels, "wrap_u": wraps[wrap], "wrap_v": wraps[wrap_v or wrap], "filter": filters[filter_type],
                               "aniso": float(max_anisotropy), "scale": (float(uscale), float(vscale)), "offset": (float(uoffset), float(voffset))})
         return len(self.textures) - 1
@@ -176,9 +217,15 @@ class SceneBuilder:
         """<emitter type="envmap">: lat-long radiance map (src/emitters/envmap.cpp); `texels` = (H, W, 3) float RGB
         (MIP level 0 as the reference stores it), `to_world` = 4x4 emitter-to-world (rotation).  `pyramid=True` adds
         the MIP levels the filtered background lookup needs (the Mitsuba shim passes the plugin's own Lanczos pyramid;
-        this harness builds a box-filtered one with `mip_pyramid` -- product and oracle consume the same levels)."""
+        this harness builds a box-filtered one with `mip_pyramid` -- product and oracle consume the same levels); pyramid="lanczos": the
+        reference's own levels (`mip_pyramid_lanczos` with repeat x clamp and no upper bound), level 0 included."""
         t = np.ascontiguousarray(texels, dtype=np.float32)
         assert t.ndim == 3 and t.shape[2] == 3
+        if isinstance(pyramid, str):
+            assert pyramid == "lanczos", pyramid
+            levels = mip_pyramid_lanczos(t, "repeat", "clamp", float("inf"))
+            t = levels[0]
+            pyramid = levels
         levels = mip_pyramid(t) if pyramid is True else ([t] + [np.ascontiguousarray(l, np.float32) for l in pyramid[1:]] if pyramid else [t])
         self._envmap = (t, float(scale), np.eye(4, dtype=np.float32) if to_world is None else np.asarray(to_world, np.float32).reshape(4, 4), levels)
         self.emitters.append({"radiance": (0.0, 0.0, 0.0), "weight": sampling_weight, "shape": 0xFFFFFFFF,
