@@ -700,6 +700,35 @@ int phip_mip_pyramid_device(phip_scene *scene, const phip_pyramid_desc *desc);
    the levels are the device call's bit for bit; the refusals are the same but for the device's. */
 int phip_mip_pyramid(const phip_pyramid_desc *desc);
 
+/* The vertex normals of a mesh exactly as the reference's TriMesh::computeNormals makes them for a mesh loaded without normals (trimesh.cpp:640-672: every corner
+   adds its triangle's unit normal times its own angle -- Thuermer and Wuethrich's weighting, unitAngle of core/util.h:309-314 --, the sum runs in triangle order, a
+   vertex whose sum has length 0 gets (1, 0, 0) and is counted), from positions in DEVICE memory into caller-allocated normals in device memory: what
+   phip_update_desc.normals takes with device_pointers = 1.  The topology is the scene's own, as created; the scene gives the device too and keeps the incidence
+   lists of its vertices from its first call on (the call takes the render lock); it is not changed otherwise.  The bits are those of the host call
+   phip_vertex_normals below, and the reference's own but for glibc's asinf.  m_flipNormals is not restated: a caller negates.
+   Positions are not validated: non-finite input gives non-finite normals, which phip_scene_update then refuses as it does today.
+   Refusals, PHIP_ERR_INVALID, all before anything is written: a NULL scene or desc, NULL positions or normals, counts that are not the scene's, indices that are
+   not NULL, a pointer that is not 4-byte aligned, positions and normals that overlap, a pointer that is not device memory of the scene's device.
+   PHIP_ERR_DEVICE without a GPU. */
+typedef struct phip_normals_desc {
+    uint32_t n_vertices, n_triangles;   /* device call: must equal the scene's counts */
+    const uint32_t *indices;            /* host call: 3 * n_triangles, host memory; device call: must be NULL (the scene's own) */
+    const float *positions;             /* 3 * n_vertices; host call: host memory; device call: device memory of the scene's device */
+    float *normals;                     /* 3 * n_vertices out, same memory kind; every vertex is written */
+    void *stream;                       /* device call: the producer's hipStream_t or NULL; the call is ordered after it and complete on return */
+    uint32_t reserved[2];
+} phip_normals_desc;
+typedef struct phip_normals_info {
+    uint32_t n_invalid;                 /* vertices without a contribution: they got (1, 0, 0) */
+    uint32_t reserved;
+    double kernel_ms;                   /* device call: the kernel in HIP-event time; host call: 0 */
+} phip_normals_info;
+int phip_vertex_normals_device(phip_scene *scene, const phip_normals_desc *desc, phip_normals_info *out_info /* may be NULL */);
+/* The same normals on HOST memory, without a device: the same statements run (normals_hd.h), so the normals are the device call's bit for bit.  Any indices do,
+   also those of several meshes in one array.  Refusals, PHIP_ERR_INVALID, before anything is written: a NULL desc, NULL positions, normals or (with triangles)
+   indices, n_vertices == 0, a pointer that is not 4-byte aligned, positions and normals that overlap, an index >= n_vertices. */
+int phip_vertex_normals(const phip_normals_desc *desc, phip_normals_info *out_info /* may be NULL */);
+
 /* Thread-safe and sticky, like Scheduler::cancel on a process (src/libcore/sched.cpp): a running phip_render returns
    PHIP_ERR_CANCELLED; a request that arrives before the render starts cancels that render.  The flag is consumed by the
    call that observes it. */
@@ -730,7 +759,7 @@ int  phip_scene_accel_info(const phip_scene *scene, phip_accel_info *out);
 /* Utilities for callers that fill a phip_scene_desc without Mitsuba at hand (the test harness, bench.py): the table of the reference's default `gaussian` reconstruction
  * filter with the given standard deviation -- (radius, PHIP_FILTER_RESOLUTION + 1 values), rfilter.cpp:38-57 + gaussian.cpp:34-57; the Mitsuba shim copies the scene's own
  * filter instead -- and sizeof of the ABI's structs by index (0 phip_material, 1 phip_shape, 2 phip_emitter, 3 phip_camera, 4 phip_film, 5 phip_scene_desc,
- * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info, 11 phip_update_desc, 12 phip_update_info, 13 phip_surface, 15 phip_radiance_desc; 14 is unassigned and answers 0: tests/test_raycast_device_host.py pins phip_abi_sizeof(14) == 0 as "one past the last struct" and stays as it is, so the new struct skips that index; 16 is unassigned likewise: tests/test_radiance_device_host.py pins it; 17 phip_camera_rays_desc, 18 phip_film_desc; 19 is unassigned likewise: tests/test_camera_film_host.py pins it; 20 phip_appearance_desc, 21 phip_appearance_info; 22 is unassigned likewise: tests/test_appearance_host.py pins it; 23 phip_bsdf_desc, 24 phip_bsdf_sample, 25 phip_emitter_sample_desc, 26 phip_emitter_sample, 27 phip_emitter_eval_desc; 28 is unassigned likewise: tests/test_shading_parts_host.py pins it; 29 phip_pyramid_desc), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
+ * 6 phip_render_params, 7 phip_stats, 8 phip_ray, 9 phip_hit, 10 phip_accel_info, 11 phip_update_desc, 12 phip_update_info, 13 phip_surface, 15 phip_radiance_desc; 14 is unassigned and answers 0: tests/test_raycast_device_host.py pins phip_abi_sizeof(14) == 0 as "one past the last struct" and stays as it is, so the new struct skips that index; 16 is unassigned likewise: tests/test_radiance_device_host.py pins it; 17 phip_camera_rays_desc, 18 phip_film_desc; 19 is unassigned likewise: tests/test_camera_film_host.py pins it; 20 phip_appearance_desc, 21 phip_appearance_info; 22 is unassigned likewise: tests/test_appearance_host.py pins it; 23 phip_bsdf_desc, 24 phip_bsdf_sample, 25 phip_emitter_sample_desc, 26 phip_emitter_sample, 27 phip_emitter_eval_desc; 28 is unassigned likewise: tests/test_shading_parts_host.py pins it; 29 phip_pyramid_desc; 30 is unassigned likewise: tests/test_pyramid_host.py pins it; 31 phip_normals_desc, 32 phip_normals_info), for bindings that mirror them (tests/test_abi.py holds the ctypes mirror against it). */
 void   phip_gaussian_filter(float stddev, float *radius, float *table);
 size_t phip_abi_sizeof(int which);
 

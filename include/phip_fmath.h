@@ -86,6 +86,7 @@ PM_FN float pm_expf(float x) { return __expf(x); }
 PM_FN float pm_logf(float xx) { return __logf(xx); }
 PM_FN float pm_powf(float x, float y) { return x == 0.0f ? (y > 0.0f ? 0.0f : 1.0f) : __expf(y * __logf(x)); }
 PM_FN float pm_acosf(float x) { return acosf(x); }
+PM_FN float pm_asinf(float x) { return asinf(x); }
 PM_FN float pm_atanf(float xx) { return atanf(xx); }
 PM_FN float pm_atan2f(float y, float x) { return atan2f(y, x); }
 PM_FN float pm_tanf(float xx) { return tanf(xx); }
@@ -215,6 +216,14 @@ PM_FN float pm_acosf(float x) {
     return (float) pmd_atan2(sqrt((1.0 - xd) * (1.0 + xd)), xd);     /* (1 - x) and (1 + x) are exact in double */
 }
 
+/* arcsine over [-1, 1] (unitAngle, core/util.h:309-314, calls it on [0, 1]): atan(x / sqrt(1 - x^2)), the quotient pmd_atan2 forms; 1 gives pi / 2 from its x == 0 branch */
+PM_FN float pm_asinf(float x) {
+    if (x < -1.0f || x > 1.0f || x != x) return pm_from_bits(0x7fc00000u);
+    if (x == 0.0f) return x;
+    double xd = (double) x;
+    return (float) pmd_atan2(xd, sqrt((1.0 - xd) * (1.0 + xd)));     /* (1 - x) and (1 + x) are exact in double */
+}
+
 PM_FN float pm_atanf(float xx) {
     if (xx != xx) return xx;
     return (float) pmd_atan((double) xx);
@@ -324,6 +333,13 @@ PM_FN float pm_acosf(float x) {
     float a = fabsf(x);
     float r = pm_asinf_core(a);
     return PM_PI_2 - (x < 0.0f ? -r : r);
+}
+
+PM_FN float pm_asinf(float x) {
+    if (x < -1.0f || x > 1.0f || x != x) return pm_from_bits(0x7fc00000u);
+    float a = fabsf(x);
+    float r = a > 0.5f ? PM_PI_2 - 2.0f * pm_asinf_core(sqrtf(0.5f * (1.0f - a))) : pm_asinf_core(a);
+    return x < 0.0f ? -r : r;
 }
 
 PM_FN float pm_atanf(float xx) {

@@ -237,6 +237,15 @@ class phip_pyramid_desc(C.Structure):
                 ("max_value", C.c_float), ("d_level0", C.c_void_p), ("d_levels", C.c_void_p * PHIP_MIP_MAX_LEVELS), ("stream", C.c_void_p)]
 
 
+class phip_normals_desc(C.Structure):
+    _fields_ = [("n_vertices", C.c_uint32), ("n_triangles", C.c_uint32), ("indices", C.c_void_p), ("positions", C.c_void_p), ("normals", C.c_void_p),
+                ("stream", C.c_void_p), ("reserved", C.c_uint32 * 2)]
+
+
+class phip_normals_info(C.Structure):
+    _fields_ = [("n_invalid", C.c_uint32), ("reserved", C.c_uint32), ("kernel_ms", C.c_double)]
+
+
 def default_render_params(**kw):
     """MonteCarloIntegrator defaults (src/librender/integrator.cpp:190-225)."""
     p = phip_render_params()

@@ -61,6 +61,8 @@ UNITS += [("phip_appearance.hip", [], "phip_appearance.o")]
 UNITS += [("phip_shading_parts.hip", [], "phip_shading_parts.o")]
 # phip_pyramid.hip (the kernels of phip_mip_pyramid_device, k_pyramid.h): one small object, inserted likewise
 UNITS += [("phip_pyramid.hip", [], "phip_pyramid.o")]
+# phip_normals.hip (the kernel of phip_vertex_normals_device, k_normals.h): one small object, inserted likewise
+UNITS += [("phip_normals.hip", [], "phip_normals.o")]
 # phip_update.hip (the refit kernels of phip_scene_update, k_update.h): one small object, appended likewise
 UNITS += [("phip_update.hip", [], "phip_update.o")]
 # phip_rebuild.hip (the device build of phip_scene_rebuild, k_rebuild.h, with rocPRIM's sort and scan): one object, appended likewise
@@ -148,7 +150,7 @@ def _build_locked(sid, out_lib, verbose):
             return 13.0
         if name.startswith("phip_raycast"):
             return 5.0
-        if name.startswith("phip_camera_film") or name.startswith("phip_appearance") or name.startswith("phip_pyramid"):
+        if name.startswith("phip_camera_film") or name.startswith("phip_appearance") or name.startswith("phip_pyramid") or name.startswith("phip_normals"):
             return 3.0
         if name.startswith("phip_shading_parts"):
             return 12.0
@@ -191,9 +193,9 @@ TEST_VARIANTS = {"fault": "-DMEGA_MB_FAULT=1",       # waves of fused launches r
                  "overflow": "-DWP_CAP=64u -DWP_SPILL_CAP=64u",      # 128-entry task stacks, half of them spilled: the tree-in-memory scenes outgrow them -- the wave stops, the pass is re-rendered
                  "notail": "-DPYRAMID_TAIL=0"}       # not a test's: tools/gpu_pyramid.py measures phip_mip_pyramid_device without its single-block tail kernel (host_pyramid.h)
 # sources whose objects a variant takes from the product build: its flags do not concern them (the task stacks are k_mega's and k_shade_trace_w's)
-VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip phip_pyramid.hip", "cap32": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip phip_pyramid.hip",
-                 "overflow": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip phip_pyramid.hip",
-                 "notail": "phip_shade.hip phip_shade_w.hip phip_mega.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip phip_pyramid.hip"}
+VARIANT_REUSE = {"fault": "phip_shade.hip phip_shade_w.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip phip_pyramid.hip phip_normals.hip", "cap32": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip phip_pyramid.hip phip_normals.hip",
+                 "overflow": "phip_shade.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip phip_pyramid.hip phip_normals.hip",
+                 "notail": "phip_shade.hip phip_shade_w.hip phip_mega.hip phip_update.hip phip_rebuild.hip phip_raycast.hip phip_shade_r.hip phip_camera_film.hip phip_appearance.hip phip_shading_parts.hip phip_pyramid.hip phip_normals.hip"}
 
 
 def build_test_variant(tag):
@@ -249,6 +251,8 @@ def lib():
     L.phip_scene_update_appearance.argtypes = [C.c_void_p, C.POINTER(A.phip_appearance_desc), C.POINTER(A.phip_appearance_info)]
     L.phip_mip_pyramid_device.argtypes = [C.c_void_p, C.POINTER(A.phip_pyramid_desc)]
     L.phip_mip_pyramid.argtypes = [C.POINTER(A.phip_pyramid_desc)]
+    L.phip_vertex_normals_device.argtypes = [C.c_void_p, C.POINTER(A.phip_normals_desc), C.POINTER(A.phip_normals_info)]
+    L.phip_vertex_normals.argtypes = [C.POINTER(A.phip_normals_desc), C.POINTER(A.phip_normals_info)]
     L.phip_develop.argtypes = [fp, C.c_size_t, fp]
     L.phip_scene_accel_info.argtypes = [C.c_void_p, C.POINTER(A.phip_accel_info)]
     L.phip_gaussian_filter.argtypes = [C.c_float, fp, fp]
@@ -313,6 +317,8 @@ def debug_lib():
     L.phip_debug_host_emitter_sample_args.argtypes = [C.c_int, C.POINTER(A.phip_emitter_sample_desc)]
     L.phip_debug_host_emitter_eval_args.argtypes = [C.c_int, C.POINTER(A.phip_emitter_eval_desc)]
     L.phip_debug_host_pyramid_args.argtypes = [C.c_int, C.POINTER(A.phip_pyramid_desc)]
+    L.phip_debug_host_normals_args.argtypes = [C.c_int, u32, u32, C.POINTER(A.phip_normals_desc)]
+    L.phip_debug_host_asinf.argtypes = [C.c_size_t, fp, fp]
     L.phip_debug_host_bsdf_parts.argtypes = [C.POINTER(A.phip_scene_desc), C.POINTER(A.phip_bsdf_desc)]
     L.phip_debug_host_emitter_sample.argtypes = [C.POINTER(A.phip_scene_desc), C.POINTER(A.phip_emitter_sample_desc)]
     L.phip_debug_host_emitter_eval.argtypes = [C.POINTER(A.phip_scene_desc), C.POINTER(A.phip_emitter_eval_desc)]

@@ -1,7 +1,7 @@
 /*
  * host_boundary.h -- what a call on the caller's device memory needs, stated once: whose memory a pointer is, how it is aligned, how many items one call takes,
  * the stream its work is ordered on, the device its parameters name, a device's CU count, one block per BLOCK items, a refusal under its call's name.
- * The per-call headers (host_raycast.h, host_radiance.h, host_camera_film.h, host_shading_parts.h, host_pyramid.h, host_update.h, host_appearance.h) and host_render.h use these
+ * The per-call headers (host_raycast.h, host_radiance.h, host_camera_film.h, host_shading_parts.h, host_pyramid.h, host_normals.h, host_update.h, host_appearance.h) and host_render.h use these
  * and keep the texts of their own refusals; the guard that brings an entry point to its body is phip.hip's (onDevice).
  * Host code only; included by phip.hip alone, after host_scene.h.
  */

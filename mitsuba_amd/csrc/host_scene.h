@@ -143,6 +143,9 @@ struct SceneDev {
     struct RadiancePlan { ShadeRaysKernel vertex[2] = { nullptr, nullptr }; RadianceOutKernel out = nullptr; } radiance;
     DevBuf<double2> radianceAcc;
     DevBuf<float> pyramidScratch;                                                           /* phip_mip_pyramid_device (host_pyramid.h): the float32 chain and the X-pass temporary; grow-only */
+    /* phip_vertex_normals_device (host_normals.h): the incidence lists of the scene's vertices (a CSR over its indices: offsets, entries in ascending order), its own
+       copy of the indices, the count of invalid vertices and the two events of kernel_ms; made at the scene's first call, valid for its life (the topology is fixed) */
+    struct NormalsState { DevBuf<uint32_t> offsets, entries, indices; DevBuf<unsigned int> invalid; hipEvent_t t0 = nullptr, t1 = nullptr; bool ready = false; } normals;
     DevBuf<float> film, patchImg;                                                           /* patchImg: k_film_splat's 16 x 16 patch images (k_film.h) */
     uint32_t lastSpp = 0, nLocalTiles = 0; unsigned long long localPixels = 0;
     int tileKey[3] = { -1, -1, -1 };
@@ -171,6 +174,8 @@ struct SceneDev {
         (void) hipSetDevice(device);
         if (stream) (void) hipStreamDestroy(stream);
         for (int i = 0; i < 2; ++i) { if (stage[i]) (void) hipHostFree(stage[i]); if (stageDone[i]) (void) hipEventDestroy(stageDone[i]); }
+        if (normals.t0) (void) hipEventDestroy(normals.t0);
+        if (normals.t1) (void) hipEventDestroy(normals.t1);
     }
 };
 

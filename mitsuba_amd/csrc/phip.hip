@@ -15,7 +15,7 @@
  *       iteration that shades a slot's vertex and traces its shadow ray and its next ray on the packed leaf table in LDS (k_shade_trace.h); scenes of that
  *       kind whose tree lives in L2: k_shade_trace_w, the same iteration on the 8-wide tree in memory (k_shade_trace_w.h)
  *
- * libphip.so is 49 objects of twelve sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
+ * libphip.so is 50 objects of thirteen sources (phip_common.h).  The other units export look-ups that return their kernels; this unit maps a render to one of them once,
  * at plan time (host_render.h -- shadeUnit: the one table over the feature sets; megaKernelOf -> FusedPlan::kernel in planFused, shadeKernelOf / shadeTraceWideKernelOf ->
  * WavefrontPlan::vertex / vertexWide in selectVertexKernel), asks the runtime for the residency of the persistent ones (residentBlocksPerCU) and launches them.
  * Kernels and where they live:
@@ -41,6 +41,8 @@
  *                 classes of the Wald records (appearance_hd.h: the arithmetic the creation shares)                                                          [phip_appearance.hip]
  *   k_pyramid.h   phip_mip_pyramid_device: level 0 into the float32 chain, one pass of one resampling step, the pyramid's tail in one block's LDS (pyramid_hd.h: the
  *                 statements the host call phip_mip_pyramid runs too)                                                                                 [phip_pyramid.hip]
+ *   k_normals.h   phip_vertex_normals_device: one lane per vertex gathers its corners' angle-weighted face normals in the reference's order (normals_hd.h: the
+ *                 statements the host call phip_vertex_normals runs too)                                                                              [phip_normals.hip]
  *   k_raycast.h   phip_trace_device: k_raycast_p (k_wide.h's persistent loop on a caller's ray array), k_surfaces (the record at every hit)            [phip_raycast.hip]
  *   k_shade_r.h   phip_radiance_device: k_shade_r (k_shade with a caller's ray array as its source of samples), k_radiance_out (the mean of a ray's samples)  [phip_shade_r.hip]
  *   k_camera_film.h  phip_camera_rays_device / phip_film_device: k_camera_rays (the camera samples of the counter stream), k_film_values (k_film's gather on a
@@ -68,7 +70,9 @@
  *   host_shading_parts.h phip_bsdf_device, phip_emitter_sample_device and phip_emitter_eval_device: the BSDF at the hits of a ray cast, emitter sampling and emitter
  *                  evaluation on the caller's arrays (k_shading_parts.h in phip_shading_parts.hip)
  *   host_pyramid.h phip_mip_pyramid_device and phip_mip_pyramid: the reference's MIP pyramid from a level 0 in device / host memory (k_pyramid.h in phip_pyramid.hip)
- * Each of the last five holds its call's checks of the arguments that need no device (`*ArgsError`, `*Refusal`: all of them come before any launch) and its body.
+ *   host_normals.h phip_vertex_normals_device and phip_vertex_normals: the reference's angle-weighted vertex normals from positions in device / host memory
+ *                  (k_normals.h in phip_normals.hip)
+ * Each of the last six holds its call's checks of the arguments that need no device (`*ArgsError`, `*Refusal`: all of them come before any launch) and its body.
  * Not MFMA work: irregular traversal and gathers.  The product never includes, links or calls anything under oracle/.
  */
 #include "phip_common.h"
@@ -109,6 +113,7 @@ static int setErr(int code, const std::string &msg) { g_err = msg; return code; 
 #include "host_camera_film.h"
 #include "host_shading_parts.h"
 #include "host_pyramid.h"
+#include "host_normals.h"
 
 /* Entry of both render functions: validation, the scene's render lock, single- or multi-device dispatch, the sticky
    cancellation flag (consumed by the call that observed it). */
@@ -457,6 +462,12 @@ int phip_mip_pyramid_device(phip_scene *scene, const phip_pyramid_desc *desc) {
     return onDevice(DEVICE_ERRORS, scene, "phip_mip_pyramid_device", [&] { return mipPyramidDevice(scene, desc); });
 }
 
+int phip_vertex_normals_device(phip_scene *scene, const phip_normals_desc *desc, phip_normals_info *out_info) {
+    if (const int rc = normalsRefusal(scene != nullptr, scene ? scene->upd.nVertices : 0u, scene ? scene->upd.nTriangles : 0u, desc)) return rc;
+    if (out_info) memset(out_info, 0, sizeof(*out_info));
+    return onDevice(DEVICE_ERRORS, scene, "phip_vertex_normals_device", [&] { return vertexNormalsDevice(scene, desc, out_info); });
+}
+
 void phip_cancel(phip_scene *scene) { if (scene && scene->cancelFlag) __atomic_store_n(scene->cancelFlag, 1, __ATOMIC_RELAXED); }
 
 void phip_develop(const float *rgbaw, size_t n_pixels, float *out_rgb) {
@@ -503,6 +514,13 @@ int phip_mip_pyramid(const phip_pyramid_desc *desc) {
     return guarded(DEVICE_ERRORS, [&]() -> int { mipPyramidHost(desc); return PHIP_OK; });
 }
 
+/* TriMesh::computeNormals on host memory (host_normals.h, normals_hd.h): the twin of phip_vertex_normals_device's kernel */
+int phip_vertex_normals(const phip_normals_desc *desc, phip_normals_info *out_info) {
+    if (const int rc = normalsHostRefusal(desc)) return rc;
+    if (out_info) memset(out_info, 0, sizeof(*out_info));
+    return guarded(DEVICE_ERRORS, [&]() -> int { vertexNormalsHost(desc, out_info); return PHIP_OK; });
+}
+
 size_t phip_abi_sizeof(int which) {
     switch (which) {
         case 0: return sizeof(phip_material);
@@ -530,6 +548,8 @@ size_t phip_abi_sizeof(int which) {
         case 26: return sizeof(phip_emitter_sample);
         case 27: return sizeof(phip_emitter_eval_desc);
         case 29: return sizeof(phip_pyramid_desc);       /* (28 likewise) */
+        case 31: return sizeof(phip_normals_desc);       /* (30 likewise) */
+        case 32: return sizeof(phip_normals_info);
         default: return 0;
     }
 }

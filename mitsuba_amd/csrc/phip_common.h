@@ -2,7 +2,7 @@
  * phip_common.h -- what every translation unit of libphip.so starts with: HIP, the C ABI, the device scene layout and
  * shading functions (dv_scene.h), the path-pool layout (k_pool.h), the error macro.
  *
- * libphip.so is built from twelve sources (49 objects) so that they compile in parallel:
+ * libphip.so is built from thirteen sources (50 objects) so that they compile in parallel:
  *   phip.hip          the C ABI + traversal and film kernels, with the host side it includes by concern: host_scene.h (scene build, replicas), host_boundary.h (what
  *                     a call on the caller's device memory needs), host_render.h (kernel selection, one device's render loop), host_multi.h (multi-device
  *                     orchestration, RCCL) and one header per entry point on the caller's device memory: 1 object
@@ -21,6 +21,7 @@
  *   phip_shading_parts.hip  the kernels of phip_bsdf_device, phip_emitter_sample_device and phip_emitter_eval_device (k_shading_parts.h) behind
  *                     phipShadingPartsKernels: 1 object
  *   phip_pyramid.hip  the kernels of phip_mip_pyramid_device (k_pyramid.h) behind phipPyramidKernels: 1 object
+ *   phip_normals.hip  the kernel of phip_vertex_normals_device (k_normals.h) behind phipNormalsKernels: 1 object
  * The other units hold kernels and the look-ups that return them, nothing else: every launch and every query of the runtime is in phip.hip and its host headers
  * (but for the launches inside rocPRIM's sort and scan, which phip_rebuild.hip wraps).
  * No device function is called across units (everything on the device side is inline in headers), so no -fgpu-rdc.
@@ -149,3 +150,9 @@ struct PyramidKernels {
     void (*tail)(const float *, int, int, int, PyramidOuts, uint32_t, uint32_t, float);
 };
 PyramidKernels phipPyramidKernels();
+/* the kernel of phip_vertex_normals_device (phip_normals.hip, k_normals.h): (incidence offsets, incidence entries, the scene's indices, positions, vertex count,
+   normals out, the count of invalid vertices) */
+struct NormalsKernels {
+    void (*vertexNormals)(const uint32_t *, const uint32_t *, const uint32_t *, const float *, uint32_t, float *, unsigned int *);
+};
+NormalsKernels phipNormalsKernels();

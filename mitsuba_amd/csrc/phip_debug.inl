@@ -725,6 +725,17 @@ extern "C" int phip_debug_host_pyramid_args(int have_scene, const phip_pyramid_d
     return pyramidDeviceRefusal(have_scene != 0, desc);
 }
 
+/* phip_vertex_normals_device's checks of the arguments (host_normals.h) likewise, against the counts a scene would have */
+extern "C" int phip_debug_host_normals_args(int have_scene, uint32_t scene_vertices, uint32_t scene_triangles, const phip_normals_desc *desc) {
+    return normalsRefusal(have_scene != 0, scene_vertices, scene_triangles, desc);
+}
+
+/* pm_asinf (phip_fmath.h) on the host: phip_debug_fmath's kernel does not know it -- on the device k_vertex_normals alone calls it */
+extern "C" int phip_debug_host_asinf(size_t n, const float *a, float *out) {
+    for (size_t i = 0; i < n; ++i) out[i] = pm_asinf(a[i]);
+    return PHIP_OK;
+}
+
 /* The DevScene of a descriptor on the host: the stages phip_scene_create runs before it uploads (none of them calls HIP) -- shapes, textures, materials, emitters,
    the tree (for the scene box the environment emitter's sphere is made of), shading records, the emitter table, the environment map's tables -- with the
    DevScene's pointers bound to the builder's arrays instead of device buffers.  What the items of k_shading_parts.h read of a scene is all there. */

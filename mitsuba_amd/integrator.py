@@ -277,6 +277,20 @@ class Scene:
             self.desc.camera = camera
         return info
 
+    def vertex_normals(self, positions, out=None, stream=None, info=False):
+        """The vertex normals of the scene's meshes at new positions as the reference's TriMesh::computeNormals makes them, on the scene's device
+        (phip_vertex_normals_device; the host call of the same bits: scene.vertex_normals_angle_weighted).  positions: a contiguous (n_vertices, 3) float32 tensor
+        on the scene's device; out: a tensor of the same kind to write into, or None (allocated); stream: the stream the positions' producer ran on.  Returns the
+        normals -- what Scene.update(positions, normals) takes next --, with info=True also the phip_normals_info (n_invalid, kernel_ms)."""
+        import torch
+        n = self.desc.n_vertices
+        positions = self._device_tensor(positions, "positions", 3, rows=n)
+        out = torch.empty((n, 3), dtype=torch.float32, device=positions.device) if out is None else self._device_tensor(out, "out", 3, rows=n)
+        d = A.phip_normals_desc(n_vertices=n, n_triangles=self.desc.n_triangles, indices=None, positions=_ptr(positions), normals=_ptr(out), stream=_stream_handle(stream))
+        inf = A.phip_normals_info()
+        _check(self._L.phip_vertex_normals_device(self._h, C.byref(d), C.byref(inf)), "phip_vertex_normals_device")
+        return (out, inf) if info else out
+
     def mip_pyramid(self, level0, wrap_u="repeat", wrap_v=None, max_value=1.0, out=None, stream=None):
         """The MIP pyramid of a texture or an environment map as the reference's TMIPMap builds and stores it, on the scene's device (phip_mip_pyramid_device; the
         host call of the same bits: scene.mip_pyramid_lanczos).  level0: a contiguous (h, w, 3) float32 tensor on the scene's device.  wrap_u / wrap_v: "clamp",

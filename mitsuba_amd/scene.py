@@ -102,6 +102,22 @@ def mip_pyramid_lanczos(level0, wrap_u="repeat", wrap_v=None, max_value=1.0):
     return out
 
 
+def vertex_normals_angle_weighted(P, T, return_invalid=False):
+    """Vertex normals of the mesh (P: (n, 3) positions, T: (m, 3) indices) exactly as the reference's TriMesh::computeNormals makes them for a mesh loaded without
+    normals (phip_vertex_normals: every corner adds its triangle's unit normal times its angle, in triangle order; a vertex nothing contributes to gets (1, 0, 0)).
+    Returns the (n, 3) float32 normals, with return_invalid=True also the number of vertices that got (1, 0, 0).  Runs on the host: no GPU is needed."""
+    from . import _ffi
+    P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1, 3)
+    T = np.ascontiguousarray(T, dtype=np.uint32).reshape(-1, 3)
+    N = np.empty_like(P)
+    d = A.phip_normals_desc(n_vertices=len(P), n_triangles=len(T), indices=T.ctypes.data if len(T) else None, positions=P.ctypes.data, normals=N.ctypes.data)
+    info = A.phip_normals_info()
+    rc = _ffi.lib().phip_vertex_normals(C.byref(d), C.byref(info))
+    if rc != 0:
+        raise _ffi.PhipError(rc, "phip_vertex_normals")
+    return (N, int(info.n_invalid)) if return_invalid else N
+
+
 class SceneBuilder:
     def __init__(self):
         self.positions = []      # list of (n,3) float32
@@ -189,6 +205,9 @@ class SceneBuilder:
     def mesh(self, positions, triangles, material, normals=None, radiance=None, sampling_weight=1.0, uvs=None):
         positions = _f32(positions).reshape(-1, 3)
         triangles = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+        if isinstance(normals, str):         # normals="angle": the reference's own for a mesh loaded without normals (vertex_normals_angle_weighted)
+            assert normals == "angle", normals
+            normals = vertex_normals_angle_weighted(positions, triangles)
         if normals is not None:
             normals = _f32(normals).reshape(-1, 3)
             assert normals.shape == positions.shape
